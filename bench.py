@@ -2,6 +2,7 @@
 """Headline benchmark: env-steps/sec (rollout + update), PPO-Lag on SafetyPointGoal1 shapes.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full               # + secondary legs and CPU baselines
     python bench.py --gpus N --steps K --warmup W      # launches its own N ranks (one per GPU, RCCL), like the
                                                        # reference's fork(): omnisafe/utils/distributed.py:121-137
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -16,10 +17,16 @@ SafetyPointGoal1-v0, 1xMI355X, 4096 vectorized envs, steps_per_epoch=65536"); we
 owns 4096 envs, steps_per_epoch = 65 536 x world_size; under data parallelism the rollouts are all-gathered
 once per epoch and every rank runs the whole global optimiser chain (no per-step collective, profiles/HISTORY.md §5).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (ms of one timed epoch), the
+configuration and
   roofline     dominant kernel (osa_ppo_pass_kernel: one persistent launch = one whole pass of 1024 dependent
                64-row optimiser steps of all three networks), algorithmic FLOPs / mean launch time measured
                with HIP events in the timed region
+A plain run does only that: set up, warm up (--warmup epochs), time --steps epochs, print.  `--dump-outputs DIR`
+also writes what the last timed epoch computed (parameters after the update, the batch it consumed, the Lagrange
+multiplier) as DIR/*.npy; the inputs are seeded, so equal arguments give equal inputs.  `--full` adds what takes runs
+of its own: the measured cost of the skipped KL passes, the secondary legs (allreduce_mode and p2p_mode under
+--gpus N, kl_early_stop_epoch), and
   cpu_baseline the UNMODIFIED REFERENCE (kind "reference": omnisafe.Agent('PPOLag', device=cpu).learn() from the staged
                archive oracle/_ref/omnisafe_ref.zip) timed on this box's host cores on a bounded sample of the same
                workload (--ref-sample-iters of the 40 passes executed, the passes scaled; `full_epoch_value` = the
@@ -89,7 +96,7 @@ def parse():
     # data-parallel update mode of the headline line under --gpus N > 1 (omnisafe_amd/update.py): 'replicated' (default:
     # rollouts all-gathered once per epoch, every GPU runs the whole global optimiser chain, no per-step collective),
     # 'replicated-steps', 'allreduce' (per optimiser step: gradient kernel -> ONE flat RCCL all-reduce -> Adam: the
-    # reference's structure, policy_gradient.py:437-443).  With N > 1 the line also carries an `allreduce_mode` object
+    # reference's structure, policy_gradient.py:437-443).  With N > 1 and --full the line carries an `allreduce_mode` object
     # (the same workload in the per-step all-reduce mode, --allreduce-steps epochs) unless --no-allreduce-leg, and the
     # large-batch `throughput_variant` (one flat RCCL all-reduce per step inside the captured update graph).
     # 'p2p' (round 6): every rank runs the single-GPU persistent pass on its own rows; clipped gradients exchanged by
@@ -105,6 +112,11 @@ def parse():
     # the N = 1 value of the same command (env-steps/s): adds efficiency_vs_n1 = value / (N x n1) to the line
     ap.add_argument('--n1-value', type=float, default=None)
     ap.add_argument('--n1-variant-value', type=float, default=None)
+    # everything beyond the headline: the measured KL-pass cost, the secondary legs (all-reduce, p2p, early-stop,
+    # large-batch variant) and the CPU baselines.  Without it a run sets up, warms up, times --steps epochs and prints
+    ap.add_argument('--full', action='store_true')
+    # write what the last timed epoch computed (parameters after the update, the batch it consumed, lambda) as DIR/*.npy
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None)
     return ap.parse_args()
 
 
@@ -460,6 +472,39 @@ def kl_pass_us(algo, dev, reps=20):
         return None
 
 
+DUMP_BYTES = 64 << 20  # cap of --dump-outputs; a larger batch is written as a fixed, seeded sample of its rows
+
+
+def dump_outputs(algo, out_dir):
+    """What the last timed epoch returned to its caller: the three networks' parameters after the update
+    (`params`: actor, reward critic, cost critic), the env-major batch the update consumed (rollout + GAE +
+    standardisation: `batch_<key>`) and, for the Lagrangian algorithms, the multiplier.  float32 as computed,
+    the multiplier float64.  The inputs are seeded (config seed 0), so equal arguments give equal inputs."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    data = getattr(algo, '_last_update_data', None) or dict(algo._buf._out)
+    arrays = {'params': algo._actor_critic.params.detach().float().cpu().numpy()}
+    for k in sorted(data):
+        arrays[f'batch_{k}'] = data[k].detach().float().cpu().numpy()
+    lag = getattr(algo, '_lagrange', None)
+    if lag is not None and hasattr(lag, 'lagrangian_multiplier'):
+        arrays['lagrange_multiplier'] = np.array([float(lag.lagrangian_multiplier)], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        rows = {a.shape[0] for k, a in arrays.items() if k.startswith('batch_')}
+        assert len(rows) == 1, rows
+        m = rows.pop()
+        fixed = total - sum(a.nbytes for k, a in arrays.items() if k.startswith('batch_'))
+        row_bytes = (total - fixed) // m + 8  # (+ its float64 entry in batch_sample_rows)
+        keep = max(1, min(m, (DUMP_BYTES - fixed) // row_bytes))
+        idx = np.sort(np.random.default_rng(0).choice(m, size=keep, replace=False))
+        arrays = {k: (a[idx] if k.startswith('batch_') else a) for k, a in arrays.items()}
+        arrays['batch_sample_rows'] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and 'RANK' not in os.environ and int(os.environ.get('WORLD_SIZE', '1')) == 1:
@@ -494,6 +539,8 @@ def main():
     algo._updater.profile_events = None
     if hasattr(algo, '_solver'):
         algo._solver.profile_events = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(algo, args.dump_outputs)
     per_gpu_steps = args.envs * args.steps_per_env
     value = world * per_gpu_steps * args.steps / dt
     out = {
@@ -561,7 +608,7 @@ def main():
     # (without early stop only the last pass's KL is evaluated; with it, one per pass: update.py)
     out['whole_path'] = whole_path(args, value, world, args.update_iters,
                                    args.update_iters if args.kl_early_stop else 1)
-    if not args.kl_early_stop and args.algo == 'PPOLag':
+    if args.full and not args.kl_early_stop and args.algo == 'PPOLag':
         # Work NOT done in the timed region against the reference's loop: the reference evaluates the full-batch KL after
         # EVERY pass (policy_gradient.py:383-390); with kl_early_stop off only the last value is observable (logged
         # Train/KL), so the earlier update_iters - 1 passes are not computed.  Their cost, measured:
@@ -572,7 +619,8 @@ def main():
             out['config']['kl_passes_skipped_frac_of_epoch'] = round((args.update_iters - 1) * us * 1e-3 /
                                                                       (dt / args.steps * 1e3), 5)
     headline_mode = os.environ.get('OSA_DP_MODE', 'replicated')
-    if world > 1 and not args.no_allreduce_leg and headline_mode != 'allreduce' and args.algo == 'PPOLag':
+    # (the legs below run under --full only: a plain run reports the headline and the roofline of its own timed launches)
+    if args.full and world > 1 and not args.no_allreduce_leg and headline_mode != 'allreduce' and args.algo == 'PPOLag':
         try:
             # the same workload in the reference's own structure: per optimiser step gradient kernel -> ONE flat RCCL
             # all-reduce of the three networks' clipped gradients -> Adam (policy_gradient.py:437-443 with 1 message for 19);
@@ -605,7 +653,7 @@ def main():
             out['allreduce_mode'] = {'error': repr(exc)[:400]}
             os.environ['OSA_DP_MODE'] = headline_mode
             algo = None
-    if world > 1 and not args.no_p2p_leg and headline_mode != 'p2p' and args.algo == 'PPOLag' and not general:
+    if args.full and world > 1 and not args.no_p2p_leg and headline_mode != 'p2p' and args.algo == 'PPOLag' and not general:
         try:
             # the same workload with the one-shot peer exchange (round 6): each rank runs the single-GPU persistent pass on
             # its own rows, the clipped gradients travel by peer writes into hipIpc-mapped buffers -- no collective and no
@@ -644,7 +692,8 @@ def main():
             out['p2p_mode'] = {'error': repr(exc)[:400]}
             os.environ['OSA_DP_MODE'] = headline_mode
             algo = None
-    if world == 1 and not args.no_early_stop_leg and args.algo == 'PPOLag' and not args.kl_early_stop and not general:
+    if (args.full and world == 1 and not args.no_early_stop_leg and args.algo == 'PPOLag' and not args.kl_early_stop
+            and not general):
         try:
             # the YAML default `kl_early_stop: true` (PPOLag.yaml; SURVEY 8d's parity variant): one full-batch KL pass AND
             # one host synchronisation per pass.  (a) target_kl at the YAML's 0.02: the update stops where the reference's
@@ -678,7 +727,7 @@ def main():
             out['kl_early_stop_epoch'] = {'error': repr(exc)[:400]}
             os.environ['OSA_DP_MODE'] = headline_mode
             algo = None
-    if not args.no_variant and args.algo == 'PPOLag':
+    if args.full and not args.no_variant and args.algo == 'PPOLag':
         try:
             # the large-batch setting on EVERY rank (round 4): under world_size > 1 the update is the data-parallel
             # large-batch pass -- partial gradients, local clip, ONE flat RCCL all-reduce, Adam per step, the whole pass
@@ -716,7 +765,7 @@ def main():
             out['throughput_variant'] = {'error': repr(exc)[:400]}
             os.environ['OSA_DP_MODE'] = headline_mode
             algo = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         port = cpu_baseline(args)
         ref = cpu_baseline_reference(args)
         if ref is not None and 'error' not in ref:

@@ -28,15 +28,16 @@ def test_config_defaults_match_reference_yaml_values():
     assert c['algo_cfgs']['cost_limit'] == 25.0 and 'lagrange_cfgs' not in c
 
 
-@pytest.mark.reference
-def test_config_defaults_equal_reference_yaml():
-    """Every default of the three accelerated algorithms equals the reference's YAML ``defaults``."""
-    import yaml
+def test_config_defaults_equal_reference_yaml(golden_dir):
+    """Every default of the three accelerated algorithms equals the reference's YAML ``defaults`` (the snapshot
+    tests/golden/config_defaults.json that oracle/make_golden.py writes from the YAML files)."""
+    import json
 
     from omnisafe_amd.config import get_default_kwargs
 
+    ref_all = json.load(open(os.path.join(golden_dir, 'config_defaults.json')))
     for algo in ('PPOLag', 'TRPOLag', 'CPO'):
-        ref = yaml.safe_load(open(f'/root/reference/omnisafe/configs/on-policy/{algo}.yaml'))['defaults']
+        ref = ref_all[algo]
         mine = get_default_kwargs(algo)
 
         def walk(r, m, path):

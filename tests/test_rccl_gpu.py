@@ -331,7 +331,8 @@ def test_bench_launches_its_own_ranks(tmp_path):
     else:
         env.pop('OSA_SINGLE_DEVICE_RANKS', None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '1', '--warmup', '2', '--envs',
-           '256', '--update-iters', '2', '--allreduce-steps', '1', '--variant-batch', '2048', '--n1-value', '50000']
+           '256', '--update-iters', '2', '--allreduce-steps', '1', '--variant-batch', '2048', '--n1-value', '50000',
+           '--full']
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

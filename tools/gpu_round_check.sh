@@ -20,22 +20,22 @@ mkdir -p $O
 SQ="SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES"
 if [[ $STAGES == *1* ]]; then
 timeout 1500 python -m pytest tests -q -m gpu --tb=short --show-capture=no 2>&1 | tail -60 > $O/${T}_final_pytest.log; tail -4 $O/${T}_final_pytest.log
-timeout 600 python bench.py > $O/${T}_bench_final.json 2> $O/${T}_bench_final.err; tail -c 600 $O/${T}_bench_final.json
+timeout 600 python bench.py --full > $O/${T}_bench_final.json 2> $O/${T}_bench_final.err; tail -c 600 $O/${T}_bench_final.json
 # (the driver's own command line: bench.py launches its two ranks itself; one device -> gloo, a code-path check)
-OSA_SINGLE_DEVICE_RANKS=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 2 --update-iters 8 --allreduce-update-iters 1 > $O/${T}_bench_2ranks_on_1gpu.json 2> $O/${T}_bench_2rank.err; tail -c 400 $O/${T}_bench_2ranks_on_1gpu.json
+OSA_SINGLE_DEVICE_RANKS=1 timeout 900 python bench.py --full --gpus 2 --steps 2 --warmup 2 --update-iters 8 --allreduce-update-iters 1 > $O/${T}_bench_2ranks_on_1gpu.json 2> $O/${T}_bench_2rank.err; tail -c 400 $O/${T}_bench_2ranks_on_1gpu.json
 fi
 cd /tmp && export TMPDIR=/tmp
 if [[ $STAGES == *2* ]]; then
 rm -rf $O/${T}_prof $O/${T}_pmc_*
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python $R/bench.py --steps 2 --warmup 2 --no-cpu-baseline > $O/${T}_prof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python $R/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline > $O/${T}_prof.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/${T}_pmc_bench_$c -- python $R/bench.py --steps 1 --warmup 2 --update-iters 4 --no-cpu-baseline --no-variant > $O/${T}_pmc_bench_$c.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/${T}_pmc_variant_$c -- python $R/bench.py --steps 1 --warmup 3 --batch-size 16384 --update-iters 8 --no-cpu-baseline --no-variant > $O/${T}_pmc_variant_$c.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/${T}_pmc_bench_$c -- python $R/bench.py --full --steps 1 --warmup 2 --update-iters 4 --no-cpu-baseline --no-variant > $O/${T}_pmc_bench_$c.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/${T}_pmc_variant_$c -- python $R/bench.py --full --steps 1 --warmup 3 --batch-size 16384 --update-iters 8 --no-cpu-baseline --no-variant > $O/${T}_pmc_variant_$c.log 2>&1
 done
 python $R/tools/pmc_summary.py $O/${T}_pmc_bench_FETCH_SIZE $O/${T}_pmc_bench_WRITE_SIZE $O/${T}_pmc_traffic_bench | head -12
 python $R/tools/pmc_summary.py $O/${T}_pmc_variant_FETCH_SIZE $O/${T}_pmc_variant_WRITE_SIZE $O/${T}_pmc_traffic_variant | head -12
-timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/${T}_pmc_sq_bench -- python $R/bench.py --steps 1 --warmup 2 --update-iters 2 --no-cpu-baseline --no-variant > $O/${T}_pmc_sq_bench.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/${T}_pmc_sq_variant -- python $R/bench.py --steps 1 --warmup 3 --batch-size 16384 --update-iters 8 --no-cpu-baseline --no-variant > $O/${T}_pmc_sq_variant.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/${T}_pmc_sq_bench -- python $R/bench.py --full --steps 1 --warmup 2 --update-iters 2 --no-cpu-baseline --no-variant > $O/${T}_pmc_sq_bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc $SQ --output-format csv -d $O/${T}_pmc_sq_variant -- python $R/bench.py --full --steps 1 --warmup 3 --batch-size 16384 --update-iters 8 --no-cpu-baseline --no-variant > $O/${T}_pmc_sq_variant.log 2>&1
 python $R/tools/pmc_sq_summary.py $O/${T}_pmc_sq_bench $O/${T}_pmc_sq_mfma_busy_bench | head -20
 python $R/tools/pmc_sq_summary.py $O/${T}_pmc_sq_variant $O/${T}_pmc_sq_mfma_busy_variant | head -20
 rm -rf $O/${T}_pmc_bench_* $O/${T}_pmc_variant_* $O/${T}_pmc_sq_bench $O/${T}_pmc_sq_variant
@@ -57,7 +57,7 @@ for A in CPO TRPOLag; do
 done
 fi
 if [[ $STAGES == *4* ]]; then
-cd $R; timeout 900 python bench.py --hidden-sizes 1024 1024 --update-iters 1 --steps 2 --no-cpu-baseline > $O/${T}_bench_hidden1024.json 2> $O/${T}_bench_hidden1024.err; tail -c 900 $O/${T}_bench_hidden1024.json
+cd $R; timeout 900 python bench.py --full --hidden-sizes 1024 1024 --update-iters 1 --steps 2 --no-cpu-baseline > $O/${T}_bench_hidden1024.json 2> $O/${T}_bench_hidden1024.err; tail -c 900 $O/${T}_bench_hidden1024.json
 timeout 600 python tools/general_mlp_timing.py --out $O/${T}_general_mlp_timing.json 2>&1 | grep -v amdgpu
 OSA_GMLP_SKINNY=0 timeout 300 python tools/general_mlp_timing.py --shapes 1024x1024:64 512x512x512:64 256x128:64 --out $O/${T}_general_mlp_timing_tiled_B64.json 2>&1 | grep -v amdgpu
 cd /tmp; rm -rf $O/${T}_prof_gm $O/${T}_pmc_sq_gm
