@@ -65,6 +65,24 @@ __host__ __device__ inline OsaNet osa_make_net(int obs_dim, int act_dim, int hid
   return n;
 }
 
+// The operands the fused-family entry points (OsaPassArgs, OsaWideArgs, OsaSplitArgs, OsaMbArgs) take from their
+// common C-ABI arguments; the rows of the launch (perm / idx, M, B, nmb) and everything else are the caller's.
+// nets_mask: without the cost critic unless hp->use_cost.
+template <class Args>
+static inline void osa_fill_operands(Args& a, int obs_dim, int act_dim, int hidden, float* params, float* adam_m,
+                                     float* adam_v, int* adam_step, const float* obs, int ld_obs, const float* act,
+                                     int ld_act, const float* logp, const float* tgt_r, const float* tgt_c,
+                                     const float* adv_r, const float* adv_c, const float* lagrange,
+                                     const osa_ppo_hparams* hp, int loss_kind, int nets_mask, float* stats) {
+  a.nd = osa_make_net(obs_dim, act_dim, hidden);
+  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
+  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
+  a.tgt_r = tgt_r; a.tgt_c = tgt_c; a.adv_r = adv_r; a.adv_c = adv_c;
+  a.lagrange = lagrange;
+  osa_copy_hparams(a.hp, hp);
+  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = stats;
+}
+
 // tanh = 1 - 2 / (1 + e^{2x}) on the hardware exp2 / rcp units: 2 transcendental + 3 plain VALU ops
 // per element, no branch, saturates correctly (e^{2x} -> inf gives 1, -> 0 gives -1).  Absolute error
 // <= ~1.5e-7 (one ulp of 1.0) everywhere; ocml's tanhf costs ~5x as much and dominated the forward

@@ -1293,18 +1293,11 @@ int osa_ppo_minibatch_ext(int obs_dim, int act_dim, int hidden, float* params, f
     a.ext_ratio_scale = ext->ratio_scale; a.ext_cost_kappa = ext->cost_kappa;
     a.ext_cost_excess = ext->cost_excess;
   }
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step; a.grads = grads;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.idx = idx; a.B = B; a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.lr_dev = hp->lr_device; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.mode = mode; a.stats = step_stats; a.loss_kind = loss_kind;
-  a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3);
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.hp.lr_dev = hp->lr_device;
+  a.grads = grads; a.idx = idx; a.B = B;
+  a.mode = mode;
   a.dbg = g_osa_dbg_clocks;
   a.vec = nullptr; a.fvp_scale = 0.f;
   const int spc = osa_mb_spc(a.nd);

@@ -20,6 +20,32 @@
 
 static inline hipStream_t osa_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// osa_ppo_hparams as the fused-family kernels take it by value (the persistent, wide and split passes)
+struct OsaPassHp {
+  float clip, entropy_coef, critic_norm_coef, max_grad_norm;
+  float lr_actor, lr_critic, beta1, beta2, adam_eps;
+  int use_critic_norm, use_max_grad_norm, use_cost;
+};
+
+// osa_ppo_hparams -> OsaPassHp, or mlp_kernels.hip's OsaHp (the same leading fields)
+template <class Hp>
+static inline void osa_copy_hparams(Hp& h, const osa_ppo_hparams* hp) {
+  h.clip = hp->clip; h.entropy_coef = hp->entropy_coef;
+  h.critic_norm_coef = hp->critic_norm_coef; h.max_grad_norm = hp->max_grad_norm;
+  h.lr_actor = hp->lr_actor; h.lr_critic = hp->lr_critic; h.beta1 = hp->beta1;
+  h.beta2 = hp->beta2; h.adam_eps = hp->adam_eps; h.use_critic_norm = hp->use_critic_norm;
+  h.use_max_grad_norm = hp->use_max_grad_norm; h.use_cost = hp->use_cost;
+}
+
+// Observation rows the fused kernels take: 16-byte aligned with a leading dimension of whole float4s (pad the rows),
+// and `rows` x ld_obs (x ld_act where given) below `limit` elements -- the kernels index rows in int32 (limit 2^31;
+// 4 x that where they index in float4s).  false: OSA_EUNSUPPORTED.
+static inline bool osa_rows_ok(const float* obs, int ld_obs, double rows, int ld_act = 0,
+                               double limit = 2147483647.0) {
+  return ld_obs % 4 == 0 && (reinterpret_cast<uintptr_t>(obs) & 15) == 0 && rows * ld_obs < limit &&
+         rows * ld_act < limit;
+}
+
 // "done once PER DEVICE": hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current device only, and a
 // process may drive more than one (the launch of a > 64 KB LDS kernel on a second device would otherwise fail)
 struct OsaPerDeviceOnce {

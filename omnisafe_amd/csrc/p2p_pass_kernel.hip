@@ -29,32 +29,12 @@ __global__ __launch_bounds__(256, 1) void osa_ppo_p2p_pass_kernel(OsaPassArgs a)
   osa_ppo_pass_body<KB, OT, MULTI, true, false, false, false, SO, true>(a, net, a.p2p_rank);
 }
 
-static size_t osa_p2p_lds_bytes(int KB, int OT) {
-  const size_t fl = (size_t)osa_pass_lds_floats(KB, OT) + (osa_pass_has_w2t(KB, OT) ? 64 * PSLD : 0);
-  return fl * sizeof(float);
-}
-
-template <int KB, int OT, bool MULTI, bool SO>
-static int osa_launch_p2p(const OsaPassArgs& a, hipStream_t stream) {
-  static OsaPerDeviceOnce attr_set;
-  const size_t lds = osa_p2p_lds_bytes(KB, OT);
-  if (lds > 160 * 1024) return OSA_EUNSUPPORTED;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&osa_ppo_p2p_pass_kernel<KB, OT, MULTI, SO>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return OSA_EHIP;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((osa_ppo_p2p_pass_kernel<KB, OT, MULTI, SO>), dim3(17), dim3(256), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
-}
-
+// the SO instantiation where it applies, on the 17-block grid
 template <int KB, int OT, bool MULTI>
 static int osa_launch_p2p_so(const OsaPassArgs& a, hipStream_t stream) {
-  if constexpr (OT == 1) {
-    if (a.nd.act_dim <= 2) return osa_launch_p2p<KB, OT, MULTI, true>(a, stream);
-  }
-  return osa_launch_p2p<KB, OT, MULTI, false>(a, stream);
+  return osa_pass_so<OT>(a.nd, [&](auto SO) {
+    return osa_launch_pass_kernel<osa_ppo_p2p_pass_kernel<KB, OT, MULTI, SO>>(a, dim3(17), stream);
+  });
 }
 
 // exchange buffers of this process: own allocations (base, bytes) and peers' buffers opened through IPC handles
@@ -160,8 +140,7 @@ int osa_ppo_p2p_pass(int obs_dim, int act_dim, int hidden, float* params, float*
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats && peers);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && rank >= 0 && rank < world);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim && timeout_s > 0.0);
-  if ((double)M * ld_obs >= 2147483647.0 || (double)M * ld_act >= 2147483647.0) return OSA_EUNSUPPORTED;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad rows
+  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act)) return OSA_EUNSUPPORTED;
   OsaPassArgs a = {};
   for (int q = 0; q < world; ++q) {
     OSA_REQUIRE(peers[q] != nullptr && osa_p2p_slot(peers[q]) >= 0);  // only buffers this library allocated / opened
@@ -177,28 +156,16 @@ int osa_ppo_p2p_pass(int obs_dim, int act_dim, int hidden, float* params, float*
     a.p2p_fence = sysf ? 1 : 0;
   }
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B); a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
-  a.dbg = osa_pass_dbg_ptr(); a.dp_slabs = nullptr; a.dp_world = world; a.mb0 = 0; a.dp_sync = nullptr; a.part_stride = 0;
-  a.dp_uncached = 1; a.dp_local = 0; a.dp_chunk = 0; a.dp_ranks = 1; a.one_xcc = 1;
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
+  a.dbg = osa_pass_dbg_ptr(); a.dp_world = world;
+  a.dp_uncached = 1; a.dp_ranks = 1; a.one_xcc = 1;
   const int KB = a.nd.KB, OT = a.nd.OUTP / 16;
   hipStream_t st = osa_stream(stream);
-#define OSA_P2P_CASE(K, O) \
-  if (KB == K && OT == O) return (B > 64) ? osa_launch_p2p_so<K, O, true>(a, st) : osa_launch_p2p_so<K, O, false>(a, st)
-  OSA_P2P_CASE(1, 1); OSA_P2P_CASE(2, 1); OSA_P2P_CASE(3, 1); OSA_P2P_CASE(4, 1); OSA_P2P_CASE(5, 1);
-  OSA_P2P_CASE(6, 1); OSA_P2P_CASE(1, 2); OSA_P2P_CASE(2, 2); OSA_P2P_CASE(3, 2); OSA_P2P_CASE(4, 2);
-  OSA_P2P_CASE(5, 2); OSA_P2P_CASE(6, 2);
-#undef OSA_P2P_CASE
-  return OSA_EUNSUPPORTED;
+  return osa_pass_shapes(KB, OT, [&](auto K, auto O) {
+    return (B > 64) ? osa_launch_p2p_so<K, O, true>(a, st) : osa_launch_p2p_so<K, O, false>(a, st);
+  });
 }
 
 }  // extern "C"

@@ -10,11 +10,6 @@
 #endif
 #include "ppo_pass_body.h"
 
-static size_t osa_part_lds_bytes(int KB, int OT) {
-  const size_t fl = (size_t)osa_pass_lds_floats(KB, OT) + (osa_pass_has_w2t(KB, OT) ? 64 * PSLD : 0);
-  return fl * sizeof(float);
-}
-
 // Balanced partial gradients of ONE large minibatch (OsaPassArgs.part_tpw): see there.
 template <int KB, int OT, bool SO>
 __global__ __launch_bounds__(256, 1) void osa_ppo_part_kernel(OsaPassArgs a) {
@@ -56,21 +51,6 @@ __global__ __launch_bounds__(256, 1) void osa_ppo_part_kernel(OsaPassArgs a) {
 }
 
 
-template <int KB, int OT, bool SO>
-static int osa_launch_part(const OsaPassArgs& a, hipStream_t stream, int G) {
-  static OsaPerDeviceOnce attr_set;
-  const size_t lds = osa_part_lds_bytes(KB, OT);
-  if (lds > 160 * 1024) return OSA_EUNSUPPORTED;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&osa_ppo_part_kernel<KB, OT, SO>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return OSA_EHIP;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((osa_ppo_part_kernel<KB, OT, SO>), dim3(G), dim3(256), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
-}
-
 static long long* g_osa_part_dbg = nullptr;
 extern "C" int osa_debug_set_part_clock_buffer(long long* dev_ptr) {
   g_osa_part_dbg = dev_ptr;
@@ -87,7 +67,7 @@ int osa_pass_partial_grad_balanced(int obs_dim, int act_dim, int hidden, float* 
                                    int loss_kind, int nets_mask, int max_wg, int max_stride, float* slabs,
                                    int* nslab, int* stride, void* stream) {
   if (!osa_ppo_pass_supported(obs_dim, act_dim, hidden) || B <= 64) return OSA_EUNSUPPORTED;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, 0.0)) return OSA_EUNSUPPORTED;  // (alignment only: one minibatch of B rows)
   const int nchunk = (B + 63) / 64, nq = __builtin_popcount(nets_mask & 7);
   if (nq == 0 || max_wg < 1) return OSA_EUNSUPPORTED;
   const long ntasks = (long)nq * nchunk;
@@ -107,35 +87,25 @@ int osa_pass_partial_grad_balanced(int obs_dim, int act_dim, int hidden, float* 
   *stride = st;
   OsaPassArgs a = {};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = params; a.adam_v = params; a.adam_step = nullptr;  // untouched in this mode
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = idx; a.M = B; a.B = B; a.nmb = 1; a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask; a.stats = nullptr;
-  a.dbg = g_osa_part_dbg; a.dp_slabs = slabs; a.dp_world = st; a.mb0 = 0; a.dp_sync = nullptr;
-  a.part_stride = -1; a.part_tpw = tpw; a.dp_uncached = 0;
+  // Adam state untouched in this mode
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, params, params, nullptr, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, nullptr);
+  a.nets_mask = nets_mask;  // as given: the caller (osa_ppo_minibatch_ext) has applied use_cost already
+  a.perm = idx; a.M = B; a.B = B; a.nmb = 1;
+  a.dbg = g_osa_part_dbg; a.dp_slabs = slabs; a.dp_world = st;
+  a.part_stride = -1; a.part_tpw = tpw;
   const int KB = a.nd.KB, OT = a.nd.OUTP / 16;
   hipStream_t s = osa_stream(stream);
-#define OSA_PB_CASE(K, O)                                                                  \
-  if (KB == K && OT == O) {                                                                \
-    if constexpr (O == 1) {                                                                \
-      if (a.nd.act_dim <= 2) return osa_launch_part<K, O, true>(a, s, G);                  \
-    }                                                                                      \
-    return osa_launch_part<K, O, false>(a, s, G);                                          \
-  }
+  const auto launch = [&](auto K, auto O) {
+    return osa_pass_so<O>(a.nd, [&](auto SO) {
+      return osa_launch_pass_kernel<osa_ppo_part_kernel<K, O, SO>>(a, dim3(G), s);
+    });
+  };
 #ifdef OSA_PART_QUICK  // (one instantiation: register-pressure experiments)
-  OSA_PB_CASE(4, 1)
+  if (KB != 4 || OT != 1) return OSA_EUNSUPPORTED;
+  return launch(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{});
 #else
-  OSA_PB_CASE(1, 1) OSA_PB_CASE(2, 1) OSA_PB_CASE(3, 1) OSA_PB_CASE(4, 1) OSA_PB_CASE(5, 1) OSA_PB_CASE(6, 1)
-  OSA_PB_CASE(1, 2) OSA_PB_CASE(2, 2) OSA_PB_CASE(3, 2) OSA_PB_CASE(4, 2) OSA_PB_CASE(5, 2) OSA_PB_CASE(6, 2)
+  return osa_pass_shapes(KB, OT, launch);
 #endif
-#undef OSA_PB_CASE
-  return OSA_EUNSUPPORTED;
 }
 

@@ -37,12 +37,6 @@
 #define PSPAD (PSLD - 64)
 #define PNSTAT 16
 
-struct OsaPassHp {
-  float clip, entropy_coef, critic_norm_coef, max_grad_norm;
-  float lr_actor, lr_critic, beta1, beta2, adam_eps;
-  int use_critic_norm, use_max_grad_norm, use_cost;
-};
-
 struct OsaPassArgs {
   OsaNet nd;
   float* params;   // [3][P] padded global layout
@@ -1650,3 +1644,74 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
   (void)out_dim;
 }
 
+
+// ---- host side of the pass launchers (ppo_pass_kernel.hip, p2p_pass_kernel.hip, part_grad_kernel.hip) ----------
+#include <type_traits>
+
+static inline size_t osa_pass_lds_bytes(int KB, int OT) {
+  const size_t fl = (size_t)osa_pass_lds_floats(KB, OT) + (osa_pass_has_w2t(KB, OT) ? 64 * PSLD : 0);
+  return fl * sizeof(float);
+}
+
+// Calls f(std::integral_constant<int, KB>, std::integral_constant<int, OT>) for the shape (KB = 1..6 input blocks,
+// OT = 1..2 output tiles) the pass kernels are instantiated for; OSA_EUNSUPPORTED for any other.
+template <int I = 0, class F>
+static int osa_pass_shapes(int KB, int OT, F&& f) {
+  if constexpr (I == 12) {
+    return OSA_EUNSUPPORTED;
+  } else {
+    constexpr int K = I % 6 + 1, O = I / 6 + 1;
+    if (KB == K && OT == O) return f(std::integral_constant<int, K>{}, std::integral_constant<int, O>{});
+    return osa_pass_shapes<I + 1>(KB, OT, f);
+  }
+}
+
+// Calls f(std::true_type) for the single-output instantiation where it applies (one output tile and act_dim <= 2:
+// every network then has 1-2 outputs), f(std::false_type) otherwise.
+template <int OT, class F>
+static int osa_pass_so(const OsaNet& nd, F&& f) {
+  if constexpr (OT == 1) {
+    if (nd.act_dim <= 2) return f(std::true_type{});
+  }
+  return f(std::false_type{});
+}
+
+// Launches the pass-kernel instantiation K on `grid` with the dynamic LDS of a's shape, raising K's LDS limit once
+// per device.  COOP: the workgroups meet at arrival counters every step, so they MUST be co-resident -- a
+// cooperative launch makes the runtime verify that (occupancy x CUs >= grid) instead of inferring it from the CU
+// count, and refuses the launch otherwise (OSA_EUNSUPPORTED: the caller takes the stepwise path).
+// (OSA_DP_PLAIN_LAUNCH=1: A/B switch of tools/dp_timing.py -- plain launch behind the occupancy check)
+template <auto K, bool COOP = false>
+static int osa_launch_pass_kernel(const OsaPassArgs& a, dim3 grid, hipStream_t stream) {
+  static OsaPerDeviceOnce attr_set;
+  const size_t lds = osa_pass_lds_bytes(a.nd.KB, a.nd.OUTP / 16);
+  if (lds > 160 * 1024) return OSA_EUNSUPPORTED;
+  if (attr_set.need()) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024) != hipSuccess)
+      return OSA_EHIP;
+    attr_set.set();
+  }
+  if constexpr (COOP) {
+    static bool coop_refused = getenv("OSA_DP_PLAIN_LAUNCH") != nullptr && getenv("OSA_DP_PLAIN_LAUNCH")[0] == '1';
+    if (!coop_refused) {
+      OsaPassArgs arg = a;
+      void* kargs[] = {&arg};
+      const hipError_t e =
+          hipLaunchCooperativeKernel(reinterpret_cast<const void*>(K), grid, dim3(256), kargs, (unsigned)lds, stream);
+      if (e == hipSuccess) return OSA_OK;
+      (void)hipGetLastError();
+      if (e == hipErrorCooperativeLaunchTooLarge) return OSA_EUNSUPPORTED;
+      coop_refused = true;
+    }
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(K), 256, lds) !=
+            hipSuccess ||
+        hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return OSA_EHIP;
+    if ((long)per_cu * cus < (long)grid.x * grid.y) return OSA_EUNSUPPORTED;
+  }
+  hipLaunchKernelGGL(K, grid, dim3(256), lds, stream, a);
+  return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
+}

@@ -30,61 +30,20 @@ static long long* g_osa_pass_dbg = nullptr;
 // (library-internal: the phase-clock buffer for the other translation units that instantiate the pass body)
 long long* osa_pass_dbg_ptr() { return g_osa_pass_dbg; }
 
-static size_t osa_pass_lds_bytes(int KB, int OT) {
-  const size_t fl = (size_t)osa_pass_lds_floats(KB, OT) + (osa_pass_has_w2t(KB, OT) ? 64 * PSLD : 0);
-  return fl * sizeof(float);
-}
-
+// osa_ppo_pass_kernel<...> on its grid: 3 x grid_y, blocks 0, 8, 16 of 17 (one_xcc), 8 x grid_y (COOP, dp_local 1)
 template <int KB, int OT, bool MULTI, bool COOP = false, bool EXT = false, bool HIER = false, bool DPS = false,
           bool SO = false>
 static int osa_launch_pass(const OsaPassArgs& a, hipStream_t stream, int grid_y = 1) {
   const dim3 grid = (COOP && a.dp_local == 1) ? dim3(8 * grid_y) : ((!COOP && a.one_xcc) ? dim3(17) : dim3(3, grid_y));
-  static OsaPerDeviceOnce attr_set;
-  const size_t lds = osa_pass_lds_bytes(KB, OT);
-  if (lds > 160 * 1024) return OSA_EUNSUPPORTED;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&osa_ppo_pass_kernel<KB, OT, MULTI, COOP, EXT, HIER, DPS, SO>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return OSA_EHIP;
-    attr_set.set();
-  }
-  if constexpr (COOP) {
-    // the 3 x world workgroups meet at an arrival counter every step, so they MUST be co-resident: a
-    // cooperative launch makes the runtime verify that (occupancy x CUs >= grid) instead of inferring it
-    // from the CU count, and refuses the launch otherwise
-    // (OSA_DP_PLAIN_LAUNCH=1: A/B switch of tools/dp_timing.py -- plain launch behind the occupancy check)
-    static bool coop_refused = getenv("OSA_DP_PLAIN_LAUNCH") != nullptr && getenv("OSA_DP_PLAIN_LAUNCH")[0] == '1';
-    if (!coop_refused) {
-      OsaPassArgs arg = a;
-      void* kargs[] = {&arg};
-      const hipError_t e = hipLaunchCooperativeKernel(
-          reinterpret_cast<const void*>(&osa_ppo_pass_kernel<KB, OT, MULTI, COOP, EXT, HIER, DPS, SO>), grid,
-          dim3(256), kargs, (unsigned)lds, stream);
-      if (e == hipSuccess) return OSA_OK;
-      (void)hipGetLastError();
-      if (e == hipErrorCooperativeLaunchTooLarge) return OSA_EUNSUPPORTED;  // caller takes the stepwise path
-      coop_refused = true;
-    }
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, reinterpret_cast<const void*>(&osa_ppo_pass_kernel<KB, OT, MULTI, COOP, EXT, HIER, DPS, SO>), 256, lds) !=
-            hipSuccess ||
-        hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return OSA_EHIP;
-    if ((long)per_cu * cus < (long)grid.x * grid.y) return OSA_EUNSUPPORTED;
-  }
-  hipLaunchKernelGGL((osa_ppo_pass_kernel<KB, OT, MULTI, COOP, EXT, HIER, DPS, SO>), grid, dim3(256), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
+  return osa_launch_pass_kernel<osa_ppo_pass_kernel<KB, OT, MULTI, COOP, EXT, HIER, DPS, SO>, COOP>(a, grid, stream);
 }
 
 // the SO instantiation where it applies (one output tile and act_dim <= 2: every network then has 1-2 outputs)
 template <int KB, int OT, bool MULTI, bool COOP = false, bool EXT = false, bool HIER = false>
 static int osa_launch_pass_so(const OsaPassArgs& a, hipStream_t stream, int grid_y = 1) {
-  if constexpr (OT == 1) {
-    if (a.nd.act_dim <= 2) return osa_launch_pass<KB, OT, MULTI, COOP, EXT, HIER, false, true>(a, stream, grid_y);
-  }
-  return osa_launch_pass<KB, OT, MULTI, COOP, EXT, HIER>(a, stream, grid_y);
+  return osa_pass_so<OT>(a.nd, [&](auto SO) {
+    return osa_launch_pass<KB, OT, MULTI, COOP, EXT, HIER, false, SO>(a, stream, grid_y);
+  });
 }
 
 extern "C" {
@@ -121,23 +80,14 @@ int osa_ppo_pass_ext(int obs_dim, int act_dim, int hidden, float* params, float*
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
-  if ((double)M * ld_obs >= 2147483647.0 || (double)M * ld_act >= 2147483647.0) return OSA_EUNSUPPORTED;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad rows
+  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act)) return OSA_EUNSUPPORTED;
   OsaPassArgs a = {};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B); a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
   a.dbg = g_osa_pass_dbg;
-  a.dp_slabs = nullptr; a.dp_world = 1; a.mb0 = 0; a.dp_sync = nullptr; a.part_stride = 0; a.dp_uncached = 0;
+  a.dp_world = 1;
   {  // OSA_PASS_ONE_XCC=0: the three workgroups on three XCCs (A/B switch; traffic: profiles/r3_pmc_traffic*)
     static const bool one = !(getenv("OSA_PASS_ONE_XCC") && getenv("OSA_PASS_ONE_XCC")[0] == '0');
     a.one_xcc = one ? 1 : 0;
@@ -155,24 +105,12 @@ int osa_ppo_pass_ext(int obs_dim, int act_dim, int hidden, float* params, float*
       a.old_mean = ext->old_mean; a.ld_old_mean = ext->ld_old_mean; a.old_log_std = ext->old_log_std;
       a.ext_kl_coef = ext->kl_coef; a.ext_mask_eta = ext->kl_mask_eta; a.ext_ratio_scale = ext->ratio_scale;
       a.ext_cost_kappa = ext->cost_kappa; a.ext_cost_excess = ext->cost_excess;
-#define OSA_PASS_EXT_CASE(K, O) \
-  if (KB == K && OT == O) return osa_launch_pass_so<K, O, false, false, true>(a, st)
-      OSA_PASS_EXT_CASE(1, 1); OSA_PASS_EXT_CASE(2, 1); OSA_PASS_EXT_CASE(3, 1); OSA_PASS_EXT_CASE(4, 1);
-      OSA_PASS_EXT_CASE(5, 1); OSA_PASS_EXT_CASE(6, 1);
-      OSA_PASS_EXT_CASE(1, 2); OSA_PASS_EXT_CASE(2, 2); OSA_PASS_EXT_CASE(3, 2); OSA_PASS_EXT_CASE(4, 2);
-      OSA_PASS_EXT_CASE(5, 2); OSA_PASS_EXT_CASE(6, 2);
-#undef OSA_PASS_EXT_CASE
-      return OSA_EUNSUPPORTED;
+      return osa_pass_shapes(KB, OT, [&](auto K, auto O) { return osa_launch_pass_so<K, O, false, false, true>(a, st); });
     }
   }
-#define OSA_PASS_CASE(K, O) \
-  if (KB == K && OT == O) return (B > 64) ? osa_launch_pass_so<K, O, true>(a, st) : osa_launch_pass_so<K, O, false>(a, st)
-  OSA_PASS_CASE(1, 1); OSA_PASS_CASE(2, 1); OSA_PASS_CASE(3, 1); OSA_PASS_CASE(4, 1);
-  OSA_PASS_CASE(5, 1); OSA_PASS_CASE(6, 1);
-  OSA_PASS_CASE(1, 2); OSA_PASS_CASE(2, 2); OSA_PASS_CASE(3, 2); OSA_PASS_CASE(4, 2);
-  OSA_PASS_CASE(5, 2); OSA_PASS_CASE(6, 2);
-#undef OSA_PASS_CASE
-  return OSA_EUNSUPPORTED;
+  return osa_pass_shapes(KB, OT, [&](auto K, auto O) {
+    return (B > 64) ? osa_launch_pass_so<K, O, true>(a, st) : osa_launch_pass_so<K, O, false>(a, st);
+  });
 }
 
 }  // extern "C"
@@ -273,8 +211,7 @@ int osa_ppo_dp_step_phase(int obs_dim, int act_dim, int hidden, float* params, f
     OSA_REQUIRE(params && adam_m && adam_v && adam_step && hp && step_stats && slabs && world >= 1 && step_index >= 0);
     const OsaNet nd = osa_make_net(obs_dim, act_dim, hidden);
     OsaPassHp h = {};
-    h.lr_actor = hp->lr_actor; h.lr_critic = hp->lr_critic; h.beta1 = hp->beta1; h.beta2 = hp->beta2;
-    h.adam_eps = hp->adam_eps;
+    osa_copy_hparams(h, hp);
     hipLaunchKernelGGL(osa_dp_apply_kernel, dim3((nd.P + 255) / 256, 3), dim3(256), 0, osa_stream(stream), nd, params,
                        adam_m, adam_v, adam_step, slabs, world, h, lr_dev, nets_mask & (hp->use_cost ? 7 : 3), step_stats,
                        step_index);
@@ -283,33 +220,19 @@ int osa_ppo_dp_step_phase(int obs_dim, int act_dim, int hidden, float* params, f
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats && slabs);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && world >= 1);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim && step_index >= 0 && (long)step_index * B < M);
-  if ((double)M * world * ld_obs >= 2147483647.0) return OSA_EUNSUPPORTED;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad rows
+  if (!osa_rows_ok(obs, ld_obs, (double)M * world)) return OSA_EUNSUPPORTED;
   OsaPassArgs a = {};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = 1; a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
-  a.dbg = nullptr; a.dp_slabs = slabs; a.dp_world = world; a.mb0 = step_index; a.dp_sync = nullptr; a.part_stride = 0; a.dp_uncached = 0;
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = 1;
+  a.dp_slabs = slabs; a.dp_world = world; a.mb0 = step_index;
   const int KB = a.nd.KB, OT = a.nd.OUTP / 16;
   hipStream_t st = osa_stream(stream);
-  int rc = OSA_EUNSUPPORTED;
-#define OSA_DP_CASE(K, O)                                                                        \
-  if (KB == K && OT == O)                                                                        \
-    rc = (B > 64) ? osa_launch_pass<K, O, true, false, false, false, true>(a, st, world)  \
-                  : osa_launch_pass<K, O, false, false, false, false, true>(a, st, world)
-  OSA_DP_CASE(1, 1); OSA_DP_CASE(2, 1); OSA_DP_CASE(3, 1); OSA_DP_CASE(4, 1); OSA_DP_CASE(5, 1);
-  OSA_DP_CASE(6, 1); OSA_DP_CASE(1, 2); OSA_DP_CASE(2, 2); OSA_DP_CASE(3, 2); OSA_DP_CASE(4, 2);
-  OSA_DP_CASE(5, 2); OSA_DP_CASE(6, 2);
-#undef OSA_DP_CASE
+  const int rc = osa_pass_shapes(KB, OT, [&](auto K, auto O) {
+    return (B > 64) ? osa_launch_pass<K, O, true, false, false, false, true>(a, st, world)
+                    : osa_launch_pass<K, O, false, false, false, false, true>(a, st, world);
+  });
   if (rc != OSA_OK || phase == 1) return rc;  // (phase 1: the gradients only -- the caller's all-reduce comes next)
   hipLaunchKernelGGL(osa_dp_apply_kernel, dim3((a.nd.P + 255) / 256, 3), dim3(256), 0, st, a.nd, params,
                      adam_m, adam_v, adam_step, slabs, world, a.hp, lr_dev, a.nets_mask, step_stats,
@@ -440,8 +363,7 @@ static int osa_coop_pass(int obs_dim, int act_dim, int hidden, float* params, fl
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && world >= 1);
   OSA_REQUIRE(exchange && sync && ld_obs >= obs_dim && ld_act >= act_dim);
-  if ((double)M * (chunk ? ranks : world) * ld_obs >= 2147483647.0) return OSA_EUNSUPPORTED;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad rows
+  if (!osa_rows_ok(obs, ld_obs, (double)M * (chunk ? ranks : world))) return OSA_EUNSUPPORTED;
   // all 3 * world workgroups must be co-resident (one per compute unit: ~150 KB of LDS each)
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -453,18 +375,11 @@ static int osa_coop_pass(int obs_dim, int act_dim, int hidden, float* params, fl
   a.dp_chunk = chunk ? 1 : 0;
   a.dp_ranks = chunk ? ranks : 1;
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B); a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
-  a.dbg = g_osa_pass_dbg; a.dp_slabs = exchange; a.dp_world = world; a.mb0 = 0; a.dp_sync = sync; a.part_stride = 0; a.dp_uncached = osa_is_exchange_ptr(exchange) ? 1 : 0;
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
+  a.dbg = g_osa_pass_dbg; a.dp_slabs = exchange; a.dp_world = world; a.dp_sync = sync;
+  a.dp_uncached = osa_is_exchange_ptr(exchange) ? 1 : 0;
   hipStream_t st = osa_stream(stream);
   // sync[0..2]: per-network arrival counters of this pass; sync[3]: STICKY "a peer never arrived" flag --
   // it survives the per-pass reset so that a timeout in any pass of an update is still visible when the
@@ -474,16 +389,11 @@ static int osa_coop_pass(int obs_dim, int act_dim, int hidden, float* params, fl
   // (chunk mode under data parallelism: the per-rank arrival counters of the first hand-off; sync is int[64] there)
   if ((chunk && ranks > 1) && hipMemsetAsync(sync + 8, 0, 48 * sizeof(int), st) != hipSuccess) return OSA_EHIP;
   const int KB = a.nd.KB, OT = a.nd.OUTP / 16;
-#define OSA_DPP_CASE(K, O)                                                                       \
-  if (KB == K && OT == O)                                                                        \
-    return (chunk && ranks > 1) ? osa_launch_pass_so<K, O, false, true, false, true>(a, st, world) \
-           : (B > 64 && !chunk) ? osa_launch_pass<K, O, true, true>(a, st, world)                \
-                                : osa_launch_pass_so<K, O, false, true>(a, st, world)
-  OSA_DPP_CASE(1, 1); OSA_DPP_CASE(2, 1); OSA_DPP_CASE(3, 1); OSA_DPP_CASE(4, 1); OSA_DPP_CASE(5, 1);
-  OSA_DPP_CASE(6, 1); OSA_DPP_CASE(1, 2); OSA_DPP_CASE(2, 2); OSA_DPP_CASE(3, 2); OSA_DPP_CASE(4, 2);
-  OSA_DPP_CASE(5, 2); OSA_DPP_CASE(6, 2);
-#undef OSA_DPP_CASE
-  return OSA_EUNSUPPORTED;
+  return osa_pass_shapes(KB, OT, [&](auto K, auto O) {
+    return (chunk && ranks > 1) ? osa_launch_pass_so<K, O, false, true, false, true>(a, st, world)
+           : (B > 64 && !chunk) ? osa_launch_pass<K, O, true, true>(a, st, world)
+                                : osa_launch_pass_so<K, O, false, true>(a, st, world);
+  });
 }
 
 }  // extern "C"
@@ -496,31 +406,20 @@ int osa_pass_partial_grad(int obs_dim, int act_dim, int hidden, float* params, c
                           const long* idx, int B, const float* lagrange, const osa_ppo_hparams* hp,
                           int loss_kind, int nets_mask, int nblk, float* slabs, void* stream) {
   if (!osa_ppo_pass_supported(obs_dim, act_dim, hidden) || B <= 64) return OSA_EUNSUPPORTED;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, 0.0)) return OSA_EUNSUPPORTED;  // (alignment only: one minibatch of B rows)
   OsaPassArgs a = {};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = params; a.adam_v = params; a.adam_step = nullptr;  // untouched in this mode
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = idx; a.M = B; a.B = B; a.nmb = 1; a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask; a.stats = nullptr;
-  a.dbg = nullptr; a.dp_slabs = slabs; a.dp_world = nblk; a.mb0 = 0; a.dp_sync = nullptr;
-  a.part_stride = nblk; a.dp_uncached = 0;
+  // Adam state untouched in this mode
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, params, params, nullptr, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, nullptr);
+  a.nets_mask = nets_mask;  // as given: the caller (osa_ppo_minibatch_ext) has applied use_cost already
+  a.perm = idx; a.M = B; a.B = B; a.nmb = 1;
+  a.dp_slabs = slabs; a.dp_world = nblk; a.part_stride = nblk;
   const int KB = a.nd.KB, OT = a.nd.OUTP / 16;
   hipStream_t st = osa_stream(stream);
-#define OSA_PG_CASE(K, O) \
-  if (KB == K && OT == O) return osa_launch_pass<K, O, true, false, false, false, true>(a, st, nblk)
-  OSA_PG_CASE(1, 1); OSA_PG_CASE(2, 1); OSA_PG_CASE(3, 1); OSA_PG_CASE(4, 1); OSA_PG_CASE(5, 1);
-  OSA_PG_CASE(6, 1); OSA_PG_CASE(1, 2); OSA_PG_CASE(2, 2); OSA_PG_CASE(3, 2); OSA_PG_CASE(4, 2);
-  OSA_PG_CASE(5, 2); OSA_PG_CASE(6, 2);
-#undef OSA_PG_CASE
-  return OSA_EUNSUPPORTED;
+  return osa_pass_shapes(KB, OT, [&](auto K, auto O) {
+    return osa_launch_pass<K, O, true, false, false, false, true>(a, st, nblk);
+  });
 }
 
 extern "C" {

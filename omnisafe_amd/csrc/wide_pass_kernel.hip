@@ -29,12 +29,6 @@
 #define WSLD 68  // leading dimension (floats) of every [row][64 + pad] LDS tile
 #define WNSTAT 16
 
-struct OsaWideHp {
-  float clip, entropy_coef, critic_norm_coef, max_grad_norm;
-  float lr_actor, lr_critic, beta1, beta2, adam_eps;
-  int use_critic_norm, use_max_grad_norm, use_cost;
-};
-
 struct OsaWideArgs {
   OsaNet nd;
   float* params;   // [3][P] padded global layout
@@ -55,7 +49,7 @@ struct OsaWideArgs {
   int B;    // minibatch size (<= 64); the last minibatch may be smaller
   int nmb;  // minibatches in this launch
   const float* lagrange;
-  OsaWideHp hp;
+  OsaPassHp hp;
   int loss_kind;
   int nets_mask;
   float* stats;  // [nmb][WNSTAT]
@@ -856,21 +850,12 @@ int osa_ppo_wide_pass(int obs_dim, int act_dim, int hidden, float* params, float
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats && ws);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad the rows
-  if ((double)M * ld_obs >= 2147483647.0 * 4) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M, 0, 2147483647.0 * 4)) return OSA_EUNSUPPORTED;
   OsaWideArgs a = {};
   a.ws = ws;
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B); a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
   hipStream_t st = osa_stream(stream);
   const int OT = a.nd.OUTP / 16;
   if (OT == 1) return osa_launch_wide<1>(a, st);

@@ -55,12 +55,6 @@
 #define SF_ERR 96                          // sticky: a peer never arrived (1) / a network on two XCCs (2)
 #define SF_ARRIVE 97                       // arrivals of the placement check (zeroed per launch)
 
-struct OsaSplitHp {
-  float clip, entropy_coef, critic_norm_coef, max_grad_norm;
-  float lr_actor, lr_critic, beta1, beta2, adam_eps;
-  int use_critic_norm, use_max_grad_norm, use_cost;
-};
-
 struct OsaSplitArgs {
   OsaNet nd;
   float* params;   // [3][P] padded global layout
@@ -81,7 +75,7 @@ struct OsaSplitArgs {
   int B;    // minibatch size (<= 64); the last minibatch may be smaller
   int nmb;  // minibatches in this launch
   const float* lagrange;
-  OsaSplitHp hp;
+  OsaPassHp hp;
   int loss_kind;
   int nets_mask;
   float* stats;  // [nmb][SNSTAT]
@@ -1322,23 +1316,14 @@ int osa_ppo_split_pass(int obs_dim, int act_dim, int hidden, float* params, floa
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
   if (!local && !osa_is_exchange_ptr(xch)) return OSA_EINVAL;  // hand-offs across XCCs rely on uncached memory
   if (local && osa_is_exchange_ptr(xch)) return OSA_EINVAL;
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad the rows
-  if ((double)M * ld_obs >= 2147483647.0 * 4) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M, 0, 2147483647.0 * 4)) return OSA_EUNSUPPORTED;
   OsaSplitArgs a = {};
   a.xch = xch;
   a.local = local;  // 0, 1, or 3 (see the kernel)
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
   a.C = (a.nd.KB + SKQ - 1) / SKQ;
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B); a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
   hipStream_t st = osa_stream(stream);
   // flag words are step counters of THIS launch (the sticky error word, SF_ERR, survives)
   if (hipMemsetAsync(xch, 0, SF_ERR * sizeof(int), st) != hipSuccess) return OSA_EHIP;
@@ -1378,10 +1363,11 @@ int osa_ppo_split_dp_pass(int obs_dim, int act_dim, int hidden, float* params, f
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && world >= 1);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
   if (!osa_is_exchange_ptr(xch)) return OSA_EINVAL;  // hand-offs across XCCs rely on uncached memory
-  if (ld_obs % 4 != 0 || (reinterpret_cast<uintptr_t>(obs) & 15) != 0) return OSA_EUNSUPPORTED;  // pad the rows
-  if ((double)M * world * ld_obs >= 2147483647.0 * 4) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M * world, 0, 2147483647.0 * 4)) return OSA_EUNSUPPORTED;
   OsaSplitArgs a = {};
-  a.nd = osa_make_net(obs_dim, act_dim, hidden);
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
   a.C = (a.nd.KB + SKQ - 1) / SKQ;
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -1398,16 +1384,6 @@ int osa_ppo_split_dp_pass(int obs_dim, int act_dim, int hidden, float* params, f
   a.dpx = dpx ? dpx : xch + (size_t)world * per_rank;
   a.dp_hdr = reinterpret_cast<int*>(xch + (size_t)world * per_rank);
   a.dp_place = place;
-  a.params = params; a.adam_m = adam_m; a.adam_v = adam_v; a.adam_step = adam_step;
-  a.obs = obs; a.ld_obs = ld_obs; a.act = act; a.ld_act = ld_act; a.logp = logp;
-  a.tgt_r = target_value_r; a.tgt_c = target_value_c; a.adv_r = adv_r; a.adv_c = adv_c;
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B); a.lagrange = lagrange;
-  a.hp.clip = hp->clip; a.hp.entropy_coef = hp->entropy_coef;
-  a.hp.critic_norm_coef = hp->critic_norm_coef; a.hp.max_grad_norm = hp->max_grad_norm;
-  a.hp.lr_actor = hp->lr_actor; a.hp.lr_critic = hp->lr_critic; a.hp.beta1 = hp->beta1;
-  a.hp.beta2 = hp->beta2; a.hp.adam_eps = hp->adam_eps; a.hp.use_critic_norm = hp->use_critic_norm;
-  a.hp.use_max_grad_norm = hp->use_max_grad_norm; a.hp.use_cost = hp->use_cost;
-  a.loss_kind = loss_kind; a.nets_mask = nets_mask & (hp->use_cost ? 7 : 3); a.stats = step_stats;
   hipStream_t st = osa_stream(stream);
   // flag words and arrival counters are step counters of THIS launch (rank 0's sticky error word survives)
   for (int r = 0; r < world; ++r) {

@@ -180,6 +180,49 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         m = (0b110 if self.hp.use_cost else 0b010) if self.update_critics else 0
         return m | (1 if self.update_actor else 0)
 
+    def _operands(self, data: dict, perm: torch.Tensor | None, M: int | None, B: int) -> tuple:
+        """Leading arguments of the fused-family entry points: dims, parameters, Adam moments and step, the seven data
+        arrays with their leading dimensions, perm, M, B.  M None: osa_ppo_minibatch(_ext)'s form -- the gradient
+        buffer after the Adam step, `perm` the rows of one minibatch of B."""
+        ac = self.ac
+        head = (ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m), _lib.ptr(ac.adam_v),
+                _lib.ptr(ac.adam_step))
+        rows = (_lib.ptr(data['obs']), data['obs'].stride(0), _lib.ptr(data['act']), data['act'].stride(0),
+                _lib.ptr(data['logp']), _lib.ptr(data['target_value_r']), _lib.ptr(data['target_value_c']),
+                _lib.ptr(data['adv_r']), _lib.ptr(data['adv_c']), _lib.ptr(perm))
+        if M is None:
+            return head + (_lib.ptr(ac.grads),) + rows + (B,)
+        return head + rows + (M, B)
+
+    def _profile_begin(self) -> tuple | None:
+        """Start of a profiled launch: an event pair with the start recorded, or None when not profiling."""
+        if self.profile_events is None:
+            return None
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        return ev
+
+    def _profile_end(self, ev: tuple | None, name: str, rows: int) -> None:
+        """End of a profiled launch: records (name, rows, events) -- bench.py's roofline reads the names."""
+        if ev is not None:
+            ev[1].record()
+            self.profile_events.append((name, rows, ev))
+
+    @staticmethod
+    def _placement_verified(read_flag, timeout_msg: str) -> bool:
+        """First pass of a one-XCC variant: the kernel checks its placement before it modifies anything and returns
+        untouched when it does not hold.  Waits for the pass and reads its flag word: 0 -> True; 1 (a workgroup never
+        arrived: not a placement question, the parameters may be modified) -> raises; else -> False, recorded for the
+        process, and the caller repeats the pass spread over the XCCs."""
+        torch.cuda.synchronize()
+        flag = read_flag()
+        if flag == 1:
+            raise _lib.OsaError(timeout_msg)
+        if flag != 0:
+            _PLACEMENT['local_ok'] = False
+            return False
+        return True
+
     def shuffles(self, rows: int, M: int, out: torch.Tensor | None = None,
                  generator: torch.Generator | None = None) -> torch.Tensor:
         """`rows` random permutations of 0 .. M-1 (one per pass: the reference's DataLoader(shuffle=True),
@@ -281,11 +324,8 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
                 self._ar_end_pass()
 
         hp.lr_device = st['lr'].data_ptr()
+        ev = self._profile_begin()
         pe, self.profile_events = self.profile_events, None  # (one event pair around the pass, none inside a capture)
-        ev = None
-        if pe is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
         try:
             if st['graph'] is not None:
                 st['graph'].replay()
@@ -309,9 +349,7 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         finally:
             hp.lr_device = None
             self.profile_events = pe
-        if ev is not None:
-            ev[1].record()
-            pe.append(('gm_gemm_kernel' if self.general else 'osa_mb_grad_kernel', passes * M, ev))  # rows of the launch
+        self._profile_end(ev, 'gm_gemm_kernel' if self.general else 'osa_mb_grad_kernel', passes * M)  # rows of the launch
         stats_rows.copy_(st['stats'])
         self._graphed_pass = st['graph'] is not None
 
@@ -344,10 +382,7 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         ac, lib, st = self.ac, self.lib, _lib.stream_ptr()
         dp = dist.collectives_active()
         mode = 1 if dp else 0  # 1: gradients only (clipped locally); all-reduce + Adam follow below
-        ev = None
-        if self.profile_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
+        ev = self._profile_begin()
         if self.general:
             ws, nws = ac.gmlp_ws(B)
             gext = None
@@ -364,9 +399,7 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
                 _lib.ptr(data['adv_c']), _lib.ptr(idx), B, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind,
                 mode, self._nets_mask(), None, 0.0, _lib.ptr(ws), nws, _lib.ptr(stats_row), gext, st),
                 'osa_gmlp_minibatch_ext')
-            if ev is not None:
-                ev[1].record()
-                self.profile_events.append(('gm_gemm_kernel', B, ev))
+            self._profile_end(ev, 'gm_gemm_kernel', B)
             if dp:
                 dist.all_reduce_avg_(ac.grads)
                 _lib.check(lib.osa_gmlp_adam_apply(C.byref(ac.desc), _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
@@ -378,17 +411,11 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             # per-step all-reduce mode on the pass kernel's gradient-only form (round 5): clipped gradients of THIS rank's
             # minibatch -> ONE flat all-reduce (average) of the slab -> Adam (policy_gradient.py:437-443 order)
             slab = self._ar_slab()
-            args = (ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m), _lib.ptr(ac.adam_v),
-                    _lib.ptr(ac.adam_step), _lib.ptr(data['obs']), data['obs'].stride(0), _lib.ptr(data['act']),
-                    data['act'].stride(0), _lib.ptr(data['logp']), _lib.ptr(data['target_value_r']),
-                    _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']), _lib.ptr(data['adv_c']), _lib.ptr(idx),
-                    B, self.batch_size, 1)
+            args = self._operands(data, idx, B, self.batch_size) + (1,)
             tail = (_lib.ptr(lagrange), C.byref(self.hp), self.hp.lr_device, self.loss_kind, self._nets_mask(),
                     _lib.ptr(slab), _lib.ptr(stats_row))
             _lib.check(lib.osa_ppo_dp_step_phase(*args, 0, *tail, 1, st), 'osa_ppo_dp_step_phase(grad)')
-            if ev is not None:
-                ev[1].record()
-                self.profile_events.append(('osa_ppo_pass_kernel', B, ev))
+            self._profile_end(ev, 'osa_ppo_pass_kernel', B)
             dist.all_reduce_avg_(slab)
             _lib.check(lib.osa_ppo_dp_step_phase(*args, self._ar_k, *tail, 2, st), 'osa_ppo_dp_step_phase(apply)')
             self._ar_k += 1
@@ -400,16 +427,10 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             self.ext.old_log_std = self._old_log_std.data_ptr()
             ext = C.byref(self.ext)
         _lib.check(lib.osa_ppo_minibatch_ext(
-            ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-            _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(ac.grads), _lib.ptr(data['obs']),
-            data['obs'].stride(0), _lib.ptr(data['act']), data['act'].stride(0), _lib.ptr(data['logp']),
-            _lib.ptr(data['target_value_r']), _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']),
-            _lib.ptr(data['adv_c']), _lib.ptr(idx), B, _lib.ptr(lagrange), C.byref(self.hp),
-            self.loss_kind, mode, self._nets_mask(), self.max_blocks, _lib.ptr(self._ws),
-            _lib.ptr(stats_row), ext, st), 'osa_ppo_minibatch_ext')
-        if ev is not None:
-            ev[1].record()
-            self.profile_events.append(('osa_mb_grad_kernel', B, ev))
+            *self._operands(data, idx, None, B), _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, mode,
+            self._nets_mask(), self.max_blocks, _lib.ptr(self._ws), _lib.ptr(stats_row), ext, st),
+            'osa_ppo_minibatch_ext')
+        self._profile_end(ev, 'osa_mb_grad_kernel', B)
         if dp:
             dist.all_reduce_avg_(ac.grads)  # C1: one flat message for pi, V_r, V_c
             _lib.check(lib.osa_adam_apply(ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params),
@@ -420,21 +441,14 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
     def run_pass(self, data: dict, perm: torch.Tensor, lagrange: torch.Tensor,
                  stats_rows: torch.Tensor) -> None:
         """osa_ppo_pass: all ceil(M/B) minibatch steps of one pass in a single persistent launch."""
-        ac = self.ac
         M = data['obs'].shape[0]
-        ev = None
-        if self.profile_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        name = 'osa_ppo_pass_kernel'
+        ops = self._operands(data, perm, M, self.batch_size)
+        # (one event pair: a form that refuses its launch falls through to the next, and only the one that ran is
+        # recorded)
+        ev = self._profile_begin()
         if self._use_wide and self._split_xch:  # wide observations, first layer split over CUs (wide_split_kernel.hip)
             rc = self.lib.osa_ppo_split_pass(
-                ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-                _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(data['obs']), data['obs'].stride(0),
-                _lib.ptr(data['act']), data['act'].stride(0), _lib.ptr(data['logp']),
-                _lib.ptr(data['target_value_r']), _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']),
-                _lib.ptr(data['adv_c']), _lib.ptr(perm), M, self.batch_size, _lib.ptr(lagrange),
-                C.byref(self.hp), self.loss_kind, self._nets_mask(), C.c_void_p(self._split_xch),
+                *ops, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), C.c_void_p(self._split_xch),
                 (1 if self._split_verified else _local_arg()) if self._split_local else 0, _lib.ptr(stats_rows),
                 _lib.stream_ptr())
             if rc == _lib.OSA_EUNSUPPORTED:  # the device cannot hold the workgroups together: one CU per network
@@ -442,47 +456,30 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             else:
                 _lib.check(rc, 'osa_ppo_split_pass')
                 if self._split_local and not self._split_verified:
-                    # first pass with one XCC per network: the kernel checks its placement before it modifies
-                    # anything and returns untouched if it does not hold -> repeat spread over the XCCs
-                    torch.cuda.synchronize()
-                    flag = int(self._split_buf.view(torch.int32)[96])
-                    if flag == 1:  # a workgroup never arrived at the placement check: not a placement question
-                        raise _lib.OsaError('osa_ppo_split_pass: a cooperating workgroup never arrived at the '
-                                            'placement check (device shared with another long-running kernel?)')
-                    if flag != 0:
-                        _PLACEMENT['local_ok'] = False
+                    # first pass with one XCC per network -> repeat spread over the XCCs if the placement did not hold
+                    if not self._placement_verified(
+                            lambda: int(self._split_buf.view(torch.int32)[96]),
+                            'osa_ppo_split_pass: a cooperating workgroup never arrived at the placement check '
+                            '(device shared with another long-running kernel?)'):
                         self._split_free()
                         self._split_tried = False
                         self._split_alloc()
                         return self.run_pass(data, perm, lagrange, stats_rows)
                     self._split_verified = _PLACEMENT['local_ok'] = True
                 self.last_path = 'persistent-wide-split'
-                if ev is not None:
-                    ev[1].record()
-                    self.profile_events.append(('osa_wide_split_kernel', M, ev))
+                self._profile_end(ev, 'osa_wide_split_kernel', M)
                 return
         if self._use_wide:  # wide observations: W1 and its Adam moments streamed from L2 (wide_pass_kernel.hip)
             _lib.check(self.lib.osa_ppo_wide_pass(
-                ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-                _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(data['obs']), data['obs'].stride(0),
-                _lib.ptr(data['act']), data['act'].stride(0), _lib.ptr(data['logp']),
-                _lib.ptr(data['target_value_r']), _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']),
-                _lib.ptr(data['adv_c']), _lib.ptr(perm), M, self.batch_size, _lib.ptr(lagrange),
-                C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(self._wide_ws), _lib.ptr(stats_rows),
-                _lib.stream_ptr()), 'osa_ppo_wide_pass')
-            if ev is not None:
-                ev[1].record()
-                self.profile_events.append(('osa_wide_pass_kernel', M, ev))
+                *ops, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(self._wide_ws),
+                _lib.ptr(stats_rows), _lib.stream_ptr()), 'osa_ppo_wide_pass')
+            self._profile_end(ev, 'osa_wide_pass_kernel', M)
             return
         if self._chunk_ok(data):  # 64 < B: the minibatch's 64-row chunks on cooperating workgroups (one XCC per network)
             ck = self._chunk
             rc = self.lib.osa_ppo_chunked_pass(
-                ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-                _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(data['obs']), data['obs'].stride(0),
-                _lib.ptr(data['act']), data['act'].stride(0), _lib.ptr(data['logp']),
-                _lib.ptr(data['target_value_r']), _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']),
-                _lib.ptr(data['adv_c']), _lib.ptr(perm), M, self.batch_size, _lib.ptr(lagrange),
-                C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(ck['xch']), _lib.ptr(ck['sync']),
+                *ops, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(ck['xch']),
+                _lib.ptr(ck['sync']),
                 (1 if ck.get('verified') else _local_arg()) if ck.get('local', 1) else 0, _lib.ptr(stats_rows),
                 _lib.stream_ptr())
             if rc == _lib.OSA_EUNSUPPORTED:  # not co-resident: one workgroup walks through the chunks
@@ -490,23 +487,18 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             else:
                 _lib.check(rc, 'osa_ppo_chunked_pass')
                 if ck.get('local', 1) and not ck.get('verified'):
-                    # (as above: an unverified placement leaves everything untouched; repeat with the workgroups
-                    # spread over the XCCs and agent-scope release / acquire fences around the hand-offs)
-                    torch.cuda.synchronize()
-                    flag = int(ck['sync'][3])
-                    if flag == 1:  # time-out, not placement: never re-run on possibly modified parameters
-                        raise _lib.OsaError('osa_ppo_chunked_pass: a cooperating workgroup never arrived at the '
-                                            'placement check (device shared with another long-running kernel?)')
-                    if flag != 0:
-                        _PLACEMENT['local_ok'] = False
+                    # (as above; the repeat spreads the workgroups over the XCCs with agent-scope release / acquire
+                    # fences around the hand-offs)
+                    if not self._placement_verified(
+                            lambda: int(ck['sync'][3]),
+                            'osa_ppo_chunked_pass: a cooperating workgroup never arrived at the placement check '
+                            '(device shared with another long-running kernel?)'):
                         ck['sync'].zero_()
                         ck['local'] = 0
                         return self.run_pass(data, perm, lagrange, stats_rows)
                     ck['verified'] = _PLACEMENT['local_ok'] = True
                 self.last_path = 'persistent-chunked'
-                if ev is not None:
-                    ev[1].record()
-                    self.profile_events.append(('osa_ppo_pass_kernel', M, ev))
+                self._profile_end(ev, 'osa_ppo_pass_kernel', M)
                 return
         ext = None
         if self.ext is not None:  # extended actor surrogate (FOCOPS / CUP / P3O) inside the persistent pass
@@ -515,16 +507,9 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             self.ext.old_log_std = self._old_log_std.data_ptr()
             ext = C.byref(self.ext)
         _lib.check(self.lib.osa_ppo_pass_ext(
-            ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-            _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(data['obs']), data['obs'].stride(0),
-            _lib.ptr(data['act']), data['act'].stride(0), _lib.ptr(data['logp']),
-            _lib.ptr(data['target_value_r']), _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']),
-            _lib.ptr(data['adv_c']), _lib.ptr(perm), M, self.batch_size, _lib.ptr(lagrange),
-            C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(stats_rows), ext,
+            *ops, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(stats_rows), ext,
             _lib.stream_ptr()), 'osa_ppo_pass_ext')
-        if ev is not None:
-            ev[1].record()
-            self.profile_events.append((name, M, ev))
+        self._profile_end(ev, 'osa_ppo_pass_kernel', M)
 
     # ------------------------------------------------------------------ one-shot peer exchange (dp_mode 'p2p')
     def _p2p_ok(self, data: dict) -> bool:
@@ -613,25 +598,16 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
     def run_pass_p2p(self, data: dict, perm: torch.Tensor, lagrange: torch.Tensor, stats_rows: torch.Tensor) -> None:
         """osa_ppo_p2p_pass: one pass of THIS rank's minibatches in one persistent launch, gradients exchanged by peer
         writes (policy_gradient.py:366-382 + 437-443 under torch.distributed)."""
-        ac, st = self.ac, self._p2p
+        st = self._p2p
         M = data['obs'].shape[0]
         nmb = (M + self.batch_size - 1) // self.batch_size
-        ev = None
-        if self.profile_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
+        ev = self._profile_begin()
         _lib.check(self.lib.osa_ppo_p2p_pass(
-            ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m), _lib.ptr(ac.adam_v),
-            _lib.ptr(ac.adam_step), _lib.ptr(data['obs']), data['obs'].stride(0), _lib.ptr(data['act']),
-            data['act'].stride(0), _lib.ptr(data['logp']), _lib.ptr(data['target_value_r']),
-            _lib.ptr(data['target_value_c']), _lib.ptr(data['adv_r']), _lib.ptr(data['adv_c']), _lib.ptr(perm), M,
-            self.batch_size, st['W'], dist.rank(), st['peers'], st['seq'] & 0xFFFFFFFF, st['timeout'],
-            _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(stats_rows),
-            _lib.stream_ptr()), 'osa_ppo_p2p_pass')
+            *self._operands(data, perm, M, self.batch_size), st['W'], dist.rank(), st['peers'],
+            st['seq'] & 0xFFFFFFFF, st['timeout'], _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind,
+            self._nets_mask(), _lib.ptr(stats_rows), _lib.stream_ptr()), 'osa_ppo_p2p_pass')
         st['seq'] += nmb
-        if ev is not None:
-            ev[1].record()
-            self.profile_events.append(('osa_ppo_p2p_pass_kernel', M, ev))
+        self._profile_end(ev, 'osa_ppo_p2p_pass_kernel', M)
 
     # ------------------------------------------------------------------ replicated-data DP path
     _DP_KEYS = ('obs', 'act', 'logp', 'target_value_r', 'target_value_c', 'adv_r', 'adv_c')
@@ -673,16 +649,12 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
 
     def _dp_enqueue_pass(self, data_all: dict, M: int, W: int, lagrange: torch.Tensor, st: dict, nmb: int) -> None:
         ac, lib = self.ac, self.lib
+        ops = self._operands(data_all, st['perm'], M, self.batch_size)
         for k in range(nmb):
             _lib.check(lib.osa_ppo_dp_step(
-                ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-                _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(data_all['obs']),
-                data_all['obs'].stride(0), _lib.ptr(data_all['act']), data_all['act'].stride(0),
-                _lib.ptr(data_all['logp']), _lib.ptr(data_all['target_value_r']),
-                _lib.ptr(data_all['target_value_c']), _lib.ptr(data_all['adv_r']), _lib.ptr(data_all['adv_c']),
-                _lib.ptr(st['perm']), M, self.batch_size, W, k, _lib.ptr(lagrange), C.byref(self.hp),
-                _lib.ptr(st['lr']), self.loss_kind, self._nets_mask(), _lib.ptr(st['slabs']),
-                _lib.ptr(st['pass_stats'][k]), _lib.stream_ptr()), 'osa_ppo_dp_step')
+                *ops, W, k, _lib.ptr(lagrange), C.byref(self.hp), _lib.ptr(st['lr']), self.loss_kind,
+                self._nets_mask(), _lib.ptr(st['slabs']), _lib.ptr(st['pass_stats'][k]), _lib.stream_ptr()),
+                'osa_ppo_dp_step')
         _lib.check(lib.osa_ppo_dp_end_pass(_lib.ptr(ac.adam_step), self._nets_mask() & (7 if self.hp.use_cost else 3),
                                            nmb, _lib.stream_ptr()), 'osa_ppo_dp_end_pass')
 
@@ -730,26 +702,22 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
                                              dtype=torch.float32, device=ac.device)
         place = st['wide_place']
         _lib.check(lib.osa_ppo_split_dp_pass(
-            ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m), _lib.ptr(ac.adam_v),
-            _lib.ptr(ac.adam_step), _lib.ptr(data_all['obs']), data_all['obs'].stride(0), _lib.ptr(data_all['act']),
-            data_all['act'].stride(0), _lib.ptr(data_all['logp']), _lib.ptr(data_all['target_value_r']),
-            _lib.ptr(data_all['target_value_c']), _lib.ptr(data_all['adv_r']), _lib.ptr(data_all['adv_c']),
-            _lib.ptr(st['perm']), M, self.batch_size, W, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind,
-            self._nets_mask(), C.c_void_p(st['wide_xch']), _lib.ptr(st['wide_dpx']) if place else None,
+            *self._operands(data_all, st['perm'], M, self.batch_size), W, _lib.ptr(lagrange), C.byref(self.hp),
+            self.loss_kind, self._nets_mask(), C.c_void_p(st['wide_xch']), _lib.ptr(st['wide_dpx']) if place else None,
             ((1 if st['wide_verified'] else _local_arg()) if place else 0), _lib.ptr(st['pass_stats']),
             _lib.stream_ptr()), 'osa_ppo_split_dp_pass')
         if place and not st['wide_verified']:
-            # first pass with the owner groups on one XCC each: an unverified placement returns with everything
-            # untouched -> repeat rank-major with the uncached exchange
-            torch.cuda.synchronize()
-            flag = C.c_int(0)
-            _lib.check(lib.osa_ppo_split_pass_timed_out(C.c_void_p(st['wide_xch']), C.byref(flag)),
-                       'osa_ppo_split_pass_timed_out')
-            if flag.value == 1:
-                raise _lib.OsaError('osa_ppo_split_dp_pass: a cooperating workgroup never arrived at the placement '
-                                    'check (device shared with another long-running kernel?)')
-            if flag.value != 0:
-                _PLACEMENT['local_ok'] = False
+            # first pass with the owner groups on one XCC each -> repeat rank-major with the uncached exchange if the
+            # placement did not hold
+            def read_flag() -> int:
+                flag = C.c_int(0)
+                _lib.check(lib.osa_ppo_split_pass_timed_out(C.c_void_p(st['wide_xch']), C.byref(flag)),
+                           'osa_ppo_split_pass_timed_out')
+                return flag.value
+
+            if not self._placement_verified(
+                    read_flag, 'osa_ppo_split_dp_pass: a cooperating workgroup never arrived at the placement check '
+                    '(device shared with another long-running kernel?)'):
                 st['wide_place'] = False
                 _lib.check(lib.osa_ppo_split_pass_clear_flag(C.c_void_p(st['wide_xch'])),
                            'osa_ppo_split_pass_clear_flag')
@@ -806,12 +774,7 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         st['sliced'] = False
         fn = lib.osa_ppo_dp_chunked_pass if chunked else lib.osa_ppo_dp_pass_placed
         rc = fn(
-            ac.obs_dim, ac.act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(ac.adam_m),
-            _lib.ptr(ac.adam_v), _lib.ptr(ac.adam_step), _lib.ptr(data_all['obs']),
-            data_all['obs'].stride(0), _lib.ptr(data_all['act']), data_all['act'].stride(0),
-            _lib.ptr(data_all['logp']), _lib.ptr(data_all['target_value_r']),
-            _lib.ptr(data_all['target_value_c']), _lib.ptr(data_all['adv_r']), _lib.ptr(data_all['adv_c']),
-            _lib.ptr(st['perm']), M, self.batch_size, W, _lib.ptr(lagrange), C.byref(self.hp),
+            *self._operands(data_all, st['perm'], M, self.batch_size), W, _lib.ptr(lagrange), C.byref(self.hp),
             self.loss_kind, self._nets_mask(), st['xch_ptr'], _lib.ptr(st['sync']),
             (1 if st.get('verified') else _local_arg()) if st['local'] else 0,
             _lib.ptr(st['pass_stats']), _lib.stream_ptr())
@@ -822,15 +785,12 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             return False
         _lib.check(rc, 'osa_ppo_dp_chunked_pass' if chunked else 'osa_ppo_dp_pass_placed')
         if st['local'] and not st.get('verified'):
-            # first pass with one XCC per network: an unverified placement returns with everything untouched
-            # -> repeat spread over the XCCs (same buffer, agent-scope release / acquire fences)
-            torch.cuda.synchronize()
-            flag = int(st['sync'][3])
-            if flag == 1:  # time-out, not placement: never re-run on possibly modified parameters
-                raise _lib.OsaError('osa_ppo_dp_pass_placed: a peer workgroup never arrived at the placement check '
-                                    '(workgroups not co-resident?); set OSA_DP_MODE=replicated-steps')
-            if flag != 0:
-                _PLACEMENT['local_ok'] = False
+            # first pass with one XCC per network -> repeat spread over the XCCs if the placement did not hold (same
+            # buffer, agent-scope release / acquire fences)
+            if not self._placement_verified(
+                    lambda: int(st['sync'][3]),
+                    'osa_ppo_dp_pass_placed: a peer workgroup never arrived at the placement check '
+                    '(workgroups not co-resident?); set OSA_DP_MODE=replicated-steps'):
                 st['sync'].zero_()
                 st['local'] = False
                 return self._dp_coop_pass(data_all, M, W, lagrange, st)
@@ -885,36 +845,23 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         else:  # W shuffles, one launch (every rank draws the same seeds from the generator they all seeded alike)
             self.shuffles(W, M, out=st['perm'], generator=st['gen'])
         if self._repl_wide:  # wide observations: the data-parallel split pass (no stepwise variant)
-            ev = None
-            if self.profile_events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
+            ev = self._profile_begin()
             self._wide_dp_pass(data_all, M, W, lagrange, st)
-            if ev is not None:
-                ev[1].record()
-                self.profile_events.append(('osa_wide_split_kernel', W * M, ev))
+            self._profile_end(ev, 'osa_wide_split_kernel', W * M)
             stats_rows.copy_(st['pass_stats'][:stats_rows.shape[0]])
             return
         if coop is None:
             coop = self.dp_mode != 'replicated-steps'
         if coop:
-            ev = None
-            if self.profile_events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
+            ev = self._profile_begin()
             if self._dp_coop_pass(data_all, M, W, lagrange, st):
-                if ev is not None:
-                    ev[1].record()
-                    self.profile_events.append(('osa_ppo_dp_pass', W * M, ev))
+                self._profile_end(ev, 'osa_ppo_dp_pass', W * M)
                 stats_rows.copy_(st['pass_stats'][:stats_rows.shape[0]])
                 return
         st['lr'][0] = float(self.hp.lr_actor)
         st['lr'][1] = float(self.hp.lr_critic)
         key = (M, W, nmb, self._nets_mask(), int(lagrange.data_ptr()), data_all['obs'].data_ptr())
-        ev = None
-        if self.profile_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
+        ev = self._profile_begin()
         graph_ok = use_graph and not st.get('graph_failed', False) and st.get('warm', False)
         if graph_ok and (st.get('graph') is None or st.get('graph_key') != key):
             try:  # capture records the launches without executing them
@@ -931,9 +878,7 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             # first pass (also sets the kernels' LDS attributes, which must not happen under capture)
             self._dp_enqueue_pass(data_all, M, W, lagrange, st, nmb)
             st['warm'] = True
-        if ev is not None:
-            ev[1].record()
-            self.profile_events.append(('osa_ppo_dp_step', W * M, ev))
+        self._profile_end(ev, 'osa_ppo_dp_step', W * M)
         stats_rows.copy_(st['pass_stats'][:stats_rows.shape[0]])
 
     def _aligned_rows(self, data: dict) -> dict:
