@@ -769,6 +769,35 @@ int osa_actor_eval(int obs_dim, int act_dim, int hidden, const float* actor_para
  * (drawn by the host framework's seeded generator); perm: device int64 [rows][M].  M <= 2^40, rows <= 65535. */
 int osa_shuffle_rows(const long long* row_seeds, int rows, long M, long long* perm, void* stream);
 
+/* Deterministic evaluation of a saved policy (omnisafe/evaluator.py:399-490), K episodes in ONE launch: episode k
+ * plays env index k of a device env from a fresh reset, at Philox stream positions 0 (reset), 1, 2, ... -- the
+ * numbers the per-step env launches of a fresh env seeded `seed` draw for env k.  Every step: the raw observation
+ * normalised with FROZEN statistics (norm_*: as osa_normalizer_apply, no push; all three NULL: no normaliser; the
+ * reference's evaluator keeps pushing, normalizer.py:103), the Saute / Simmer safety column z appended when saute != 0
+ * (evaluator.py:432-433; z = 1 at reset, z <- (z - cost / saute_budget) / saute_gamma in float32 after every step,
+ * :456-458), the actor mean (fused family: hidden as for osa_policy_step, act_dim <= 32, policy input obs_dim + saute
+ * <= 992 columns), ActionScale (old_min / old_max: act_dim floats, as osa_action_scale), the env transition.  In
+ * float64: ep_ret += reward, ep_cost += cost_criteria^len * cost (:460-461), then len += 1; early_terminated != 0
+ * ends the episode once ep_cost >= cost_limit (:462-466); an episode ends at its first terminated / truncated step
+ * (the env's own `horizon`) or after max_steps steps.
+ * env_kind: OSA_EVAL_ENV_SYNTH (osa_synth_env_step; cost_p used) or OSA_EVAL_ENV_REACH (osa_reach_env_step: obs_dim
+ * >= 6, act_dim >= 2); anything else OSA_EUNSUPPORTED.  Outputs: ep_ret, ep_cost double[K], ep_len int32[K].
+ * trace (NULL in production): float[max_steps][K][osa_eval_trace_floats(...)], zero-initialised by the caller; the
+ * record of (step, episode) is written while the episode plays: policy input row, env action, reward, cost, 1.0
+ * (alive), and for SynthReach the 6-float state before the step.  Arguments are checked before any launch. */
+#define OSA_EVAL_ENV_SYNTH 0
+#define OSA_EVAL_ENV_REACH 1
+int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden, const float* params,
+                      const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
+                      const float* old_min, const float* old_max, float min_action, float max_action,
+                      unsigned long long seed, int horizon, float cost_p, int max_steps, int saute,
+                      float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
+                      double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
+                      void* stream);
+
+/* Floats per trace record of osa_eval_episodes (0 for bad dims). */
+int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,3 +67,27 @@ class Agent:  # the reference exposes AlgoWrapper under this name (omnisafe/__in
     def learn(self) -> tuple[float, float, float]:
         """algo_wrapper.py:172-184."""
         return self.agent.learn()
+
+    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0) -> dict:
+        """algo_wrapper.py:215-229: every ``torch_save/*.pt`` of this run, in epoch order, through
+        :class:`omnisafe_amd.evaluator.Evaluator`; ``{model_name: (episode_rewards, episode_costs)}``.  Under a world
+        size > 1 only rank 0 evaluates (no collective is entered); the other ranks return ``{}``."""
+        if dist.world_size() > 1 and dist.rank() != 0:
+            return {}
+        from .evaluator import Evaluator
+
+        log_dir = self.agent.logger.log_dir
+        save = os.path.join(log_dir, 'torch_save')
+        names = [n for n in os.listdir(save) if n.endswith('.pt') and os.path.isfile(os.path.join(save, n))]
+
+        def epoch(name: str) -> tuple[int, str]:
+            stem = name[:-3].rsplit('-', 1)[-1]
+            return (int(stem), name) if stem.isdigit() else (1 << 62, name)
+
+        ev = Evaluator(seed=int(self.cfgs.seed), device=str(self.cfgs.train_cfgs.device),
+                       verbose=bool(getattr(self.cfgs.logger_cfgs, 'verbose', True)))
+        out = {}
+        for name in sorted(names, key=epoch):
+            ev.load_saved(save_dir=log_dir, model_name=name)
+            out[name] = ev.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria)
+        return out

@@ -1,0 +1,212 @@
+// Persistent deterministic evaluation of a saved policy on a device env (omnisafe/evaluator.py:399-490, episodes in
+// parallel lanes): one launch plays K episodes.  Episode k is row j = k & 15 of the wave of workgroup k / 16 (the row
+// mapping of osa_policy_step_kernel: the four lane groups g = lane >> 4 of a row share its MFMA fragments).  Each step
+// of a row: frozen-statistics normalisation of the env observation (osa_normalize_kernel's expression), Saute /
+// Simmer safety column, actor mean (osa_mlp_forward), ActionScale (osa_action_scale1), env transition (env_device.h),
+// float64 episode sums, early termination.  A workgroup ends when its 16 rows are done: no atomics, no spins and no
+// barrier between workgroups.
+//
+// Random numbers: row k replays env index k of the per-step env launches at stream positions 0 (reset), 1, 2, ...
+// so that this kernel and the per-step path (omnisafe_amd/evaluator.py) play the same episodes bit for bit.
+#include "env_device.h"
+
+struct OsaEvalArgs {
+  OsaNet nd;  // actor shape; nd.obs_dim = policy input width = obs_dim + saute
+  const float* params;
+  int K, obs_dim, max_steps, horizon;
+  const float *mean, *std_;
+  const long* count;
+  float clip;
+  const float *old_min, *old_max;
+  float min_a, max_a;
+  unsigned long long seed;
+  float cost_p;
+  int saute;
+  float budget, saute_gamma;
+  int early_terminated;
+  double cost_limit, cost_criteria;
+  double *ep_ret, *ep_cost;
+  int* ep_len;
+  float* trace;
+  int rec;  // floats per trace record
+};
+
+#define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
+
+#pragma clang fp contract(off)
+// normalizer.py:104-107 with frozen statistics (osa_normalize_kernel without the mask)
+__device__ __forceinline__ float osa_eval_norm(const OsaEvalArgs& a, bool on, float v, int col) {
+  if (on) {
+    v = (v - a.mean[col]) / a.std_[col];
+    v = fminf(fmaxf(v, -a.clip), a.clip);
+  }
+  return v;
+}
+
+// The env observation of row k at stream position `pos` into its LDS input row (lane group g takes a quarter of the
+// columns).  Reach: from the state s.  Synth: the non-truncating draw (a, b) of every feature pair.
+template <int ENV>
+__device__ __forceinline__ void osa_eval_obs(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
+                                             int k, unsigned long long pos, const float (&s)[6]) {
+  const int D = a.obs_dim;
+  if (ENV == OSA_EVAL_ENV_REACH) {
+    for (int c = g; c < D; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_reach_obs_col(s, c), c);
+  } else {
+    for (int pair = g; 2 * pair < D; pair += 4) {
+      float v0, v1, c2, d2;
+      osa_synth_obs_pair(a.seed, pos, k, pair, v0, v1, c2, d2);
+      xrow[2 * pair] = osa_eval_norm(a, norm_on, v0, 2 * pair);
+      if (2 * pair + 1 < D) xrow[2 * pair + 1] = osa_eval_norm(a, norm_on, v1, 2 * pair + 1);
+    }
+  }
+}
+
+template <int HT, int OT, int ENV>
+__global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
+  extern __shared__ f32x4 osa_eval_lds[];
+  const OsaNet& nd = a.nd;
+  const int lane = threadIdx.x, j = lane & 15, g = lane >> 4;
+  const int k = blockIdx.x * 16 + j;
+  const bool valid = k < a.K;
+  const int in_w = nd.obs_dim, INP = nd.INP;
+  float* __restrict__ xrow = reinterpret_cast<float*>(osa_eval_lds) + j * INP;
+  float* __restrict__ arow = reinterpret_cast<float*>(osa_eval_lds) + 16 * INP + j * OSA_EVAL_ACT_LD;
+  const bool norm_on = a.mean != nullptr && *a.count > 1;
+  // reset (stream position 0)
+  float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (ENV == OSA_EVAL_ENV_REACH) {
+    uint32_t w0[4], w1[4];
+    osa_philox(a.seed ^ OSA_REACH_KEY, 0, ((unsigned long long)k << 20) + 1, w0);
+    osa_philox(a.seed ^ OSA_REACH_KEY, 0, ((unsigned long long)k << 20) + 2, w1);
+    osa_reach_fresh(w0, w1, s);
+  }
+  if (valid) osa_eval_obs<ENV>(a, norm_on, xrow, g, k, 0, s);
+  float z = 1.f;  // Saute / Simmer safety budget left (evaluator.py:415)
+  if (a.saute && g == 0) xrow[a.obs_dim] = z;
+  double ret = 0.0, cost = 0.0;
+  int len = 0;
+  bool alive = valid;
+  for (int t = 0; t < a.max_steps; ++t) {
+    if (__ballot(alive) == 0) break;  // (one wave per workgroup: a uniform exit)
+    __syncthreads();  // this step's input rows are in LDS
+    float* rec = (a.trace != nullptr && alive) ? a.trace + ((long)t * a.K + k) * a.rec : nullptr;
+    if (rec)
+      for (int c = g; c < in_w; c += 4) rec[c] = xrow[c];
+    f32x4 h1[HT], h2[HT], out[OT];
+    osa_mlp_forward<HT, OT>(nd, a.params, valid ? xrow : nullptr, INP, true, h1, h2, out);
+#pragma unroll
+    for (int o = 0; o < OT; ++o) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int d = 16 * o + 4 * g + r;
+        if (d < nd.act_dim) {
+          const float act = osa_action_scale1(out[o][r], a.old_min[d], a.old_max[d], a.min_a, a.max_a);
+          arow[d] = act;
+          if (rec) rec[in_w + d] = act;
+        }
+      }
+    }
+    __syncthreads();  // the row's env action is in LDS; the forward's reads of the input row are done
+    const unsigned long long pos = (unsigned long long)t + 1;
+    const bool trunc = t + 1 >= a.horizon;
+    float rw, cs;
+    if (ENV == OSA_EVAL_ENV_REACH) {
+      if (rec && g == 0)
+        for (int q = 0; q < 6; ++q) rec[in_w + nd.act_dim + 3 + q] = s[q];
+      uint32_t w1[4];
+      osa_philox(a.seed ^ OSA_REACH_KEY, pos, ((unsigned long long)k << 20) + 2, w1);
+      osa_reach_transition(s, arow[0], arow[1], w1, rw, cs);
+    } else {
+      uint32_t w[4];
+      osa_philox(a.seed ^ OSA_SYNTH_RC_KEY, pos, (unsigned long long)k, w);
+      rw = osa_synth_reward(w);
+      cs = osa_synth_cost(w, a.cost_p);
+    }
+    if (rec && g == 0) {
+      rec[in_w + nd.act_dim + 0] = rw;
+      rec[in_w + nd.act_dim + 1] = cs;
+      rec[in_w + nd.act_dim + 2] = 1.f;
+    }
+    if (alive) {  // evaluator.py:455-468, in its order
+      if (a.saute) {
+        z = z - cs / a.budget;
+        z = z / a.saute_gamma;
+      }
+      ret = ret + (double)rw;
+      cost = cost + pow(a.cost_criteria, (double)len) * (double)cs;
+      const bool term = a.early_terminated && cost >= a.cost_limit;
+      len += 1;
+      if (term || trunc) {
+        alive = false;
+        if (g == 0) {
+          a.ep_ret[k] = ret;
+          a.ep_cost[k] = cost;
+          a.ep_len[k] = len;
+        }
+      } else {
+        osa_eval_obs<ENV>(a, norm_on, xrow, g, k, pos, s);
+        if (a.saute && g == 0) xrow[a.obs_dim] = z;
+      }
+    }
+  }
+  if (alive && g == 0) {  // max_steps reached first
+    a.ep_ret[k] = ret;
+    a.ep_cost[k] = cost;
+    a.ep_len[k] = len;
+  }
+}
+#pragma clang fp contract(fast)
+
+extern "C" {
+
+int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden, const float* params,
+                      const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
+                      const float* old_min, const float* old_max, float min_action, float max_action,
+                      unsigned long long seed, int horizon, float cost_p, int max_steps, int saute,
+                      float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
+                      double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
+                      void* stream) {
+  OSA_REQUIRE(K >= 1 && obs_dim >= 1 && act_dim >= 1 && max_steps >= 1 && horizon >= 1);
+  OSA_REQUIRE(params && old_min && old_max && max_action != min_action && ep_ret && ep_cost && ep_len);
+  OSA_REQUIRE((norm_mean == nullptr) == (norm_std == nullptr) && (norm_mean == nullptr) == (norm_count == nullptr));
+  OSA_REQUIRE(!saute || (saute_budget != 0.f && saute_gamma != 0.f));
+  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH) return OSA_EUNSUPPORTED;
+  if (env_kind == OSA_EVAL_ENV_REACH) OSA_REQUIRE(obs_dim >= 6 && act_dim >= 2);
+  const int in_w = obs_dim + (saute ? 1 : 0);
+  const int rc = osa_check_dims(in_w, act_dim, hidden);
+  if (rc != OSA_OK) return rc;
+  OsaEvalArgs a;
+  a.nd = osa_make_net(in_w, act_dim, hidden);
+  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD) * sizeof(float);
+  if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns
+  a.params = params;
+  a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
+  a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
+  a.old_min = old_min; a.old_max = old_max; a.min_a = min_action; a.max_a = max_action;
+  a.seed = seed; a.cost_p = cost_p;
+  a.saute = saute ? 1 : 0; a.budget = saute_budget; a.saute_gamma = saute_gamma;
+  a.early_terminated = early_terminated ? 1 : 0; a.cost_limit = cost_limit; a.cost_criteria = cost_criteria;
+  a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len; a.trace = trace;
+  a.rec = osa_eval_trace_floats(env_kind, obs_dim, act_dim, saute);
+  const dim3 grid((unsigned)((K + 15) / 16));
+#define OSA_CALL(HT, OT, NSB)                                                                                   \
+  do {                                                                                                          \
+    if (env_kind == OSA_EVAL_ENV_REACH)                                                                         \
+      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_REACH>), grid, dim3(64), lds,           \
+                         osa_stream(stream), a);                                                                \
+    else                                                                                                        \
+      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_SYNTH>), grid, dim3(64), lds,           \
+                         osa_stream(stream), a);                                                                \
+  } while (0)
+  OSA_DISPATCH_OT(a.nd, OSA_CALL);
+#undef OSA_CALL
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute) {
+  if (obs_dim < 1 || act_dim < 1) return 0;
+  return obs_dim + (saute ? 1 : 0) + act_dim + 3 + (env_kind == OSA_EVAL_ENV_REACH ? 6 : 0);
+}
+
+}  // extern "C"

@@ -1169,27 +1169,7 @@ static size_t osa_mb_lds_bytes(const OsaNet& nd) {
   return (size_t)(4 * nd.H + 2 * nd.OUTP) * (spc + 4) * sizeof(float) + 32 * sizeof(float) + (size_t)spc * sizeof(long);
 }
 
-static int osa_check_dims(int obs_dim, int act_dim, int hidden) {
-  if (obs_dim < 1 || act_dim < 1) return OSA_EINVAL;
-  // hidden_sizes [H, H]: 64 (all BASELINE configs; the persistent passes), and 32 / 128 / 256 on this per-step family
-  const int H_ = hidden & 0xFFFF;
-  if (H_ != 32 && H_ != 64 && H_ != 128 && H_ != 256) return OSA_EUNSUPPORTED;
-  if ((hidden >> 16) > OSA_ACT_IDENTITY) return OSA_EUNSUPPORTED;  // activation code (mlp_device.h)
-  if (act_dim > 32) return OSA_EUNSUPPORTED;
-  return OSA_OK;
-}
-
-// CALL(HT, OT, NSB): hidden tiles, output tiles, 16-sample blocks per chunk of osa_mb_grad_kernel (ignored by the
-// forward-only kernels)
-#define OSA_DISPATCH_OT(nd, CALL)                                   \
-  do {                                                              \
-    const int ot_ = (nd).OUTP == 16 ? 1 : 2;                        \
-    if ((nd).H == 64) { if (ot_ == 1) { CALL(4, 1, 4); } else { CALL(4, 2, 4); } }          \
-    else if ((nd).H == 128) { if (ot_ == 1) { CALL(8, 1, 4); } else { CALL(8, 2, 4); } }    \
-    else if ((nd).H == 256) { if (ot_ == 1) { CALL(16, 1, 2); } else { CALL(16, 2, 2); } }  \
-    else { if (ot_ == 1) { CALL(2, 1, 4); } else { CALL(2, 2, 4); } }                       \
-  } while (0)
-
+// (osa_check_dims and OSA_DISPATCH_OT: mlp_device.h)
 static long long* g_osa_dbg_clocks = nullptr;
 
 // fvp_kernel.hip: the Fisher-vector product with the parameters in LDS (OSA_EUNSUPPORTED: shape outside that kernel)

@@ -1,7 +1,7 @@
 // Rollout-side kernels: running observation normaliser (K2), action scaling (K3), per-step episode
 // accounting + bootstrap selection (the per-env Python loop of OnPolicyAdapter.rollout), and the
 // synthetic fixed-shape vector environment used by the throughput benchmark.
-#include "mlp_device.h"
+#include "env_device.h"
 
 // ------------------------------------------------------------------------------------------------
 // K2  Normalizer._push + normalize  (omnisafe/common/normalizer.py:88-139)
@@ -294,11 +294,8 @@ __global__ __launch_bounds__(256) void osa_synth_env_kernel(
   uint8_t trunc = 0;
   if (!reset_only) trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
   for (int pair = threadIdx.x; 2 * pair < D; pair += blockDim.x) {
-    uint32_t w[4];
-    osa_philox(seed, step, ((unsigned long long)n << 20) + pair, w);
     float a, b, c2, d2;
-    osa_box_muller(w[0], w[1], a, b);
-    osa_box_muller(w[2], w[3], c2, d2);  // second pair: the post-reset observation
+    osa_synth_obs_pair(seed, step, n, pair, a, b, c2, d2);  // (env_device.h)
     const int i0 = 2 * pair, i1 = 2 * pair + 1;
     if (trunc) {
       if (final_obs) {
@@ -314,11 +311,9 @@ __global__ __launch_bounds__(256) void osa_synth_env_kernel(
   }
   if (threadIdx.x == 0 && !reset_only) {
     uint32_t w[4];
-    osa_philox(seed ^ 0x9E3779B97F4A7C15ull, step, (unsigned long long)n, w);
-    float a, b;
-    osa_box_muller(w[0], w[1], a, b);
-    reward[n] = a;
-    cost[n] = (osa_u01(w[2]) <= cost_p) ? 1.f : 0.f;
+    osa_philox(seed ^ OSA_SYNTH_RC_KEY, step, (unsigned long long)n, w);
+    reward[n] = osa_synth_reward(w);  // (env_device.h)
+    cost[n] = osa_synth_cost(w, cost_p);
     terminated[n] = 0;
     truncated[n] = trunc;
     steps[n] = trunc ? 0 : steps[n] + 1;
@@ -334,27 +329,6 @@ __global__ __launch_bounds__(256) void osa_synth_env_kernel(
 // transition, lane k writes column k of the observation row (coalesced 240-byte row stores).
 // ------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-__device__ __forceinline__ float osa_reach_dist(float ux, float uy, float vx, float vy) {
-  const float dx = ux - vx, dy = uy - vy;
-  const float xx = dx * dx, yy = dy * dy;
-  return sqrtf(xx + yy);
-}
-
-__device__ __forceinline__ float osa_reach_obs_col(const float (&s)[6], int k) {
-  float v = 0.f;
-  if (k == 0) v = s[0];
-  if (k == 1) v = s[1];
-  if (k == 2) v = s[2] - s[0];
-  if (k == 3) v = s[3] - s[1];
-  if (k == 4) v = s[4] - s[0];
-  if (k == 5) v = s[5] - s[1];
-  return v;
-}
-
-__device__ __forceinline__ float osa_reach_uniform(uint32_t w) {  // [-1, 1]
-  return 2.f * osa_u01(w) - 1.f;
-}
-
 __global__ __launch_bounds__(64) void osa_reach_env_kernel(
     unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
     int D, int horizon, float* __restrict__ state, int* __restrict__ steps,
@@ -369,7 +343,7 @@ __global__ __launch_bounds__(64) void osa_reach_env_kernel(
   for (int k = 0; k < 6; ++k) s[k] = state[(long)n * 8 + k];
   uint32_t w0[4], w1[4];  // fresh positions for a reset: 6 uniforms
   osa_philox(seed ^ 0xD1B54A32D192ED03ull, step, ((unsigned long long)n << 20) + 1, w0);
-  osa_philox(seed ^ 0xD1B54A32D192ED03ull, step, ((unsigned long long)n << 20) + 2, w1);
+  osa_philox(seed ^ 0xD1B54A32D192ED03ull, step, ((unsigned long long)n << 20) + 2, w1);  // (env_device.h)
   const float fresh[6] = {osa_reach_uniform(w0[0]), osa_reach_uniform(w0[1]), osa_reach_uniform(w0[2]),
                           osa_reach_uniform(w0[3]), osa_reach_uniform(w1[0]), osa_reach_uniform(w1[1])};
   uint8_t trunc = 0;
@@ -378,22 +352,7 @@ __global__ __launch_bounds__(64) void osa_reach_env_kernel(
 #pragma unroll
     for (int k = 0; k < 6; ++k) s[k] = fresh[k];
   } else {
-    const float a0 = fminf(fmaxf(action[(long)n * ld_a + 0], -1.f), 1.f);
-    const float a1 = fminf(fmaxf(action[(long)n * ld_a + 1], -1.f), 1.f);
-    const float m0 = 0.1f * a0, m1 = 0.1f * a1;
-    const float qx = fminf(fmaxf(s[0] + m0, -1.5f), 1.5f);
-    const float qy = fminf(fmaxf(s[1] + m1, -1.5f), 1.5f);
-    const float d0 = osa_reach_dist(s[0], s[1], s[2], s[3]);
-    const float d1 = osa_reach_dist(qx, qy, s[2], s[3]);
-    const bool reached = d1 < 0.15f;
-    r = (d0 - d1) + (reached ? 1.f : 0.f);
-    c = (osa_reach_dist(qx, qy, s[4], s[5]) < 0.3f) ? 1.f : 0.f;
-    s[0] = qx;
-    s[1] = qy;
-    if (reached) {
-      s[2] = osa_reach_uniform(w1[2]);
-      s[3] = osa_reach_uniform(w1[3]);
-    }
+    osa_reach_transition(s, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], w1, r, c);
     trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
     if (trunc) {
       if (final_obs)

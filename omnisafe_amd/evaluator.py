@@ -1,0 +1,244 @@
+"""``Evaluator`` -- deterministic evaluation of a saved checkpoint (mirror of omnisafe/evaluator.py:355-490).
+
+``load_saved(save_dir, model_name)`` reads what this package's logger writes (``config.json``,
+``torch_save/<model_name>`` with keys ``pi`` and, with ``obs_normalize``, ``obs_normalizer``); ``evaluate()`` plays
+``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does.
+
+Two paths, one semantics:
+  persistent  a fused-family actor on a device env (SynthReach-v0, Synth*-v0): every episode in ONE launch of
+              osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a fresh env.
+  per-step    everything else (general networks, host envs, an env object given as ``env=``): the existing launches
+              per vector step -- Normalizer.apply, ConstraintActorCritic.step(deterministic=True, nets_mask=1) with
+              ActionScale fused, env.step -- and the same float64 sums in the same order.
+``OSA_EVAL_PATH=per-step|persistent`` forces a path (the persistent one raises when it cannot take the case).
+
+Deviations from the reference, decided for parallel episodes:
+  * Episodes run side by side in the lanes of a vector env, not one after another.
+  * The observation statistics stay FROZEN at the checkpoint's values.  The reference's Evaluator wraps the env in
+    ObsNormalize, whose ``normalize`` always pushes (omnisafe/common/normalizer.py:103), so its episode k sees
+    statistics moved by episodes 0 .. k-1; no parallel schedule can reproduce that drift.
+  * Device envs end episodes through their own ``horizon`` (env_cfgs); other envs get the reference's TimeLimit of
+    1000 steps (evaluator.py:179-180).
+"""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import envs as envs_mod
+from .config import Config
+from .models import ConstraintActorCritic
+from .normalizer import Normalizer
+from .spaces import Box
+
+TIME_LIMIT = 1000  # evaluator.py:179-180
+
+
+class Evaluator:  # pylint: disable=too-many-instance-attributes
+    def __init__(self, seed: int = 0, device='cuda:0', verbose: bool = True, env=None) -> None:
+        self._seed = int(seed)
+        self._device = torch.device(device)
+        self._verbose = verbose
+        self._user_env = env
+        self._cfgs: Config | None = None
+        self._actor: ConstraintActorCritic | None = None
+        self._normalizer: Normalizer | None = None
+        self.episode_lengths: list[float] = []
+        self.path: str | None = None  # path of the last evaluate(): 'persistent' or 'per-step'
+
+    # ------------------------------------------------------------------ loading
+    def load_saved(self, save_dir: str, model_name: str) -> None:
+        """evaluator.py:355-398 (no render options: the device envs do not render)."""
+        with open(os.path.join(save_dir, 'config.json'), encoding='utf-8') as f:
+            self._dict_cfgs = json.load(f)
+        self._cfgs = Config.dict2config(self._dict_cfgs)
+        ck = torch.load(os.path.join(save_dir, 'torch_save', model_name), weights_only=False)
+        self._env_id = self._cfgs.env_id
+        self._env_cfgs = dict(self._dict_cfgs.get('env_cfgs') or {})
+        algo = str(self._cfgs.algo)
+        a = self._cfgs.algo_cfgs
+        self._saute = 'Saute' in algo or 'Simmer' in algo
+        if self._saute:  # evaluator.py:165-172 (the float64 expression, then float32 through torch.ones(1))
+            self._budget = float(np.float32(a.safety_budget * (1 - a.saute_gamma ** a.max_ep_len)
+                                             / (1 - a.saute_gamma) / a.max_ep_len))
+            self._saute_gamma = float(a.saute_gamma)
+        self._early_terminated = 'EarlyTerminated' in algo
+        self._cost_limit = float(a.cost_limit) if self._early_terminated else 0.0
+        obs_dim, act_dim = self._env_dims()
+        in_dim = obs_dim + (1 if self._saute else 0)
+        self._actor = ConstraintActorCritic(Box(-np.inf, np.inf, (in_dim,)), Box(-1.0, 1.0, (act_dim,)),
+                                            self._cfgs.model_cfgs, epochs=1, device=self._device)
+        self._actor.actor.load_state_dict(ck['pi'])
+        self._normalizer = None
+        if a.obs_normalize:  # evaluator.py:174-177
+            self._normalizer = Normalizer((obs_dim,), clip=5, device=self._device)
+            self._normalizer.load_state_dict(ck['obs_normalizer'])
+
+    def _env_dims(self) -> tuple[int, int]:
+        if self._user_env is not None:
+            return (int(self._user_env.observation_space.shape[0]), int(self._user_env.action_space.shape[0]))
+        if self._env_id == 'SynthReach-v0':
+            return 60, 2
+        if self._env_id in envs_mod.SYNTH_DIMS:
+            return envs_mod.SYNTH_DIMS[self._env_id]
+        env = envs_mod.make(self._env_id, num_envs=1, device=self._device, **self._env_cfgs)
+        dims = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
+        env.close()
+        return dims
+
+    # ------------------------------------------------------------------ evaluation
+    def _persistent_ok(self) -> bool:
+        return (self._user_env is None and not self._actor.general
+                and envs_mod.ENV_REGISTRY.get(self._env_id) in (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv))
+
+    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, trace: bool = False):
+        """evaluator.py:399-490: ``(episode_rewards, episode_costs)``; ``episode_lengths`` is kept as an attribute.
+        ``trace=True`` also keeps the per-step record of osa_eval_episodes as ``self.trace`` (tests)."""
+        if self._actor is None:
+            raise ValueError('The policy must be loaded (load_saved) before evaluating the agent.')
+        num_episodes = int(num_episodes)
+        assert num_episodes >= 1
+        want = os.environ.get('OSA_EVAL_PATH', '')
+        if want not in ('', 'per-step', 'persistent'):
+            raise ValueError(f'OSA_EVAL_PATH={want!r}: per-step or persistent')
+        persistent = self._persistent_ok() if want == '' else want == 'persistent'
+        if persistent and not self._persistent_ok():
+            raise _lib.OsaError('OSA_EVAL_PATH=persistent: the persistent kernel takes a fused-family actor on a '
+                                f'device env (here {self._env_id}, general network: {self._actor.general})')
+        self.path = 'persistent' if persistent else 'per-step'
+        run = self._run_persistent if persistent else self._run_per_step
+        ret, cost, length = run(num_episodes, float(cost_criteria), trace)
+        rewards, costs = ret.cpu().tolist(), cost.cpu().tolist()
+        self.episode_lengths = [float(x) for x in length.cpu().tolist()]
+        if self._verbose:
+            for i, (r, c, n) in enumerate(zip(rewards, costs, self.episode_lengths)):
+                print(f'Episode {i} results:')
+                print(f'Episode reward: {r}')
+                print(f'Episode cost: {c}')
+                print(f'Episode length: {n}')
+            print('-' * 60)
+            print('Evaluation results:')
+            print(f'Average episode reward: {np.mean(a=rewards)}')
+            print(f'Average episode cost: {np.mean(a=costs)}')
+            print(f'Average episode length: {np.mean(a=self.episode_lengths)}')
+        return rewards, costs
+
+    def _make_env(self, K: int):
+        env = envs_mod.make(self._env_id, num_envs=K, device=self._device, **self._env_cfgs)
+        env.set_seed(self._seed)
+        return env
+
+    def _scale_bounds(self, env) -> tuple[torch.Tensor, torch.Tensor]:
+        f32 = dict(dtype=torch.float32, device=self._device)
+        lo = torch.as_tensor(env.action_space.low, **f32).reshape(-1).contiguous()
+        hi = torch.as_tensor(env.action_space.high, **f32).reshape(-1).contiguous()
+        return lo, hi
+
+    def _trace_floats(self, kind: int, obs_dim: int, act_dim: int) -> int:
+        return int(_lib.load().osa_eval_trace_floats(kind, obs_dim, act_dim, int(self._saute)))
+
+    def _run_persistent(self, K: int, cost_criteria: float, trace: bool):
+        lib = _lib.load(require_gpu=True)
+        env = self._make_env(K)
+        kind = 1 if isinstance(env, envs_mod.ReachVectorEnv) else 0  # OSA_EVAL_ENV_REACH / _SYNTH
+        obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
+        lo, hi = self._scale_bounds(env)
+        horizon = int(env.max_episode_steps)
+        dev = self._device
+        ret = torch.zeros(K, dtype=torch.float64, device=dev)
+        cost = torch.zeros(K, dtype=torch.float64, device=dev)
+        length = torch.zeros(K, dtype=torch.int32, device=dev)
+        tr = None
+        if trace:
+            tr = torch.zeros(horizon, K, self._trace_floats(kind, obs_dim, act_dim), dtype=torch.float32, device=dev)
+        nm = self._normalizer
+        ac = self._actor
+        _lib.check(lib.osa_eval_episodes(
+            kind, K, obs_dim, act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(nm._mean) if nm else None,
+            _lib.ptr(nm._std) if nm else None, _lib.ptr(nm._count) if nm else None,
+            float(nm._clip_value) if nm else 0.0, _lib.ptr(lo), _lib.ptr(hi), -1.0, 1.0,
+            env._seed & 0xFFFFFFFFFFFFFFFF, horizon, float(getattr(env, '_cost_p', 0.0)), horizon,
+            int(self._saute), self._budget if self._saute else 0.0, self._saute_gamma if self._saute else 0.0,
+            int(self._early_terminated), self._cost_limit, cost_criteria, _lib.ptr(ret), _lib.ptr(cost),
+            _lib.ptr(length), _lib.ptr(tr), _lib.stream_ptr()), 'osa_eval_episodes')
+        self.trace = tr
+        env.close()
+        return ret, cost, length
+
+    def _run_per_step(self, num_episodes: int, cost_criteria: float, trace: bool):
+        rets, costs, lens = [], [], []
+        done_eps = 0
+        self.trace = None
+        while done_eps < num_episodes:  # a user env plays batches of its num_envs lanes
+            env = self._user_env if self._user_env is not None else self._make_env(num_episodes)
+            r, c, n = self._per_step_batch(env, cost_criteria, trace)
+            rets.append(r)
+            costs.append(c)
+            lens.append(n)
+            done_eps += r.numel()
+            if self._user_env is None:
+                env.close()
+        return (torch.cat(rets)[:num_episodes], torch.cat(costs)[:num_episodes], torch.cat(lens)[:num_episodes])
+
+    def _per_step_batch(self, env, cost_criteria: float, trace: bool):  # pylint: disable=too-many-locals
+        """evaluator.py:425-468 for the K lanes of `env`; a lane stops counting at its first terminated / truncated
+        step (vector envs auto-reset; what a finished lane does afterwards is masked)."""
+        dev = self._device
+        K = int(env.num_envs)
+        obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
+        lo, hi = self._scale_bounds(env)
+        device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in (
+            envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv)
+        max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
+        is_reach = isinstance(env, envs_mod.ReachVectorEnv)
+        f64 = dict(dtype=torch.float64, device=dev)
+        ret, cost = torch.zeros(K, **f64), torch.zeros(K, **f64)
+        length = torch.zeros(K, dtype=torch.int32, device=dev)
+        alive = torch.ones(K, dtype=torch.bool, device=dev)
+        act_env = torch.empty(K, act_dim, dtype=torch.float32, device=dev)
+        z = torch.ones(K, 1, dtype=torch.float32, device=dev)
+        if self._saute:
+            budget = torch.tensor([self._budget], dtype=torch.float32, device=dev)
+            gamma = torch.tensor([self._saute_gamma], dtype=torch.float32, device=dev)
+        tr = None
+        if trace:
+            kind = 1 if is_reach else 0
+            tr = torch.zeros(max_steps, K, self._trace_floats(kind, obs_dim, act_dim), dtype=torch.float32,
+                             device=dev)
+        obs, _ = env.reset()
+        for t in range(max_steps):
+            x = obs.reshape(K, obs_dim).to(dev, torch.float32)
+            if self._normalizer is not None:
+                x = self._normalizer.apply(x)
+            if self._saute:  # evaluator.py:432-433
+                x = torch.cat([x, z], dim=1)
+            state = env.state[:, :6].clone() if (tr is not None and is_reach) else None
+            self._actor.step(x, deterministic=True, nets_mask=1, out={'scale': (act_env, lo, hi, -1.0, 1.0)})
+            obs, r, c, term, trunc, _ = env.step(act_env)
+            r = r.reshape(K).to(dev, torch.float32)
+            c = c.reshape(K).to(dev, torch.float32)
+            if tr is not None:
+                one = torch.ones(K, 1, dtype=torch.float32, device=dev)
+                parts = [x, act_env, r[:, None], c[:, None], one] + ([state] if state is not None else [])
+                tr[t] = torch.where(alive[:, None], torch.cat(parts, dim=1), torch.zeros((), device=dev))
+            if self._saute:  # evaluator.py:456-458, float32 (tensor divisors: true division)
+                z = (z - c[:, None] / budget) / gamma
+            # evaluator.py:460-466 in float64; cost_criteria ** length with the common length t of the live lanes
+            ret = torch.where(alive, ret + r.double(), ret)
+            cost = torch.where(alive, cost + (cost_criteria ** t) * c.double(), cost)
+            ended = term.reshape(K).to(dev).bool() | trunc.reshape(K).to(dev).bool()
+            if self._early_terminated:
+                ended = ended | (cost >= self._cost_limit)
+            length = length + alive.to(torch.int32)
+            alive = alive & ~ended
+            if not bool(alive.any()):
+                break
+        self.trace = tr
+        return ret, cost, length
+
+
+__all__ = ['Evaluator']

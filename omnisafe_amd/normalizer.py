@@ -78,6 +78,20 @@ class Normalizer:
             'osa_normalizer_apply')
         return y.reshape(data.shape) if out is None else y
 
+    def apply(self, data: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """clamp((x - mean)/std, -clip, clip) with the statistics as they are (no push): the normalisation of a
+        frozen checkpoint (omnisafe_amd.evaluator)."""
+        x = data.reshape(-1, self._D).to(self.device, torch.float32)
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        N, D = x.shape
+        y = out if out is not None else torch.empty(N, D, dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.osa_normalizer_apply(
+            _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), N, D, None, _lib.ptr(self._mean),
+            _lib.ptr(self._std), _lib.ptr(self._count), self._clip_value, _lib.stream_ptr()),
+            'osa_normalizer_apply')
+        return y
+
     def state_dict(self) -> 'OrderedDict[str, torch.Tensor]':
         sh = self._shape
         return OrderedDict([('_mean', self._mean.clone().view(sh)), ('_sumsq', self._sumsq.clone().view(sh)),
