@@ -365,6 +365,47 @@ int osa_ppo_pass_ext(int obs_dim, int act_dim, int hidden, float* params, float*
                  const float* adv_r, const float* adv_c, const long* perm, long M, int B,
                  const float* lagrange, const osa_ppo_hparams* hp, int loss_kind, int nets_mask,
                  float* step_stats, const osa_surrogate_ext* ext, void* stream);
+/* The passes of n INDEPENDENT agents in one launch.  The reference runs the seeds and variants of an experiment
+ * as one training per worker of a process pool (ExperimentGrid.run, omnisafe/common/experiment_grid.py:387-471);
+ * here every agent of the group is a member of one process and member s's pass -- exactly the arguments and the
+ * arithmetic of osa_ppo_pass_ext (has_ext = 0: ext == NULL) -- is three workgroups of a grid of 24 ceil(n / 8):
+ * bit-identical to n calls of osa_ppo_pass_ext, in the time of about one while 3 n compute units are free.  Members
+ * share (obs_dim, act_dim, hidden) and may differ in everything else (M, B, hyper-parameters, masks, ...), except
+ * that one launch is one kernel instantiation: all members have B <= 64 or all have B > 64, and all or none use an
+ * extended surrogate (OSA_EINVAL for a mixed array, nothing is launched; the caller issues one call per class).
+ * workspace: osa_ppo_pass_group_ws_bytes(n) bytes of device memory, 16-byte aligned, used by the launches of ONE
+ * stream: the members' argument blocks are staged there by copy launches ordered on `stream`, so the call may be
+ * repeated with the same workspace, and `members` reused, without waiting for the previous pass.  Any n >= 1 (more
+ * than compute units / 3 members: the workgroups queue).  The cooperative forms (osa_ppo_chunked_pass, the split and
+ * data-parallel passes) and osa_ppo_wide_pass are not grouped. */
+typedef struct osa_pass_member {
+  float* params;
+  float* adam_m;
+  float* adam_v;
+  int* adam_step;
+  const float* obs;
+  int ld_obs;
+  const float* act;
+  int ld_act;
+  const float* logp;
+  const float* target_value_r;
+  const float* target_value_c;
+  const float* adv_r;
+  const float* adv_c;
+  const long* perm;
+  long M;
+  int B;
+  const float* lagrange;
+  osa_ppo_hparams hp;
+  int loss_kind;
+  int nets_mask;
+  float* step_stats;
+  int has_ext; /* 0: plain surrogate, `ext` ignored */
+  osa_surrogate_ext ext;
+} osa_pass_member;
+size_t osa_ppo_pass_group_ws_bytes(int n);
+int osa_ppo_pass_group(int obs_dim, int act_dim, int hidden, const osa_pass_member* members, int n, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* Data-parallel optimiser step WITHOUT a per-step cross-GPU collective ("replicated data").  The data
  * arrays hold the all-gathered env-major rollouts of all `world` ranks ([world * M] rows, rank r at

@@ -2,6 +2,7 @@
 CPO update) behind the interfaces of PKU-Alignment/omnisafe.  See DESIGN.md and INTEGRATION.md."""
 from .agent import Agent  # noqa: F401
 from .evaluator import Evaluator  # noqa: F401
+from .group import AgentGroup  # noqa: F401
 from .plugin import install, uninstall  # noqa: F401
 
 __version__ = '0.1.0'

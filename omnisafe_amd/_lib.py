@@ -110,6 +110,9 @@ SIGNATURES: dict[str, tuple] = {
                                    _P, _P, _I, _I, _P, _P, _I, _P, _P]),
     'osa_ppo_pass_ext': (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I,
                               _P, _P, _I, _I, _P, _P, _P]),
+    # grouped plain pass (csrc/group_pass_kernel.hip): an array of models.PassMember
+    'osa_ppo_pass_group_ws_bytes': (C.c_size_t, [_I]),
+    'osa_ppo_pass_group': (_I, [_I, _I, _I, _P, _I, _P, C.c_size_t, _P]),
     'osa_adam_apply': (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     'osa_actor_fvp_raw': (_I, [_I, _I, _I, _P, _P, _P, _I, _L, _P, _I, _P, _P, _P]),
     'osa_fvp_finish': (_I, [_I, _P, _P, _F, _I, _I, _F, _P, _P]),

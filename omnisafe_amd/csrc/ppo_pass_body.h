@@ -1681,10 +1681,12 @@ static int osa_pass_so(const OsaNet& nd, F&& f) {
 // cooperative launch makes the runtime verify that (occupancy x CUs >= grid) instead of inferring it from the CU
 // count, and refuses the launch otherwise (OSA_EUNSUPPORTED: the caller takes the stepwise path).
 // (OSA_DP_PLAIN_LAUNCH=1: A/B switch of tools/dp_timing.py -- plain launch behind the occupancy check)
-template <auto K, bool COOP = false>
-static int osa_launch_pass_kernel(const OsaPassArgs& a, dim3 grid, hipStream_t stream) {
+// A: the kernel's argument block -- OsaPassArgs, or (group_pass_kernel.hip) the pointer to the members' staged blocks,
+// with `nd` the shape all of them share.
+template <auto K, bool COOP = false, class A>
+static int osa_launch_pass_kernel(const A& a, const OsaNet& nd, dim3 grid, hipStream_t stream) {
   static OsaPerDeviceOnce attr_set;
-  const size_t lds = osa_pass_lds_bytes(a.nd.KB, a.nd.OUTP / 16);
+  const size_t lds = osa_pass_lds_bytes(nd.KB, nd.OUTP / 16);
   if (lds > 160 * 1024) return OSA_EUNSUPPORTED;
   if (attr_set.need()) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1695,7 +1697,7 @@ static int osa_launch_pass_kernel(const OsaPassArgs& a, dim3 grid, hipStream_t s
   if constexpr (COOP) {
     static bool coop_refused = getenv("OSA_DP_PLAIN_LAUNCH") != nullptr && getenv("OSA_DP_PLAIN_LAUNCH")[0] == '1';
     if (!coop_refused) {
-      OsaPassArgs arg = a;
+      A arg = a;
       void* kargs[] = {&arg};
       const hipError_t e =
           hipLaunchCooperativeKernel(reinterpret_cast<const void*>(K), grid, dim3(256), kargs, (unsigned)lds, stream);
@@ -1714,4 +1716,44 @@ static int osa_launch_pass_kernel(const OsaPassArgs& a, dim3 grid, hipStream_t s
   }
   hipLaunchKernelGGL(K, grid, dim3(256), lds, stream, a);
   return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
+}
+
+template <auto K, bool COOP = false>
+static int osa_launch_pass_kernel(const OsaPassArgs& a, dim3 grid, hipStream_t stream) {
+  return osa_launch_pass_kernel<K, COOP>(a, a.nd, grid, stream);
+}
+
+// Argument block of the plain persistent pass (osa_ppo_pass_ext, and every member of osa_ppo_pass_group): checks
+// and operands; *extended: the EXT instantiation is needed (an `ext` that extends nothing takes the plain one).
+static inline int osa_plain_pass_args(OsaPassArgs& a, bool* extended, int obs_dim, int act_dim, int hidden,
+                                      float* params, float* adam_m, float* adam_v, int* adam_step, const float* obs,
+                                      int ld_obs, const float* act, int ld_act, const float* logp,
+                                      const float* target_value_r, const float* target_value_c, const float* adv_r,
+                                      const float* adv_c, const long* perm, long M, int B, const float* lagrange,
+                                      const osa_ppo_hparams* hp, int loss_kind, int nets_mask, float* step_stats,
+                                      const osa_surrogate_ext* ext) {
+  OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats);
+  OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0);
+  OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
+  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act)) return OSA_EUNSUPPORTED;
+  a = OsaPassArgs{};
+  a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
+  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
+                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
+  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
+  a.dp_world = 1;
+  *extended = false;
+  if (ext) {  // extended actor surrogates: single-chunk minibatches only (mask mean / penalty are per minibatch)
+    if (B > 64) return OSA_EUNSUPPORTED;
+    const bool need_old = ext->kl_coef != 0.f || ext->kl_mask_eta >= 0.f;
+    OSA_REQUIRE(!need_old || (ext->old_mean && ext->old_log_std && ext->ld_old_mean >= act_dim));
+    if (need_old || ext->cost_kappa > 0.f || ext->ratio_scale != 1.f) {
+      OSA_REQUIRE(ext->old_mean && ext->old_log_std);  // (the kernel reads them unconditionally)
+      a.old_mean = ext->old_mean; a.ld_old_mean = ext->ld_old_mean; a.old_log_std = ext->old_log_std;
+      a.ext_kl_coef = ext->kl_coef; a.ext_mask_eta = ext->kl_mask_eta; a.ext_ratio_scale = ext->ratio_scale;
+      a.ext_cost_kappa = ext->cost_kappa; a.ext_cost_excess = ext->cost_excess;
+      *extended = true;
+    }
+  }
+  return OSA_OK;
 }

@@ -77,37 +77,21 @@ int osa_ppo_pass_ext(int obs_dim, int act_dim, int hidden, float* params, float*
                  const float* lagrange, const osa_ppo_hparams* hp, int loss_kind, int nets_mask,
                  float* step_stats, const osa_surrogate_ext* ext, void* stream) {
   if (!osa_ppo_pass_supported(obs_dim, act_dim, hidden)) return OSA_EUNSUPPORTED;
-  OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats);
-  OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0);
-  OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
-  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act)) return OSA_EUNSUPPORTED;
-  OsaPassArgs a = {};
-  a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
-  osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
-                    target_value_r, target_value_c, adv_r, adv_c, lagrange, hp, loss_kind, nets_mask, step_stats);
-  a.perm = perm; a.M = M; a.B = B; a.nmb = (int)((M + B - 1) / B);
+  OsaPassArgs a;
+  bool extended = false;
+  const int rc = osa_plain_pass_args(a, &extended, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs,
+                                     ld_obs, act, ld_act, logp, target_value_r, target_value_c, adv_r, adv_c, perm, M,
+                                     B, lagrange, hp, loss_kind, nets_mask, step_stats, ext);
+  if (rc != OSA_OK) return rc;
   a.dbg = g_osa_pass_dbg;
-  a.dp_world = 1;
   {  // OSA_PASS_ONE_XCC=0: the three workgroups on three XCCs (A/B switch; traffic: profiles/r3_pmc_traffic*)
     static const bool one = !(getenv("OSA_PASS_ONE_XCC") && getenv("OSA_PASS_ONE_XCC")[0] == '0');
     a.one_xcc = one ? 1 : 0;
   }
   const int KB = a.nd.KB, OT = a.nd.OUTP / 16;
   hipStream_t st = osa_stream(stream);
-  if (ext) {  // extended actor surrogates: single-chunk minibatches only (mask mean / penalty are per minibatch)
-    if (B > 64) return OSA_EUNSUPPORTED;
-    const bool need_old = ext->kl_coef != 0.f || ext->kl_mask_eta >= 0.f;
-    OSA_REQUIRE(!need_old || (ext->old_mean && ext->old_log_std && ext->ld_old_mean >= act_dim));
-    if (!need_old && ext->cost_kappa <= 0.f && ext->ratio_scale == 1.f) {
-      ext = nullptr;  // nothing extended: the plain instantiation
-    } else {
-      OSA_REQUIRE(ext->old_mean && ext->old_log_std);  // (the kernel reads them unconditionally)
-      a.old_mean = ext->old_mean; a.ld_old_mean = ext->ld_old_mean; a.old_log_std = ext->old_log_std;
-      a.ext_kl_coef = ext->kl_coef; a.ext_mask_eta = ext->kl_mask_eta; a.ext_ratio_scale = ext->ratio_scale;
-      a.ext_cost_kappa = ext->cost_kappa; a.ext_cost_excess = ext->cost_excess;
-      return osa_pass_shapes(KB, OT, [&](auto K, auto O) { return osa_launch_pass_so<K, O, false, false, true>(a, st); });
-    }
-  }
+  if (extended)  // FOCOPS / CUP / P3O surrogates (single-chunk minibatches)
+    return osa_pass_shapes(KB, OT, [&](auto K, auto O) { return osa_launch_pass_so<K, O, false, false, true>(a, st); });
   return osa_pass_shapes(KB, OT, [&](auto K, auto O) {
     return (B > 64) ? osa_launch_pass_so<K, O, true>(a, st) : osa_launch_pass_so<K, O, false>(a, st);
   });

@@ -49,6 +49,17 @@ class SurrogateExt(C.Structure):
         super().__init__(None, 0, None, kl_coef, kl_mask_eta, ratio_scale, cost_kappa, cost_excess)
 
 
+class PassMember(C.Structure):
+    """ctypes mirror of ``osa_pass_member`` (include/omnisafe_amd.h): one agent's pass in osa_ppo_pass_group."""
+
+    _fields_ = [('params', C.c_void_p), ('adam_m', C.c_void_p), ('adam_v', C.c_void_p), ('adam_step', C.c_void_p),
+                ('obs', C.c_void_p), ('ld_obs', C.c_int), ('act', C.c_void_p), ('ld_act', C.c_int),
+                ('logp', C.c_void_p), ('target_value_r', C.c_void_p), ('target_value_c', C.c_void_p),
+                ('adv_r', C.c_void_p), ('adv_c', C.c_void_p), ('perm', C.c_void_p), ('M', C.c_long), ('B', C.c_int),
+                ('lagrange', C.c_void_p), ('hp', HParams), ('loss_kind', C.c_int), ('nets_mask', C.c_int),
+                ('step_stats', C.c_void_p), ('has_ext', C.c_int), ('ext', SurrogateExt)]
+
+
 class Layout:
     """Padded parameter block of one network + index maps to the reference tensor order."""
 

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from . import distributed as dist
-from .models import ConstraintActorCritic, HParams, SurrogateExt
+from .models import ConstraintActorCritic, HParams, PassMember, SurrogateExt
 
 NSTAT = 16
 
@@ -96,6 +96,13 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         # torch's current stream (bench.py turns this on for the timed region)
         self.profile_events: list | None = None
         self.last_path: str | None = None
+        # AgentGroup (group.py): `generator` -- the member's own device generator for the shuffles (None: torch's global
+        # one, the solo run); `pass_submit(updater, member)` -- called INSTEAD of the plain pass launch, returns the
+        # number of members of the grouped launch that carried the pass once that launch is enqueued; `last_group` --
+        # that number for the last pass of the last update (0: launched on its own)
+        self.generator: torch.Generator | None = None
+        self.pass_submit = None
+        self.last_group = 0
         self._graphed_pass = False
         self._use_wide = False
         self._split_xch: int | None = None  # uncached exchange buffer of the split wide pass (raw pointer)
@@ -230,6 +237,8 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
         int64 per row from torch's (seeded) device generator.  OSA_SHUFFLE=sort: the batched argsort of random
         62-bit keys of rounds 1-3 (torch / rocPRIM merge sorts: ~45 launches, 0.3 ms for 8 x 65 536)."""
         dev = self.ac.device
+        if generator is None:
+            generator = self.generator
         if os.environ.get('OSA_SHUFFLE', 'bijection') == 'sort':
             keys = torch.randint(0, 1 << 62, (rows, M), generator=generator, device=dev, dtype=torch.int64)
             p = keys.argsort(dim=1)
@@ -506,10 +515,26 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             self.ext.ld_old_mean = self._old_mean.stride(0)
             self.ext.old_log_std = self._old_log_std.data_ptr()
             ext = C.byref(self.ext)
-        _lib.check(self.lib.osa_ppo_pass_ext(
-            *ops, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(stats_rows), ext,
-            _lib.stream_ptr()), 'osa_ppo_pass_ext')
+        if self.pass_submit is not None:  # member of an AgentGroup: the group launches the members' passes together
+            self.last_group = int(self.pass_submit(self, self._pass_member(ops, lagrange, stats_rows)))
+        else:
+            _lib.check(self.lib.osa_ppo_pass_ext(
+                *ops, _lib.ptr(lagrange), C.byref(self.hp), self.loss_kind, self._nets_mask(), _lib.ptr(stats_rows),
+                ext, _lib.stream_ptr()), 'osa_ppo_pass_ext')
         self._profile_end(ev, 'osa_ppo_pass_kernel', M)
+
+    def _pass_member(self, ops: tuple, lagrange: torch.Tensor, stats_rows: torch.Tensor) -> PassMember:
+        """The arguments of this updater's osa_ppo_pass_ext call as an osa_pass_member (a copy: hp / ext by value)."""
+        m = PassMember()
+        (m.params, m.adam_m, m.adam_v, m.adam_step, m.obs, m.ld_obs, m.act, m.ld_act, m.logp, m.target_value_r,
+         m.target_value_c, m.adv_r, m.adv_c, m.perm, m.M, m.B) = ops[3:]
+        m.lagrange, m.loss_kind, m.nets_mask, m.step_stats = _lib.ptr(lagrange), self.loss_kind, self._nets_mask(), \
+            _lib.ptr(stats_rows)
+        C.memmove(C.byref(m.hp), C.byref(self.hp), C.sizeof(self.hp))
+        m.has_ext = int(self.ext is not None)
+        if self.ext is not None:
+            C.memmove(C.byref(m.ext), C.byref(self.ext), C.sizeof(self.ext))
+        return m
 
     # ------------------------------------------------------------------ one-shot peer exchange (dp_mode 'p2p')
     def _p2p_ok(self, data: dict) -> bool:
@@ -953,6 +978,7 @@ class PPOUpdater:  # pylint: disable=too-many-instance-attributes
             self.snapshot_old_distribution(obs)
         update_counts, final_kl, step = 0, 0.0, 0
         kl_dev = None
+        self.last_group = 0
         self._pass_fn = None
         self._graphed_pass = False
         # (with the minibatch's chunks on cooperating workgroups the persistent pass wins up to 1024 rows: 24.6 us per
