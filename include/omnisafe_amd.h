@@ -749,6 +749,27 @@ int osa_reach_env_step(unsigned long long seed, unsigned long long step,
                        uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                        void* stream);
 
+/* Lidar navigation vector CMDP "SynthNavGoal{0,1,2}-v0" (obs_dim >= 60, 2 actions; stand-in for the Safety-Gymnasium
+ * Goal tasks behind omnisafe/envs/safety_gymnasium_env.py:160-210 step / reset and envs/core.py:37-182, whose MuJoCo
+ * physics is third-party CPU code outside the reference repo; a specification of this package, not a port): a point
+ * robot with a unit heading u and a forward speed f.  Under clip(action,-1,1): f <- 0.9 f + 0.02 a0; u is turned by
+ * the rational rotation of parameter t = 0.15 a1 (c = (1 - t^2)/(1 + t^2), s = 2t/(1 + t^2)) and renormalised;
+ * p <- clip(p + f u, -2, 2).  reward = decrease of the distance to the goal, +1 and a new goal (the first of four
+ * candidates in [-1.5,1.5]^2 that keeps 0.55 from every hazard, else the fourth) when within 0.3 of it; cost = 1
+ * inside a hazard disc (radius 0.2) or, on level 2, a vase disc (radius 0.1).  level 0 / 1 / 2: 0 / 8 / 10 hazards,
+ * 0 / 1 / 10 vases.  Never terminates, truncates every `horizon` steps (gymnasium vector auto-reset convention as
+ * above).  state: N x 64 floats owned by the caller, updated in place: p(2) u(2) f f_prev t 0 goal(2) 0 0
+ * hazards(10 x 2) vases(10 x 2) 0(12).  obs row = [f, f - f_prev, t, u, 0 (7), goal lidar (16), hazard lidar (16),
+ * vase lidar (16), 0...]: an object at distance r in the egocentric 22.5-degree sector k reads max(0, 1 - r/3) in bin
+ * k, a bin keeps the maximum of its class.  float32 without fused multiply-adds, correctly rounded / and sqrt: a numpy
+ * twin reproduces every bit.  reset_only != 0 draws fresh states and zeroes `steps`. */
+int osa_nav_env_step(unsigned long long seed, unsigned long long step,
+                     const unsigned long long* step_base, int N, int obs_dim,
+                     int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                     float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                     uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Trust-region machinery (NaturalPG / TRPO / TRPOLag / CPO actor update)
  *
@@ -821,13 +842,15 @@ int osa_shuffle_rows(const long long* row_seeds, int rows, long M, long long* pe
  * float64: ep_ret += reward, ep_cost += cost_criteria^len * cost (:460-461), then len += 1; early_terminated != 0
  * ends the episode once ep_cost >= cost_limit (:462-466); an episode ends at its first terminated / truncated step
  * (the env's own `horizon`) or after max_steps steps.
- * env_kind: OSA_EVAL_ENV_SYNTH (osa_synth_env_step; cost_p used) or OSA_EVAL_ENV_REACH (osa_reach_env_step: obs_dim
- * >= 6, act_dim >= 2); anything else OSA_EUNSUPPORTED.  Outputs: ep_ret, ep_cost double[K], ep_len int32[K].
+ * env_kind: OSA_EVAL_ENV_SYNTH (osa_synth_env_step; cost_p used), OSA_EVAL_ENV_REACH (osa_reach_env_step: obs_dim
+ * >= 6, act_dim >= 2) or OSA_EVAL_ENV_NAV0 + level (osa_nav_env_step: obs_dim >= 60, act_dim >= 2, policy input <= 928
+ * columns); anything else OSA_EUNSUPPORTED.  Outputs: ep_ret, ep_cost double[K], ep_len int32[K].
  * trace (NULL in production): float[max_steps][K][osa_eval_trace_floats(...)], zero-initialised by the caller; the
  * record of (step, episode) is written while the episode plays: policy input row, env action, reward, cost, 1.0
- * (alive), and for SynthReach the 6-float state before the step.  Arguments are checked before any launch. */
+ * (alive), and the state before the step (SynthReach: 6 floats, SynthNavGoal: the 64-float row).  Arguments are checked before any launch. */
 #define OSA_EVAL_ENV_SYNTH 0
 #define OSA_EVAL_ENV_REACH 1
+#define OSA_EVAL_ENV_NAV0 16 /* + level 0 .. 2 */
 int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden, const float* params,
                       const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
                       const float* old_min, const float* old_max, float min_action, float max_action,

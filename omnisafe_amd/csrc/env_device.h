@@ -1,6 +1,6 @@
-// Per-env transitions of the two device-resident vector envs, shared by their per-step kernels
-// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel) and the persistent evaluation kernel
-// (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream position `step`, env
+// Per-env transitions of the device-resident vector envs, shared by their per-step kernels
+// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_nav_env_kernel) and the persistent evaluation
+// kernel (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream position `step`, env
 // index n), so a caller that replays env n at positions 0, 1, 2, ... sees the same episode as the per-step launches.
 #pragma once
 #include "mlp_device.h"
@@ -91,5 +91,226 @@ __device__ __forceinline__ void osa_reach_transition(float (&s)[6], float a0_in,
     s[2] = osa_reach_uniform(w1[2]);
     s[3] = osa_reach_uniform(w1[3]);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// SynthNavGoal{0,1,2}-v0: a point robot with heading and inertia, a resampled goal, static hazards and vases, seen
+// through three egocentric 16-bin lidars.  State row of an env, 64 floats:
+//   [0:2] p  [2:4] u (unit heading)  [4] f (forward speed)  [5] f_prev  [6] t (last turn parameter)  [7] 0
+//   [8:10] g  [10:12] 0  [12:32] hazards 10 x 2  [32:52] vases 10 x 2  [52:64] 0
+// The callers keep the row in LDS (`row`: the objects, read-only between resets) and its first ten floats in
+// registers (`d`: what a transition changes), the same in every lane that works on the env.  float32 with only
+// + - * / sqrt min max and compares, no fused multiply-adds: the numpy twin kept with the tests (tests/nav_twin.py)
+// computes the same bits.
+// ------------------------------------------------------------------------------------------------
+#define OSA_NAV_KEY 0xA0761D6478BD642Full
+#define OSA_NAV_STATE 64  // floats per state row
+#define OSA_NAV_DYN 10    // leading floats of the row that a transition changes
+#define OSA_NAV_HAZ 12    // first hazard column of the row
+#define OSA_NAV_VASE 32   // first vase column of the row
+#define OSA_NAV_OBS 60    // observation columns
+
+__device__ __forceinline__ int osa_nav_hazards(int level) { return level == 0 ? 0 : (level == 1 ? 8 : 10); }
+__device__ __forceinline__ int osa_nav_vases(int level) { return level == 0 ? 0 : (level == 1 ? 1 : 10); }
+
+// E[k] = (float32(cos(k pi / 8)), float32(sin(k pi / 8))) rounded from float64; lidar bin k lies between E[k] and
+// E[(k + 1) & 15].
+static __device__ const float OSA_NAV_EDGE[16][2] = {
+    {1.f, 0.f},
+    {0.923879504f, 0.382683426f},
+    {0.707106769f, 0.707106769f},
+    {0.382683426f, 0.923879504f},
+    {6.12323426e-17f, 1.f},
+    {-0.382683426f, 0.923879504f},
+    {-0.707106769f, 0.707106769f},
+    {-0.923879504f, 0.382683426f},
+    {-1.f, 1.22464685e-16f},
+    {-0.923879504f, -0.382683426f},
+    {-0.707106769f, -0.707106769f},
+    {-0.382683426f, -0.923879504f},
+    {-1.83697015e-16f, -1.f},
+    {0.382683426f, -0.923879504f},
+    {0.707106769f, -0.707106769f},
+    {0.923879504f, -0.382683426f},
+};
+
+// Uniform i of env n at position `pos`, ARENA (2 u01 - 1): word i % 4 of block first_block + i / 4.  Blocks 1 .. 13
+// hold the 52 uniforms of a reset, blocks 14 and 15 the eight of a transition's goal candidates.
+__device__ __forceinline__ float osa_nav_uniform(unsigned long long key, unsigned long long pos, int n,
+                                                 int first_block, int i) {
+  uint32_t w[4];
+  osa_philox(key, pos, ((unsigned long long)n << 20) + (unsigned long long)(first_block + (i >> 2)), w);
+  const int q = i & 3;
+  const uint32_t x = q == 0 ? w[0] : (q == 1 ? w[1] : (q == 2 ? w[2] : w[3]));
+  return 1.5f * (2.f * osa_u01(x) - 1.f);
+}
+
+// Of the four candidate points c[0:2] .. c[6:8], the first whose distance to every hazard is >= KEEP; the fourth if
+// none is.
+__device__ __forceinline__ void osa_nav_pick_goal(const float (&c)[8], const float* __restrict__ row, int level,
+                                                  float& gx, float& gy) {
+  const int H = osa_nav_hazards(level);
+  gx = c[6];
+  gy = c[7];
+  bool taken = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    bool ok = true;
+    for (int h = 0; h < H; ++h) {
+      const float* __restrict__ o = row + OSA_NAV_HAZ + 2 * h;
+      ok = ok && osa_reach_dist(c[2 * j], c[2 * j + 1], o[0], o[1]) >= 0.55f;
+    }
+    if (ok && !taken) {
+      gx = c[2 * j];
+      gy = c[2 * j + 1];
+    }
+    taken = taken || ok;
+  }
+}
+
+// Column `col` (12 .. 63) of a fresh state row: hazard and vase coordinates are reset uniforms 12 .. 51, slots past
+// the level's counts and the padding are 0.
+__device__ __forceinline__ float osa_nav_fresh_obj(unsigned long long key, unsigned long long pos, int n, int level,
+                                                   int col) {
+  const bool haz = col >= OSA_NAV_HAZ && col < OSA_NAV_HAZ + 2 * osa_nav_hazards(level);
+  const bool vase = col >= OSA_NAV_VASE && col < OSA_NAV_VASE + 2 * osa_nav_vases(level);
+  return (haz || vase) ? osa_nav_uniform(key, pos, n, 1, col) : 0.f;
+}
+
+// The first ten floats of a fresh state row (reset uniforms 0 .. 11); `row` already holds the fresh hazards.
+__device__ __forceinline__ void osa_nav_fresh(unsigned long long key, unsigned long long pos, int n, int level,
+                                              const float* __restrict__ row, float (&d)[OSA_NAV_DYN]) {
+  float u[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) u[i] = osa_nav_uniform(key, pos, n, 1, i);
+  d[0] = u[0];
+  d[1] = u[1];
+  const float xx = u[2] * u[2], yy = u[3] * u[3];
+  const float nrm = sqrtf(xx + yy);
+  d[2] = nrm > 0.f ? u[2] / nrm : 1.f;
+  d[3] = nrm > 0.f ? u[3] / nrm : 0.f;
+  d[4] = d[5] = d[6] = d[7] = 0.f;
+  const float c[8] = {u[4], u[5], u[6], u[7], u[8], u[9], u[10], u[11]};
+  osa_nav_pick_goal(c, row, level, d[8], d[9]);
+}
+
+// One transition of env n at position `pos` under the (unclamped) env action (a0, a1), all but its cost (which is a
+// function of the new position: osa_nav_cost, or the caller's own walk over the objects).
+__device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
+                                                float a0_in, float a1_in, unsigned long long key,
+                                                unsigned long long pos, int n, float& r) {
+  const float a0 = fminf(fmaxf(a0_in, -1.f), 1.f);
+  const float a1 = fminf(fmaxf(a1_in, -1.f), 1.f);
+  const float fa = 0.9f * d[4], fb = 0.02f * a0;
+  const float f2 = fa + fb;
+  const float t = 0.15f * a1;
+  const float tt = t * t;
+  const float den = 1.f + tt;
+  const float cs = (1.f - tt) / den;
+  const float sn = (2.f * t) / den;
+  const float cx = cs * d[2], sy = sn * d[3], sx = sn * d[2], cy = cs * d[3];
+  const float ux = cx - sy, uy = sx + cy;
+  const float xx = ux * ux, yy = uy * uy;
+  const float nrm = sqrtf(xx + yy);
+  const float u2x = ux / nrm, u2y = uy / nrm;
+  const float mx = f2 * u2x, my = f2 * u2y;
+  const float qx = fminf(fmaxf(d[0] + mx, -2.f), 2.f);
+  const float qy = fminf(fmaxf(d[1] + my, -2.f), 2.f);
+  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
+  const float d1 = osa_reach_dist(qx, qy, d[8], d[9]);
+  const bool reached = d1 < 0.3f;
+  r = (d0 - d1) + (reached ? 1.f : 0.f);
+  d[0] = qx;
+  d[1] = qy;
+  d[2] = u2x;
+  d[3] = u2y;
+  d[5] = d[4];
+  d[4] = f2;
+  d[6] = t;
+  if (reached) {
+    float cand[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cand[i] = osa_nav_uniform(key, pos, n, 14, i);
+    osa_nav_pick_goal(cand, row, level, d[8], d[9]);
+  }
+}
+
+// An object o seen from the state: body-frame coordinates (bx, by) of r = o - p and |r|.
+__device__ __forceinline__ void osa_nav_see(const float (&d)[OSA_NAV_DYN], float ox, float oy, float& bx, float& by,
+                                            float& dist) {
+  const float rx = ox - d[0], ry = oy - d[1];
+  const float b0 = d[2] * rx, b1 = d[3] * ry, b2 = d[2] * ry, b3 = d[3] * rx;
+  bx = b0 + b1;
+  by = b2 - b3;
+  const float xx = rx * rx, yy = ry * ry;
+  dist = sqrtf(xx + yy);
+}
+// Whether the body-frame direction (bx, by) lies in lidar bin k: E[k] x b >= 0 and E[k + 1] x b < 0.
+__device__ __forceinline__ bool osa_nav_in_bin(int k, float bx, float by) {
+  const float p0 = OSA_NAV_EDGE[k][0] * by, p1 = OSA_NAV_EDGE[k][1] * bx;
+  const float p2 = OSA_NAV_EDGE[(k + 1) & 15][0] * by, p3 = OSA_NAV_EDGE[(k + 1) & 15][1] * bx;
+  return p0 - p1 >= 0.f && p2 - p3 < 0.f;
+}
+__device__ __forceinline__ float osa_nav_reading(float dist) { return fmaxf(0.f, 1.f - dist / 3.f); }
+// Whether an object of class cls (1 hazard, 2 vase) at distance dist costs: vases on level 2 only.
+__device__ __forceinline__ bool osa_nav_hit(int level, int cls, float dist) {
+  return (cls == 1 && dist < 0.2f) || (cls == 2 && level == 2 && dist < 0.1f);
+}
+
+// Cost of the transition that led to the state: 1 inside a hazard disc or (level 2) a vase disc.
+__device__ __forceinline__ float osa_nav_cost(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level) {
+  bool hit = false;
+  const int H = osa_nav_hazards(level), V = level == 2 ? osa_nav_vases(level) : 0;
+  const float *__restrict__ hz = row + OSA_NAV_HAZ, *__restrict__ vs = row + OSA_NAV_VASE;
+  for (int h = 0; h < H; ++h) hit = hit || osa_nav_hit(level, 1, osa_reach_dist(d[0], d[1], hz[2 * h], hz[2 * h + 1]));
+  for (int v = 0; v < V; ++v) hit = hit || osa_nav_hit(level, 2, osa_reach_dist(d[0], d[1], vs[2 * v], vs[2 * v + 1]));
+  return hit ? 1.f : 0.f;
+}
+
+// The whole transition, one lane per env (eval_kernels.hip).
+__device__ __forceinline__ void osa_nav_transition(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
+                                                   float a0_in, float a1_in, unsigned long long key,
+                                                   unsigned long long pos, int n, float& r, float& c) {
+  osa_nav_advance(d, row, level, a0_in, a1_in, key, pos, n, r);
+  c = osa_nav_cost(d, row, level);
+}
+
+// Columns 0 - 11 of the observation row: 0 f, 1 f - f_prev, 2 t, 3 u_x, 4 u_y, 5 - 11 zero.
+__device__ __forceinline__ float osa_nav_sensor_col(const float (&d)[OSA_NAV_DYN], int col) {
+  float v = 0.f;
+  if (col == 0) v = d[4];
+  if (col == 1) v = d[4] - d[5];
+  if (col == 2) v = d[6];
+  if (col == 3) v = d[2];
+  if (col == 4) v = d[3];
+  return v;
+}
+
+// Column `col` of the current state row.
+__device__ __forceinline__ float osa_nav_state_col(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
+                                                   int col) {
+  float v = col >= OSA_NAV_DYN ? row[col] : 0.f;
+#pragma unroll
+  for (int k = 0; k < OSA_NAV_DYN; ++k)
+    if (col == k) v = d[k];
+  return v;
+}
+
+// Column `col` of the observation row: 0 - 11 osa_nav_sensor_col, 12 - 27 goal lidar, 28 - 43 hazard lidar, 44 - 59
+// vase lidar.  An object in bin k reads max(0, 1 - |r| / LIDAR_MAX) there; a bin reads the maximum over its class.
+__device__ __forceinline__ float osa_nav_obs_col(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
+                                                 int level, int col) {
+  if (col < 12 || col >= OSA_NAV_OBS) return osa_nav_sensor_col(d, col);
+  const int cls = (col - 12) >> 4, k = (col - 12) & 15;
+  const int cnt = cls == 0 ? 1 : (cls == 1 ? osa_nav_hazards(level) : osa_nav_vases(level));
+  const float* __restrict__ objs = row + (cls == 0 ? 8 : (cls == 1 ? OSA_NAV_HAZ : OSA_NAV_VASE));
+  float out = 0.f;
+  for (int i = 0; i < cnt; ++i) {
+    const float ox = cls == 0 ? d[8] : objs[2 * i], oy = cls == 0 ? d[9] : objs[2 * i + 1];
+    float bx, by, dist;
+    osa_nav_see(d, ox, oy, bx, by, dist);
+    if (osa_nav_in_bin(k, bx, by)) out = fmaxf(out, osa_nav_reading(dist));
+  }
+  return out;
 }
 #pragma clang fp contract(fast)

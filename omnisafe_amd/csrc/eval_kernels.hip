@@ -29,6 +29,7 @@ struct OsaEvalArgs {
   int* ep_len;
   float* trace;
   int rec;  // floats per trace record
+  int level;  // SynthNavGoal level (env kinds OSA_EVAL_ENV_NAV0 + level)
 };
 
 #define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
@@ -44,7 +45,8 @@ __device__ __forceinline__ float osa_eval_norm(const OsaEvalArgs& a, bool on, fl
 }
 
 // The env observation of row k at stream position `pos` into its LDS input row (lane group g takes a quarter of the
-// columns).  Reach: from the state s.  Synth: the non-truncating draw (a, b) of every feature pair.
+// columns).  Reach: from the state s (SynthNavGoal: osa_eval_obs_nav below).  Synth: the non-truncating draw (a, b)
+// of every feature pair.
 template <int ENV>
 __device__ __forceinline__ void osa_eval_obs(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
                                              int k, unsigned long long pos, const float (&s)[6]) {
@@ -59,6 +61,12 @@ __device__ __forceinline__ void osa_eval_obs(const OsaEvalArgs& a, bool norm_on,
       if (2 * pair + 1 < D) xrow[2 * pair + 1] = osa_eval_norm(a, norm_on, v1, 2 * pair + 1);
     }
   }
+}
+
+// SynthNavGoal: from the row's state (d: its first ten floats, srow: the row in LDS with the objects).
+__device__ __forceinline__ void osa_eval_obs_nav(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
+                                                 const float (&d)[OSA_NAV_DYN], const float* __restrict__ srow) {
+  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_nav_obs_col(d, srow, a.level, c), c);
 }
 
 template <int HT, int OT, int ENV>
@@ -80,7 +88,19 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
     osa_philox(a.seed ^ OSA_REACH_KEY, 0, ((unsigned long long)k << 20) + 2, w1);
     osa_reach_fresh(w0, w1, s);
   }
-  if (valid) osa_eval_obs<ENV>(a, norm_on, xrow, g, k, 0, s);
+  // SynthNavGoal: the state row of episode k in LDS behind the action rows, its first ten floats in registers
+  float* __restrict__ srow =
+      reinterpret_cast<float*>(osa_eval_lds) + 16 * (INP + OSA_EVAL_ACT_LD) + j * OSA_NAV_STATE;
+  float d[OSA_NAV_DYN] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (ENV == OSA_EVAL_ENV_NAV0) {
+    for (int c = OSA_NAV_DYN + g; c < OSA_NAV_STATE; c += 4)
+      srow[c] = valid ? osa_nav_fresh_obj(a.seed ^ OSA_NAV_KEY, 0, k, a.level, c) : 0.f;
+    __syncthreads();  // the row's hazards are in LDS (osa_nav_fresh places the goal away from them)
+    osa_nav_fresh(a.seed ^ OSA_NAV_KEY, 0, k, a.level, srow, d);
+    if (valid) osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
+  } else if (valid) {
+    osa_eval_obs<ENV>(a, norm_on, xrow, g, k, 0, s);
+  }
   float z = 1.f;  // Saute / Simmer safety budget left (evaluator.py:415)
   if (a.saute && g == 0) xrow[a.obs_dim] = z;
   double ret = 0.0, cost = 0.0;
@@ -110,7 +130,11 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
     const unsigned long long pos = (unsigned long long)t + 1;
     const bool trunc = t + 1 >= a.horizon;
     float rw, cs;
-    if (ENV == OSA_EVAL_ENV_REACH) {
+    if (ENV == OSA_EVAL_ENV_NAV0) {
+      if (rec)
+        for (int q = g; q < OSA_NAV_STATE; q += 4) rec[in_w + nd.act_dim + 3 + q] = osa_nav_state_col(d, srow, q);
+      osa_nav_transition(d, srow, a.level, arow[0], arow[1], a.seed ^ OSA_NAV_KEY, pos, k, rw, cs);
+    } else if (ENV == OSA_EVAL_ENV_REACH) {
       if (rec && g == 0)
         for (int q = 0; q < 6; ++q) rec[in_w + nd.act_dim + 3 + q] = s[q];
       uint32_t w1[4];
@@ -144,7 +168,10 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
           a.ep_len[k] = len;
         }
       } else {
-        osa_eval_obs<ENV>(a, norm_on, xrow, g, k, pos, s);
+        if (ENV == OSA_EVAL_ENV_NAV0)
+          osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
+        else
+          osa_eval_obs<ENV>(a, norm_on, xrow, g, k, pos, s);
         if (a.saute && g == 0) xrow[a.obs_dim] = z;
       }
     }
@@ -170,15 +197,17 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   OSA_REQUIRE(params && old_min && old_max && max_action != min_action && ep_ret && ep_cost && ep_len);
   OSA_REQUIRE((norm_mean == nullptr) == (norm_std == nullptr) && (norm_mean == nullptr) == (norm_count == nullptr));
   OSA_REQUIRE(!saute || (saute_budget != 0.f && saute_gamma != 0.f));
-  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH) return OSA_EUNSUPPORTED;
+  const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
+  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH && !nav) return OSA_EUNSUPPORTED;
   if (env_kind == OSA_EVAL_ENV_REACH) OSA_REQUIRE(obs_dim >= 6 && act_dim >= 2);
+  if (nav) OSA_REQUIRE(obs_dim >= OSA_NAV_OBS && act_dim >= 2);
   const int in_w = obs_dim + (saute ? 1 : 0);
   const int rc = osa_check_dims(in_w, act_dim, hidden);
   if (rc != OSA_OK) return rc;
   OsaEvalArgs a;
   a.nd = osa_make_net(in_w, act_dim, hidden);
-  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD) * sizeof(float);
-  if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns
+  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (nav ? OSA_NAV_STATE : 0)) * sizeof(float);
+  if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns (928 with a SynthNavGoal state)
   a.params = params;
   a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
   a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
@@ -188,10 +217,14 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   a.early_terminated = early_terminated ? 1 : 0; a.cost_limit = cost_limit; a.cost_criteria = cost_criteria;
   a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len; a.trace = trace;
   a.rec = osa_eval_trace_floats(env_kind, obs_dim, act_dim, saute);
+  a.level = nav ? env_kind - OSA_EVAL_ENV_NAV0 : 0;
   const dim3 grid((unsigned)((K + 15) / 16));
 #define OSA_CALL(HT, OT, NSB)                                                                                   \
   do {                                                                                                          \
-    if (env_kind == OSA_EVAL_ENV_REACH)                                                                         \
+    if (nav)                                                                                                    \
+      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_NAV0>), grid, dim3(64), lds,            \
+                         osa_stream(stream), a);                                                                \
+    else if (env_kind == OSA_EVAL_ENV_REACH)                                                                    \
       hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_REACH>), grid, dim3(64), lds,           \
                          osa_stream(stream), a);                                                                \
     else                                                                                                        \
@@ -206,7 +239,8 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
 
 int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute) {
   if (obs_dim < 1 || act_dim < 1) return 0;
-  return obs_dim + (saute ? 1 : 0) + act_dim + 3 + (env_kind == OSA_EVAL_ENV_REACH ? 6 : 0);
+  const int state = env_kind == OSA_EVAL_ENV_REACH ? 6 : (env_kind >= OSA_EVAL_ENV_NAV0 ? OSA_NAV_STATE : 0);
+  return obs_dim + (saute ? 1 : 0) + act_dim + 3 + state;
 }
 
 }  // extern "C"

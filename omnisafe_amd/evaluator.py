@@ -5,8 +5,8 @@
 ``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does.
 
 Two paths, one semantics:
-  persistent  a fused-family actor on a device env (SynthReach-v0, Synth*-v0): every episode in ONE launch of
-              osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a fresh env.
+  persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, Synth*-v0): every episode in ONE
+              launch of osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a fresh env.
   per-step    everything else (general networks, host envs, an env object given as ``env=``): the existing launches
               per vector step -- Normalizer.apply, ConstraintActorCritic.step(deterministic=True, nets_mask=1) with
               ActionScale fused, env.step -- and the same float64 sums in the same order.
@@ -36,6 +36,14 @@ from .normalizer import Normalizer
 from .spaces import Box
 
 TIME_LIMIT = 1000  # evaluator.py:179-180
+DEVICE_ENVS = (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv, envs_mod.NavGoalVectorEnv)
+
+
+def _env_kind(env) -> int:
+    """env_kind of osa_eval_episodes: OSA_EVAL_ENV_SYNTH / _REACH / _NAV0 + level."""
+    if isinstance(env, envs_mod.NavGoalVectorEnv):
+        return 16 + env.level
+    return 1 if isinstance(env, envs_mod.ReachVectorEnv) else 0
 
 
 class Evaluator:  # pylint: disable=too-many-instance-attributes
@@ -81,7 +89,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     def _env_dims(self) -> tuple[int, int]:
         if self._user_env is not None:
             return (int(self._user_env.observation_space.shape[0]), int(self._user_env.action_space.shape[0]))
-        if self._env_id == 'SynthReach-v0':
+        if self._env_id == 'SynthReach-v0' or self._env_id in envs_mod.NAV_LEVELS:
             return 60, 2
         if self._env_id in envs_mod.SYNTH_DIMS:
             return envs_mod.SYNTH_DIMS[self._env_id]
@@ -93,7 +101,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     # ------------------------------------------------------------------ evaluation
     def _persistent_ok(self) -> bool:
         return (self._user_env is None and not self._actor.general
-                and envs_mod.ENV_REGISTRY.get(self._env_id) in (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv))
+                and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS)
 
     def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, trace: bool = False):
         """evaluator.py:399-490: ``(episode_rewards, episode_costs)``; ``episode_lengths`` is kept as an attribute.
@@ -144,7 +152,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     def _run_persistent(self, K: int, cost_criteria: float, trace: bool):
         lib = _lib.load(require_gpu=True)
         env = self._make_env(K)
-        kind = 1 if isinstance(env, envs_mod.ReachVectorEnv) else 0  # OSA_EVAL_ENV_REACH / _SYNTH
+        kind = _env_kind(env)
         obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
         lo, hi = self._scale_bounds(env)
         horizon = int(env.max_episode_steps)
@@ -191,10 +199,10 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         K = int(env.num_envs)
         obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
         lo, hi = self._scale_bounds(env)
-        device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in (
-            envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv)
+        device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS
         max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
-        is_reach = isinstance(env, envs_mod.ReachVectorEnv)
+        state_w = 6 if isinstance(env, envs_mod.ReachVectorEnv) else (
+            64 if isinstance(env, envs_mod.NavGoalVectorEnv) else 0)  # state floats of a trace record
         f64 = dict(dtype=torch.float64, device=dev)
         ret, cost = torch.zeros(K, **f64), torch.zeros(K, **f64)
         length = torch.zeros(K, dtype=torch.int32, device=dev)
@@ -206,8 +214,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             gamma = torch.tensor([self._saute_gamma], dtype=torch.float32, device=dev)
         tr = None
         if trace:
-            kind = 1 if is_reach else 0
-            tr = torch.zeros(max_steps, K, self._trace_floats(kind, obs_dim, act_dim), dtype=torch.float32,
+            tr = torch.zeros(max_steps, K, self._trace_floats(_env_kind(env), obs_dim, act_dim), dtype=torch.float32,
                              device=dev)
         obs, _ = env.reset()
         for t in range(max_steps):
@@ -216,7 +223,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
                 x = self._normalizer.apply(x)
             if self._saute:  # evaluator.py:432-433
                 x = torch.cat([x, z], dim=1)
-            state = env.state[:, :6].clone() if (tr is not None and is_reach) else None
+            state = env.state[:, :state_w].clone() if (tr is not None and state_w) else None
             self._actor.step(x, deterministic=True, nets_mask=1, out={'scale': (act_env, lo, hi, -1.0, 1.0)})
             obs, r, c, term, trunc, _ = env.step(act_env)
             r = r.reshape(K).to(dev, torch.float32)

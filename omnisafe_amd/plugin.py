@@ -91,6 +91,10 @@ def install(algorithms: tuple[str, ...] | None = None) -> list[str]:
     if reach_ids:
         reg._class['OmnisafeAmdReachVectorEnv'] = amd_envs.ReachVectorEnv  # noqa: SLF001
         reg._support_envs['OmnisafeAmdReachVectorEnv'] = reach_ids  # noqa: SLF001
+    nav_ids = [e for e in amd_envs.NavGoalVectorEnv._support_envs if e not in known]  # noqa: SLF001
+    if nav_ids:
+        reg._class['OmnisafeAmdNavGoalVectorEnv'] = amd_envs.NavGoalVectorEnv  # noqa: SLF001
+        reg._support_envs['OmnisafeAmdNavGoalVectorEnv'] = nav_ids  # noqa: SLF001
     del omnisafe
     return swapped
 

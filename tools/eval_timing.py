@@ -3,7 +3,8 @@ initialised PPOLag checkpoint with an active observation normaliser.
 
     python tools/eval_timing.py [--ks 16,1024,16384] [--reps 3]
 
-Cases: SynthReach-v0 with horizon 1000, SynthPointGoal1-v0 and SynthHumanoid-v0 (horizon 1000).  One warm-up call per
+Cases: SynthReach-v0, SynthPointGoal1-v0, SynthHumanoid-v0 and SynthNavGoal1-v0, all at horizon 1000 (--cases picks
+some by id).  One warm-up call per
 (case, K, path), then the median of --reps timed calls (host clock around evaluate() + device synchronisation).
 Prints one JSON line."""
 from __future__ import annotations
@@ -30,7 +31,7 @@ from omnisafe_amd.spaces import Box  # noqa: E402
 
 DEV = 'cuda:0'
 CASES = [('SynthReach-v0', {'horizon': 1000}), ('SynthPointGoal1-v0', {'horizon': 1000}),
-         ('SynthHumanoid-v0', {'horizon': 1000})]
+         ('SynthHumanoid-v0', {'horizon': 1000}), ('SynthNavGoal1-v0', {'horizon': 1000})]
 
 
 def checkpoint(root: str, env_id: str, env_cfgs: dict) -> str:
@@ -39,7 +40,7 @@ def checkpoint(root: str, env_id: str, env_cfgs: dict) -> str:
     os.makedirs(os.path.join(root, 'torch_save'), exist_ok=True)
     with open(os.path.join(root, 'config.json'), 'w', encoding='utf-8') as f:
         json.dump(d, f)
-    obs_dim, act_dim = dict(SYNTH_DIMS, **{'SynthReach-v0': (60, 2)})[env_id]
+    obs_dim, act_dim = dict(SYNTH_DIMS, **{'SynthReach-v0': (60, 2), 'SynthNavGoal1-v0': (60, 2)})[env_id]
     torch.manual_seed(0)
     ac = ConstraintActorCritic(Box(-np.inf, np.inf, (obs_dim,)), Box(-1.0, 1.0, (act_dim,)),
                                Config.dict2config(d).model_cfgs, epochs=1, device=DEV)
@@ -55,10 +56,13 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument('--ks', default='16,1024,16384')
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--cases', default='')
     args = ap.parse_args()
     ks = [int(k) for k in args.ks.split(',')]
     rows = []
     for env_id, env_cfgs in CASES:
+        if args.cases and env_id not in args.cases.split(','):
+            continue
         root = checkpoint(tempfile.mkdtemp(prefix='osa_eval_timing_'), env_id, env_cfgs)
         for K in ks:
             row = {'env': env_id, 'horizon': env_cfgs['horizon'], 'K': K}
