@@ -39,7 +39,8 @@ struct OsaEvalArgs {
 __device__ __forceinline__ float osa_eval_norm(const OsaEvalArgs& a, bool on, float v, int col) {
   if (on) {
     v = (v - a.mean[col]) / a.std_[col];
-    v = fminf(fmaxf(v, -a.clip), a.clip);
+    v = v < -a.clip ? -a.clip : v;  // (NaN-preserving, as osa_normalize_kernel)
+    v = v > a.clip ? a.clip : v;
   }
   return v;
 }

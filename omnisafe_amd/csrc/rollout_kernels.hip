@@ -166,7 +166,9 @@ __global__ __launch_bounds__(256) void osa_normalize_kernel(
   const bool on = mask == nullptr || mask[r] != 0;
   if (on && *count > 1) {  // normalizer.py:104-107
     v = (v - mean[col]) / std_[col];
-    v = fminf(fmaxf(v, -clip), clip);
+    // torch.clamp: a NaN stays a NaN (fminf / fmaxf return their other operand and made it -clip)
+    v = v < -clip ? -clip : v;
+    v = v > clip ? clip : v;
   }
   y[(long)r * ld_y + col] = v;
 }

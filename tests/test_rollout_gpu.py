@@ -61,6 +61,13 @@ def test_normalizer_masked_push_matches_oracle():
     before = norm.mean.clone()
     norm.push(torch.zeros(300, 60, device=DEV), mask=torch.zeros(300, dtype=torch.uint8, device=DEV))
     assert torch.equal(before, norm.mean)
+    # ... and leaves the arrival ticket armed: the push behind it merges
+    x = (rng.standard_normal((300, 60)) * 3 + 1).astype(np.float32)
+    norm.push(torch.from_numpy(x).to(DEV))
+    ref.push(torch.from_numpy(x))
+    assert int(norm._count) == ref.count and not torch.equal(before, norm.mean)
+    np.testing.assert_allclose(norm.mean.cpu().numpy(), ref.mean.numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(norm._var.cpu().numpy(), ref.var.numpy(), rtol=1e-5)
 
 
 def test_normalizer_batch_sizes_share_one_workspace():
@@ -740,3 +747,8 @@ def test_episode_flush_kernel_equals_the_torch_form(T, N, p):
     np.testing.assert_allclose(float(out), float(x[ii].double().mean()), rtol=1e-6, atol=1e-8)
     _lib.check(lib.osa_gather_mean(_lib.ptr(x), None, 77, _lib.ptr(out), _lib.stream_ptr()), 'osa_gather_mean')
     np.testing.assert_allclose(float(out), float(x[:77].double().mean()), rtol=1e-6, atol=1e-8)
+    for n in (1, 8193):  # a single element; the second trip of 8 x 1024 with one live element
+        _lib.check(lib.osa_gather_mean(_lib.ptr(x), _lib.ptr(ii), n, _lib.ptr(out), _lib.stream_ptr()), 'osa_gather_mean')
+        np.testing.assert_allclose(float(out), float(x[ii[:n]].double().mean()), rtol=1e-6)
+        _lib.check(lib.osa_gather_mean(_lib.ptr(x), None, n, _lib.ptr(out), _lib.stream_ptr()), 'osa_gather_mean')
+        np.testing.assert_allclose(float(out), float(x[:n].double().mean()), rtol=1e-6)
