@@ -140,7 +140,7 @@ int osa_ppo_p2p_pass(int obs_dim, int act_dim, int hidden, float* params, float*
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats && peers);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && rank >= 0 && rank < world);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim && timeout_s > 0.0);
-  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act)) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act) || !osa_pass_index_ok(M, B)) return OSA_EUNSUPPORTED;
   OsaPassArgs a = {};
   for (int q = 0; q < world; ++q) {
     OSA_REQUIRE(peers[q] != nullptr && osa_p2p_slot(peers[q]) >= 0);  // only buffers this library allocated / opened

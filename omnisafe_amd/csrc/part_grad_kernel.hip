@@ -67,7 +67,8 @@ int osa_pass_partial_grad_balanced(int obs_dim, int act_dim, int hidden, float* 
                                    int loss_kind, int nets_mask, int max_wg, int max_stride, float* slabs,
                                    int* nslab, int* stride, void* stream) {
   if (!osa_ppo_pass_supported(obs_dim, act_dim, hidden) || B <= 64) return OSA_EUNSUPPORTED;
-  if (!osa_rows_ok(obs, ld_obs, 0.0)) return OSA_EUNSUPPORTED;  // (alignment only: one minibatch of B rows)
+  // (alignment only: one minibatch of B rows)
+  if (!osa_rows_ok(obs, ld_obs, 0.0) || !osa_pass_index_ok(B, B)) return OSA_EUNSUPPORTED;
   const int nchunk = (B + 63) / 64, nq = __builtin_popcount(nets_mask & 7);
   if (nq == 0 || max_wg < 1) return OSA_EUNSUPPORTED;
   const long ntasks = (long)nq * nchunk;

@@ -273,22 +273,26 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
   const int cstride = part ? (contig ? 1 : a.part_stride) : 1;
   const int cfirst = part ? (contig ? pc0 : rk) : (chunked ? cchunk : 0);
   const int nchunk = strided ? (contig ? pn : (nchunk_all - cfirst + cstride - 1) / cstride) : nchunk_all;
-  auto pos_ok = [&](long cidx) -> bool {  // global chunk counter -> (minibatch, chunk)
-    const long mb = cidx / nchunk, ch = cfirst + (cidx - mb * nchunk) * cstride;
-    const long inb = ch * 64 + 16 * wave + j;
-    return (mb < a.mb0 + a.nmb) && (inb < a.B) && (mb * a.B + inb < a.M);
+  // Sample positions are 32-bit: the entry points check M + 3 B + 128 < 2^31 (osa_pass_index_ok -- the furthest
+  // position formed, by the prefetch two chunks ahead) next to rows x ld < 2^31.  In `long` this cost 64-bit compares,
+  // multiply-adds and shifts in every step, scheduled into the backward phase.
+  const int M_ = (int)a.M;
+  auto pos_ok = [&](int cidx) -> bool {  // global chunk counter -> (minibatch, chunk)
+    const int mb = cidx / nchunk, ch = cfirst + (cidx - mb * nchunk) * cstride;
+    const int inb = ch * 64 + 16 * wave + j;
+    return (mb < a.mb0 + a.nmb) && (inb < a.B) && (mb * a.B + inb < M_);
   };
-  auto row_of = [&](long cidx) -> long {  // raw (unconsumed) load of the permutation entry
-    const long mb = cidx / nchunk, ch = cfirst + (cidx - mb * nchunk) * cstride;
-    const long pc = pos_ok(cidx) ? mb * a.B + ch * 64 + 16 * wave + j : 0;
-    return perm_p ? perm_p[pc] : pc;
+  auto row_of = [&](int cidx) -> int {  // raw (unconsumed) load of the permutation entry (a row number: < 2^31)
+    const int mb = cidx / nchunk, ch = cfirst + (cidx - mb * nchunk) * cstride;
+    const int pc = pos_ok(cidx) ? mb * a.B + ch * 64 + 16 * wave + j : 0;
+    return perm_p ? (int)perm_p[pc] : pc;
   };
   // Round 6: the first two permutation entries are requested BEFORE the parameter loads -- the gather's first hop (a cold
   // trip to HBM for the index, then the rows) used to start only after the workgroup's own start-up and weight requests
   // (2 400 + 2 700 cycles per segment of the large-batch step by the part kernel's phase marks)
-  const long cidx_first = (long)a.mb0 * nchunk;
-  const long r0_first = row_of(cidx_first);
-  const long r1_first = row_of(cidx_first + 1);
+  const int cidx_first = a.mb0 * nchunk;
+  const int r0_first = row_of(cidx_first);
+  const int r1_first = row_of(cidx_first + 1);
   // serial per-step chores (entropy, statistics) go to the first thread of wave 3: waves 0-2 also own the
   // bias-like parameters, so wave 3 is the one with slack before every barrier
   const bool leader = tid == 192;
@@ -410,7 +414,9 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
   // the chunks of a chunked pass from chunk 0
   const bool own_terms = !(chunked && cchunk != 0);
   const bool l2 = critic && a.hp.use_critic_norm && !part && own_terms;
-  const float c2 = 2.f * a.hp.critic_norm_coef;
+  // (0 where there is no L2 term: g + w * 0 == g for finite w, so the term is added unconditionally -- a run-time
+  // `if (l2)` cost one select per parameter on top of the fma, on the actor too)
+  const float c2 = l2 ? 2.f * a.hp.critic_norm_coef : 0.f;
   float lam = 0.f;
   if (is_actor && a.lagrange) lam = *a.lagrange;
   const float inv_1p_lam = 1.f / (1.f + lam);
@@ -419,6 +425,9 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
   constexpr bool vec_ok = true;
   const float* __restrict__ tgt = ((net == 1) ? a.tgt_r : a.tgt_c) + roff;
 
+  // SO: act_dim <= 2 is known at compile time, so of a lane's four action dimensions r only 0 and 1 can be real: the
+  // log-probability / dL/d(out) loops and the action gather run those two (the others' terms were exact zeros)
+  constexpr int NR = (SO && OT == 1) ? 2 : 4;
   // ---- prefetch machinery: everything this lane needs for its sample of one minibatch.
   // The loads are CONSUMER-FREE: addresses are clamped into the allocation instead of predicating the
   // loads, and all zero-masking (padding columns, invalid rows of a ragged last minibatch) happens
@@ -435,8 +444,8 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
   // re-issued as soon as layer 1 has consumed it, the per-sample scalars as soon as the loss has (no second
   // buffer: the kernel is register-bound -- 256 + ~250 AGPR in use -- and every spilled value costs VALU
   // moves that, on gfx950, add to the MFMA time instead of hiding under it).
-  auto fetch_x = [&](long rr, Pre& q) {
-    const float* xrow = obs_p + (int)rr * a.ld_obs;
+  auto fetch_x = [&](int rr, Pre& q) {
+    const float* xrow = obs_p + rr * a.ld_obs;
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       const int col0 = 16 * kb + 4 * g;
@@ -452,16 +461,17 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
       }
     }
   };
-  auto fetch_s = [&](long rr, Pre& q) {
+  auto fetch_s = [&](int rr, Pre& q) {
     // 32-bit index arithmetic (host guarantees M * ld < 2^31): 64-bit multiplies per load made the
     // prefetch issue itself cost ~1k cycles.  The actor-only loads sit behind a block-uniform branch.
-    const int ri = (int)rr;
+    const int ri = rr;
     if (is_actor) {
       const float* arow = act_p + ri * a.ld_act;
 #pragma unroll
       for (int o = 0; o < OT; ++o)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) q.act[4 * o + r] = arow[min(16 * o + 4 * g + r, nd.act_dim - 1)];
+        for (int r = 0; r < 4; ++r)
+          q.act[4 * o + r] = (r < NR) ? arow[min(16 * o + 4 * g + r, nd.act_dim - 1)] : 0.f;
       q.logp = logp_p[ri];
       q.adv_r = advr_p[ri];
       q.adv_c = advc_p[ri];
@@ -493,14 +503,14 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     for (int r = 0; r < 4; ++r) dm[o][r] = (16 * o + 4 * g + r) < nd.act_dim ? 1.f : 0.f;
   OSA_PART_MARK(10);
   Pre cur;
-  long cidx = cidx_first;
+  int cidx = cidx_first;
   {
-    const long r0 = r0_first;
+    const int r0 = r0_first;
     fetch_x(r0, cur);  // first gather in flight ...
     fetch_s(r0, cur);
     cur.valid = pos_ok(cidx);
   }
-  long row_nxt = r1_first;
+  int row_nxt = r1_first;
   OSA_PART_MARK(11);
   // ... while the remaining weights stream into LDS (matters for the one-step-per-launch dp mode)
   if constexpr (VPRO) {
@@ -583,8 +593,8 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
 
   const float invB_full = 1.f / (float)a.B;
   for (int mb = a.mb0; mb < a.mb0 + a.nmb; ++mb) {
-    const long mb_lo = (long)mb * a.B;
-    const int Bcur = (int)(min(mb_lo + a.B, a.M) - mb_lo);
+    const int mb_lo = mb * a.B;
+    const int Bcur = min(mb_lo + a.B, M_) - mb_lo;
     float invB = invB_full;  // (an IEEE division per step otherwise: ~12 VALU instructions)
     if (Bcur != a.B) invB = 1.f / (float)Bcur;  // ragged last minibatch
     // weight-gradient accumulators of this optimiser step (summed over its 64-row chunks)
@@ -760,7 +770,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
         // log(sigma) = log_std (the reference takes log(exp(log_std)): equal to float32 rounding)
         const f32x4 ls = *reinterpret_cast<const f32x4*>(sLS + 16 * o + 4 * g);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        for (int r = 0; r < NR; ++r) {
           const float dmr = dm[o][r];
           const float iv = __builtin_amdgcn_exp2f(ls[r] * -2.88539008177792681472f) * dmr;
           const float z = cur.act[4 * o + r] - out[o][r];
@@ -848,7 +858,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
 #pragma unroll
         for (int o = 0; o < OT; ++o) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
+          for (int r = 0; r < NR; ++r) {  // (r >= NR: dO, dLS stay the zeros they were initialised to)
             const float z = zv[o][r], iv = ivar[o][r];
             dO[o][r] = dlogp * z * iv;
             dLS[o][r] = dlogp * (z * z * iv - dm[o][r]);
@@ -903,7 +913,18 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     };
     if (small_out) {
       // z2[f] = sum_d W3[d][f] dO[d] with dO of this lane's sample held by lane group 0 (d = r)
-      const float d0 = __shfl(dO[0][0], j, 64), d1 = __shfl(dO[0][1], j, 64);
+      // Lane groups 1-3 hold +-0 there (the actor's padding dimensions are masked by dm, critics write dO for g == 0
+      // only), so the sum over the four groups IS group 0's value in all of them, exactly -- on the VALU
+      // (v_permlane16/32_swap) instead of two ds_bpermute round trips the whole z2 computation waits for.  (EXT keeps
+      // the shuffle: its KL terms are added to dO.)
+      float d0, d1;
+      if constexpr (!EXT) {
+        d0 = osa_sum_over_groups(dO[0][0]);
+        d1 = osa_sum_over_groups(dO[0][1]);
+      } else {
+        d0 = __shfl(dO[0][0], j, 64);
+        d1 = __shfl(dO[0][1], j, 64);
+      }
       load_w2t(0, wt[0]);  // first W2^T block, in flight meanwhile
 #pragma unroll
       for (int t = 0; t < HT; ++t) {
@@ -1093,7 +1114,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
 #pragma unroll
     for (int ti = 0; ti < HT; ++ti) {
       const f32x4 w = w2r[ti];
-      if (l2) g2[ti] = g2[ti] + w * c2;
+      g2[ti] = g2[ti] + w * c2;
       if constexpr (coop && !P2P) xs4[ti * 256 + tid] = g2[ti];  // (P2P: the own gradient stays in registers)
       acc_p = acc_p + w * w;
       acc_g = acc_g + g2[ti] * g2[ti];
@@ -1101,7 +1122,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       const f32x4 w = w1r[kb];
-      if (l2) g1[kb] = g1[kb] + w * c2;
+      g1[kb] = g1[kb] + w * c2;
       if constexpr (coop && !P2P) xs4[(HT + kb) * 256 + tid] = g1[kb];
       acc_p = acc_p + w * w;
       acc_g = acc_g + g1[kb] * g1[kb];
@@ -1109,7 +1130,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
 #pragma unroll
     for (int o = 0; o < OT; ++o) {
       const f32x4 w = w3r[o];
-      if (l2) g3[o] = g3[o] + w * c2;
+      g3[o] = g3[o] + w * c2;
       if constexpr (coop && !P2P) xs4[(HT + KB + o) * 256 + tid] = g3[o];
       acc_p = acc_p + w * w;
       acc_g = acc_g + g3[o] * g3[o];
@@ -1117,7 +1138,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     float gsq = (acc_g.x + acc_g.y) + (acc_g.z + acc_g.w);
     float psq = (acc_p.x + acc_p.y) + (acc_p.z + acc_p.w);
     if (boff >= 0) {
-      if (l2) gb += c2 * wb;
+      gb += c2 * wb;
       psq += wb * wb;
       gsq += gb * gb;
     }
@@ -1653,6 +1674,10 @@ static inline size_t osa_pass_lds_bytes(int KB, int OT) {
   return fl * sizeof(float);
 }
 
+// The pass body forms sample positions (minibatch x B + row in the minibatch) in int32, up to the row it prefetches two
+// chunks ahead of the last one: false = the pass is too long for that (OSA_EUNSUPPORTED at every entry point).
+static inline bool osa_pass_index_ok(long M, int B) { return M + 3L * B + 128 <= 2147483647L; }
+
 // Calls f(std::integral_constant<int, KB>, std::integral_constant<int, OT>) for the shape (KB = 1..6 input blocks,
 // OT = 1..2 output tiles) the pass kernels are instantiated for; OSA_EUNSUPPORTED for any other.
 template <int I = 0, class F>
@@ -1735,7 +1760,7 @@ static inline int osa_plain_pass_args(OsaPassArgs& a, bool* extended, int obs_di
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim);
-  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act)) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M, ld_act) || !osa_pass_index_ok(M, B)) return OSA_EUNSUPPORTED;
   a = OsaPassArgs{};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
   osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,

@@ -204,7 +204,7 @@ int osa_ppo_dp_step_phase(int obs_dim, int act_dim, int hidden, float* params, f
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats && slabs);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && world >= 1);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim && step_index >= 0 && (long)step_index * B < M);
-  if (!osa_rows_ok(obs, ld_obs, (double)M * world)) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M * world) || !osa_pass_index_ok(M, B)) return OSA_EUNSUPPORTED;
   OsaPassArgs a = {};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
   osa_fill_operands(a, obs_dim, act_dim, hidden, params, adam_m, adam_v, adam_step, obs, ld_obs, act, ld_act, logp,
@@ -347,7 +347,8 @@ static int osa_coop_pass(int obs_dim, int act_dim, int hidden, float* params, fl
   OSA_REQUIRE(params && adam_m && adam_v && adam_step && obs && act && logp && hp && step_stats);
   OSA_REQUIRE(target_value_r && target_value_c && adv_r && adv_c && M > 0 && B > 0 && world >= 1);
   OSA_REQUIRE(exchange && sync && ld_obs >= obs_dim && ld_act >= act_dim);
-  if (!osa_rows_ok(obs, ld_obs, (double)M * (chunk ? ranks : world))) return OSA_EUNSUPPORTED;
+  if (!osa_rows_ok(obs, ld_obs, (double)M * (chunk ? ranks : world)) || !osa_pass_index_ok(M, B))
+    return OSA_EUNSUPPORTED;
   // all 3 * world workgroups must be co-resident (one per compute unit: ~150 KB of LDS each)
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -390,7 +391,8 @@ int osa_pass_partial_grad(int obs_dim, int act_dim, int hidden, float* params, c
                           const long* idx, int B, const float* lagrange, const osa_ppo_hparams* hp,
                           int loss_kind, int nets_mask, int nblk, float* slabs, void* stream) {
   if (!osa_ppo_pass_supported(obs_dim, act_dim, hidden) || B <= 64) return OSA_EUNSUPPORTED;
-  if (!osa_rows_ok(obs, ld_obs, 0.0)) return OSA_EUNSUPPORTED;  // (alignment only: one minibatch of B rows)
+  // (alignment only: one minibatch of B rows)
+  if (!osa_rows_ok(obs, ld_obs, 0.0) || !osa_pass_index_ok(B, B)) return OSA_EUNSUPPORTED;
   OsaPassArgs a = {};
   a.ext_ratio_scale = 1.f; a.ext_mask_eta = -1.f;
   // Adam state untouched in this mode
