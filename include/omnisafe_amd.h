@@ -770,6 +770,30 @@ int osa_nav_env_step(unsigned long long seed, unsigned long long step,
                      uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                      void* stream);
 
+/* Circle-running vector CMDP "SynthNavCircle{0,1,2}-v0" (obs_dim >= 28, 2 actions; stand-in for the Safety-Gymnasium
+ * Circle tasks behind omnisafe/envs/safety_gymnasium_env.py:160-210 step / reset, whose MuJoCo physics is third-party
+ * CPU code outside the reference repo; a specification of this package, not a port): the robot of SynthNavGoal -- under
+ * a = clip(action,-1,1): f <- 0.9 f + 0.02 a0; u turned by the rational rotation of parameter t = 0.15 a1 and
+ * renormalised; m = f u; q = clip(p + m, -2, 2); p <- q -- is paid for running round the origin counter-clockwise:
+ * reward = ((m_y q_x - m_x q_y) / |q|) / (1 + ||q| - 1|), 0 where |q| = 0.  cost of the transition that led to q:
+ * level 0 none, level 1: 1 if |q_x| > 0.75, level 2: 1 if |q_x| > 0.75 or |q_y| > 0.75 (the walls are not observed).
+ * The unit circle leaves either corridor, so the unconstrained optimum is infeasible on levels 1 and 2.  Never
+ * terminates, truncates every `horizon` steps (gymnasium vector auto-reset convention as above).  state: N x 8 floats
+ * owned by the caller, updated in place: p(2) u(2) f f_prev t 0.  A reset of env n at stream position pos takes
+ * uniforms 0 .. 3 in (-1.5, 1.5] of Philox block 1 keyed seed ^ OSA_CIRCLE_KEY (0xE7037ED1A0B428DB; counter as
+ * osa_nav_env_step's): p = 0.4 (u0, u1), u = (u2, u3) normalised ((1, 0) if the norm is 0), the rest 0; a truncating
+ * step at position pos draws its fresh state at the same pos; transitions draw nothing.  obs row = [f, f - f_prev, t,
+ * u, 0 (7), lidar of the origin (16), 0...]: the origin reads max(0, 1 - |p|/3) in the egocentric 22.5-degree sector it
+ * falls in (osa_nav_env_step's goal lidar with the goal at (0, 0)); at p = (0, 0) no bin is lit.  float32 without fused
+ * multiply-adds, correctly rounded / and sqrt: a numpy twin reproduces every bit.  reset_only != 0 draws fresh states
+ * and zeroes `steps`.  Launch: half a wave per env (two envs per 64-lane workgroup). */
+int osa_circle_env_step(unsigned long long seed, unsigned long long step,
+                        const unsigned long long* step_base, int N, int obs_dim,
+                        int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                        float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                        uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Trust-region machinery (NaturalPG / TRPO / TRPOLag / CPO actor update)
  *
@@ -843,14 +867,17 @@ int osa_shuffle_rows(const long long* row_seeds, int rows, long M, long long* pe
  * ends the episode once ep_cost >= cost_limit (:462-466); an episode ends at its first terminated / truncated step
  * (the env's own `horizon`) or after max_steps steps.
  * env_kind: OSA_EVAL_ENV_SYNTH (osa_synth_env_step; cost_p used), OSA_EVAL_ENV_REACH (osa_reach_env_step: obs_dim
- * >= 6, act_dim >= 2) or OSA_EVAL_ENV_NAV0 + level (osa_nav_env_step: obs_dim >= 60, act_dim >= 2, policy input <= 928
- * columns); anything else OSA_EUNSUPPORTED.  Outputs: ep_ret, ep_cost double[K], ep_len int32[K].
+ * >= 6, act_dim >= 2), OSA_EVAL_ENV_NAV0 + level (osa_nav_env_step: obs_dim >= 60, act_dim >= 2, policy input <= 928
+ * columns) or OSA_EVAL_ENV_CIRCLE0 + level (osa_circle_env_step: obs_dim >= 28, act_dim >= 2; the state stays in
+ * registers); anything else OSA_EUNSUPPORTED.  Outputs: ep_ret, ep_cost double[K], ep_len int32[K].
  * trace (NULL in production): float[max_steps][K][osa_eval_trace_floats(...)], zero-initialised by the caller; the
  * record of (step, episode) is written while the episode plays: policy input row, env action, reward, cost, 1.0
- * (alive), and the state before the step (SynthReach: 6 floats, SynthNavGoal: the 64-float row).  Arguments are checked before any launch. */
+ * (alive), and the state before the step (SynthReach: 6 floats, SynthNavGoal: the 64-float row,
+ * SynthNavCircle: the 8-float row).  Arguments are checked before any launch. */
 #define OSA_EVAL_ENV_SYNTH 0
 #define OSA_EVAL_ENV_REACH 1
 #define OSA_EVAL_ENV_NAV0 16 /* + level 0 .. 2 */
+#define OSA_EVAL_ENV_CIRCLE0 32 /* + level 0 .. 2 */
 int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden, const float* params,
                       const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
                       const float* old_min, const float* old_max, float min_action, float max_action,

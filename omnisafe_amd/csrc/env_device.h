@@ -1,7 +1,8 @@
 // Per-env transitions of the device-resident vector envs, shared by their per-step kernels
-// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_nav_env_kernel) and the persistent evaluation
-// kernel (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream position `step`, env
-// index n), so a caller that replays env n at positions 0, 1, 2, ... sees the same episode as the per-step launches.
+// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_nav_env_kernel, osa_circle_env_kernel) and the
+// persistent evaluation kernel (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream
+// position `step`, env index n), so a caller that replays env n at positions 0, 1, 2, ... sees the same episode as the
+// per-step launches.
 #pragma once
 #include "mlp_device.h"
 
@@ -194,11 +195,10 @@ __device__ __forceinline__ void osa_nav_fresh(unsigned long long key, unsigned l
   osa_nav_pick_goal(c, row, level, d[8], d[9]);
 }
 
-// One transition of env n at position `pos` under the (unclamped) env action (a0, a1), all but its cost (which is a
-// function of the new position: osa_nav_cost, or the caller's own walk over the objects).
-__device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
-                                                float a0_in, float a1_in, unsigned long long key,
-                                                unsigned long long pos, int n, float& r) {
+// The motion of a transition under the (unclamped) env action (a0, a1): f <- 0.9 f + 0.02 a0, the heading turned by the
+// rational rotation of parameter t = 0.15 a1 and renormalised, p <- clip(p + m, -2, 2) with m = f u the attempted
+// displacement.  Shared by SynthNavGoal and SynthNavCircle.
+__device__ __forceinline__ void osa_nav_move(float (&d)[OSA_NAV_DYN], float a0_in, float a1_in, float& mx, float& my) {
   const float a0 = fminf(fmaxf(a0_in, -1.f), 1.f);
   const float a1 = fminf(fmaxf(a1_in, -1.f), 1.f);
   const float fa = 0.9f * d[4], fb = 0.02f * a0;
@@ -213,20 +213,28 @@ __device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const f
   const float xx = ux * ux, yy = uy * uy;
   const float nrm = sqrtf(xx + yy);
   const float u2x = ux / nrm, u2y = uy / nrm;
-  const float mx = f2 * u2x, my = f2 * u2y;
-  const float qx = fminf(fmaxf(d[0] + mx, -2.f), 2.f);
-  const float qy = fminf(fmaxf(d[1] + my, -2.f), 2.f);
-  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
-  const float d1 = osa_reach_dist(qx, qy, d[8], d[9]);
-  const bool reached = d1 < 0.3f;
-  r = (d0 - d1) + (reached ? 1.f : 0.f);
-  d[0] = qx;
-  d[1] = qy;
+  mx = f2 * u2x;
+  my = f2 * u2y;
+  d[0] = fminf(fmaxf(d[0] + mx, -2.f), 2.f);
+  d[1] = fminf(fmaxf(d[1] + my, -2.f), 2.f);
   d[2] = u2x;
   d[3] = u2y;
   d[5] = d[4];
   d[4] = f2;
   d[6] = t;
+}
+
+// One transition of env n at position `pos` under the (unclamped) env action (a0, a1), all but its cost (which is a
+// function of the new position: osa_nav_cost, or the caller's own walk over the objects).
+__device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
+                                                float a0_in, float a1_in, unsigned long long key,
+                                                unsigned long long pos, int n, float& r) {
+  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
+  float mx, my;
+  osa_nav_move(d, a0_in, a1_in, mx, my);
+  const float d1 = osa_reach_dist(d[0], d[1], d[8], d[9]);
+  const bool reached = d1 < 0.3f;
+  r = (d0 - d1) + (reached ? 1.f : 0.f);
   if (reached) {
     float cand[8];
 #pragma unroll
@@ -312,5 +320,59 @@ __device__ __forceinline__ float osa_nav_obs_col(const float (&d)[OSA_NAV_DYN], 
     if (osa_nav_in_bin(k, bx, by)) out = fmaxf(out, osa_nav_reading(dist));
   }
   return out;
+}
+
+// ------------------------------------------------------------------------------------------------
+// SynthNavCircle{0,1,2}-v0: the robot of SynthNavGoal (osa_nav_move) is paid for running round the origin on the
+// circle of radius 1 and charged for leaving a corridor |x| <= 0.75 (level 1) or the square |x|, |y| <= 0.75 (level 2)
+// that the circle does not fit in; level 0 never costs.  State row of an env, 8 floats: the first eight of
+// SynthNavGoal's row.  The callers keep it as a SynthNavGoal `d` whose goal d[8:10] is pinned at (0, 0): the 16-bin
+// lidar of the circle's centre is then the goal lidar.  No objects, and nothing drawn but the four uniforms of a
+// reset.  The numpy twin is tests/circle_twin.py.
+// ------------------------------------------------------------------------------------------------
+#define OSA_CIRCLE_KEY 0xE7037ED1A0B428DBull
+#define OSA_CIRCLE_STATE 8  // floats per state row
+#define OSA_CIRCLE_OBS 28   // observation columns
+
+// The fresh state of a reset: p = 0.4 (u0, u1) (inside every wall), heading (u2, u3) normalised, the rest 0; u0 .. u3
+// reset uniforms 0 .. 3 (Philox block 1).
+__device__ __forceinline__ void osa_circle_fresh(unsigned long long key, unsigned long long pos, int n,
+                                                 float (&d)[OSA_NAV_DYN]) {
+  float u[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) u[i] = osa_nav_uniform(key, pos, n, 1, i);
+  d[0] = 0.4f * u[0];
+  d[1] = 0.4f * u[1];
+  const float xx = u[2] * u[2], yy = u[3] * u[3];
+  const float nrm = sqrtf(xx + yy);
+  d[2] = nrm > 0.f ? u[2] / nrm : 1.f;
+  d[3] = nrm > 0.f ? u[3] / nrm : 0.f;
+  d[4] = d[5] = d[6] = d[7] = d[8] = d[9] = 0.f;
+}
+
+// One transition under the (unclamped) env action (a0, a1).  Reward: the tangential part of the attempted
+// displacement m at the new position q, counter-clockwise positive, (m x q) / |q|, damped by 1 + ||q| - 1|.
+__device__ __forceinline__ void osa_circle_transition(float (&d)[OSA_NAV_DYN], int level, float a0_in, float a1_in,
+                                                      float& r, float& c) {
+  float mx, my;
+  osa_nav_move(d, a0_in, a1_in, mx, my);
+  const float qx = d[0], qy = d[1];
+  const float a = my * qx, b = mx * qy;
+  const float num = a - b;
+  const float xx = qx * qx, yy = qy * qy;
+  const float rad = sqrtf(xx + yy);
+  const float dev = fabsf(rad - 1.f);
+  r = rad > 0.f ? (num / rad) / (1.f + dev) : 0.f;
+  const bool out = (level >= 1 && fabsf(qx) > 0.75f) || (level == 2 && fabsf(qy) > 0.75f);
+  c = out ? 1.f : 0.f;
+}
+
+// Column `col` of the observation row: 0 - 11 osa_nav_sensor_col, 12 - 27 the lidar of the origin (bin k reads
+// max(0, 1 - |p| / 3) when the origin lies in sector k; at p = (0, 0) no bin does), 0 past them.
+__device__ __forceinline__ float osa_circle_obs_col(const float (&d)[OSA_NAV_DYN], int col) {
+  if (col < 12 || col >= OSA_CIRCLE_OBS) return osa_nav_sensor_col(d, col);
+  float bx, by, dist;
+  osa_nav_see(d, 0.f, 0.f, bx, by, dist);
+  return osa_nav_in_bin(col - 12, bx, by) ? osa_nav_reading(dist) : 0.f;
 }
 #pragma clang fp contract(fast)

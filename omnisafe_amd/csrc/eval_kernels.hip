@@ -29,7 +29,7 @@ struct OsaEvalArgs {
   int* ep_len;
   float* trace;
   int rec;  // floats per trace record
-  int level;  // SynthNavGoal level (env kinds OSA_EVAL_ENV_NAV0 + level)
+  int level;  // SynthNavGoal / SynthNavCircle level (env kinds OSA_EVAL_ENV_NAV0 + level, OSA_EVAL_ENV_CIRCLE0 + level)
 };
 
 #define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
@@ -70,6 +70,12 @@ __device__ __forceinline__ void osa_eval_obs_nav(const OsaEvalArgs& a, bool norm
   for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_nav_obs_col(d, srow, a.level, c), c);
 }
 
+// SynthNavCircle: from the row's state in registers (d: the eight state floats and the pinned centre).
+__device__ __forceinline__ void osa_eval_obs_circle(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
+                                                    const float (&d)[OSA_NAV_DYN]) {
+  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_circle_obs_col(d, c), c);
+}
+
 template <int HT, int OT, int ENV>
 __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
   extern __shared__ f32x4 osa_eval_lds[];
@@ -99,6 +105,9 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
     __syncthreads();  // the row's hazards are in LDS (osa_nav_fresh places the goal away from them)
     osa_nav_fresh(a.seed ^ OSA_NAV_KEY, 0, k, a.level, srow, d);
     if (valid) osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
+  } else if (ENV == OSA_EVAL_ENV_CIRCLE0) {  // the whole state in registers, no LDS row
+    osa_circle_fresh(a.seed ^ OSA_CIRCLE_KEY, 0, k, d);
+    if (valid) osa_eval_obs_circle(a, norm_on, xrow, g, d);
   } else if (valid) {
     osa_eval_obs<ENV>(a, norm_on, xrow, g, k, 0, s);
   }
@@ -135,6 +144,12 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
       if (rec)
         for (int q = g; q < OSA_NAV_STATE; q += 4) rec[in_w + nd.act_dim + 3 + q] = osa_nav_state_col(d, srow, q);
       osa_nav_transition(d, srow, a.level, arow[0], arow[1], a.seed ^ OSA_NAV_KEY, pos, k, rw, cs);
+    } else if (ENV == OSA_EVAL_ENV_CIRCLE0) {
+      if (rec && g == 0) {
+#pragma unroll
+        for (int q = 0; q < OSA_CIRCLE_STATE; ++q) rec[in_w + nd.act_dim + 3 + q] = d[q];
+      }
+      osa_circle_transition(d, a.level, arow[0], arow[1], rw, cs);
     } else if (ENV == OSA_EVAL_ENV_REACH) {
       if (rec && g == 0)
         for (int q = 0; q < 6; ++q) rec[in_w + nd.act_dim + 3 + q] = s[q];
@@ -171,6 +186,8 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
       } else {
         if (ENV == OSA_EVAL_ENV_NAV0)
           osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
+        else if (ENV == OSA_EVAL_ENV_CIRCLE0)
+          osa_eval_obs_circle(a, norm_on, xrow, g, d);
         else
           osa_eval_obs<ENV>(a, norm_on, xrow, g, k, pos, s);
         if (a.saute && g == 0) xrow[a.obs_dim] = z;
@@ -199,9 +216,11 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   OSA_REQUIRE((norm_mean == nullptr) == (norm_std == nullptr) && (norm_mean == nullptr) == (norm_count == nullptr));
   OSA_REQUIRE(!saute || (saute_budget != 0.f && saute_gamma != 0.f));
   const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
-  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH && !nav) return OSA_EUNSUPPORTED;
+  const bool circle = env_kind >= OSA_EVAL_ENV_CIRCLE0 && env_kind <= OSA_EVAL_ENV_CIRCLE0 + 2;
+  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH && !nav && !circle) return OSA_EUNSUPPORTED;
   if (env_kind == OSA_EVAL_ENV_REACH) OSA_REQUIRE(obs_dim >= 6 && act_dim >= 2);
   if (nav) OSA_REQUIRE(obs_dim >= OSA_NAV_OBS && act_dim >= 2);
+  if (circle) OSA_REQUIRE(obs_dim >= OSA_CIRCLE_OBS && act_dim >= 2);
   const int in_w = obs_dim + (saute ? 1 : 0);
   const int rc = osa_check_dims(in_w, act_dim, hidden);
   if (rc != OSA_OK) return rc;
@@ -218,12 +237,15 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   a.early_terminated = early_terminated ? 1 : 0; a.cost_limit = cost_limit; a.cost_criteria = cost_criteria;
   a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len; a.trace = trace;
   a.rec = osa_eval_trace_floats(env_kind, obs_dim, act_dim, saute);
-  a.level = nav ? env_kind - OSA_EVAL_ENV_NAV0 : 0;
+  a.level = nav ? env_kind - OSA_EVAL_ENV_NAV0 : (circle ? env_kind - OSA_EVAL_ENV_CIRCLE0 : 0);
   const dim3 grid((unsigned)((K + 15) / 16));
 #define OSA_CALL(HT, OT, NSB)                                                                                   \
   do {                                                                                                          \
     if (nav)                                                                                                    \
       hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_NAV0>), grid, dim3(64), lds,            \
+                         osa_stream(stream), a);                                                                \
+    else if (circle)                                                                                            \
+      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CIRCLE0>), grid, dim3(64), lds,         \
                          osa_stream(stream), a);                                                                \
     else if (env_kind == OSA_EVAL_ENV_REACH)                                                                    \
       hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_REACH>), grid, dim3(64), lds,           \
@@ -240,7 +262,9 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
 
 int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute) {
   if (obs_dim < 1 || act_dim < 1) return 0;
-  const int state = env_kind == OSA_EVAL_ENV_REACH ? 6 : (env_kind >= OSA_EVAL_ENV_NAV0 ? OSA_NAV_STATE : 0);
+  const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
+  const bool circle = env_kind >= OSA_EVAL_ENV_CIRCLE0 && env_kind <= OSA_EVAL_ENV_CIRCLE0 + 2;
+  const int state = env_kind == OSA_EVAL_ENV_REACH ? 6 : (nav ? OSA_NAV_STATE : (circle ? OSA_CIRCLE_STATE : 0));
   return obs_dim + (saute ? 1 : 0) + act_dim + 3 + state;
 }
 

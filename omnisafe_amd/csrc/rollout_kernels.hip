@@ -475,6 +475,60 @@ __global__ __launch_bounds__(64) void osa_nav_env_kernel(
     }
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// "SynthNavCircle{0,1,2}" (env_device.h): state[n][8], 28 observation columns, no objects.  The env is too small for a
+// wave: HALF a wave per env, two envs per 64-lane workgroup.  Lane l of a half computes the whole (tiny) transition
+// from the 32-byte state row and writes column l of the observation row (one 112-byte row store per half); columns
+// past 31 of a wider row are zeros in the same strided loop.  Lane 0 of a half writes the state, reward, cost, flags
+// and the step counter.  No LDS, no barrier, no cross-lane operation: the half-wave of a missing last env (odd N)
+// leaves at once.  (OSA_CIRCLE_LANES = 64 builds the one-wave-per-env mapping of the sibling kernels for comparison:
+// tools/circle_env_timing.py.)
+// ------------------------------------------------------------------------------------------------
+#ifndef OSA_CIRCLE_LANES
+#define OSA_CIRCLE_LANES 32  // lanes per env
+#endif
+#define OSA_CIRCLE_PER_WG (64 / OSA_CIRCLE_LANES)  // envs per workgroup
+__global__ __launch_bounds__(64) void osa_circle_env_kernel(
+    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
+    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
+    const float* __restrict__ action, int ld_a,
+    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
+    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
+    int ld_f, int reset_only) {
+  if (step_base) step += *step_base;
+  const int n = OSA_CIRCLE_PER_WG * blockIdx.x + threadIdx.x / OSA_CIRCLE_LANES, lane = threadIdx.x % OSA_CIRCLE_LANES;
+  if (n >= N) return;
+  const unsigned long long key = seed ^ OSA_CIRCLE_KEY;
+  float* __restrict__ srow = state + (long)n * OSA_CIRCLE_STATE;
+  float d[OSA_NAV_DYN];
+#pragma unroll
+  for (int k = 0; k < OSA_CIRCLE_STATE; ++k) d[k] = srow[k];
+  d[8] = d[9] = 0.f;  // the lidar's object: the circle's centre
+  uint8_t trunc = 0;
+  float r = 0.f, c = 0.f;
+  if (!reset_only) {
+    osa_circle_transition(d, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], r, c);
+    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
+    if (trunc && final_obs)
+      for (int k = lane; k < D; k += OSA_CIRCLE_LANES) final_obs[(long)n * ld_f + k] = osa_circle_obs_col(d, k);
+  }
+  if (reset_only || trunc) osa_circle_fresh(key, step, n, d);
+  for (int k = lane; k < D; k += OSA_CIRCLE_LANES) obs[(long)n * ld + k] = osa_circle_obs_col(d, k);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < OSA_CIRCLE_STATE; ++k) srow[k] = d[k];
+    if (reset_only) {
+      steps[n] = 0;
+    } else {
+      reward[n] = r;
+      cost[n] = c;
+      terminated[n] = 0;
+      truncated[n] = trunc;
+      steps[n] = trunc ? 0 : steps[n] + 1;
+    }
+  }
+}
 #pragma clang fp contract(fast)
 
 // ------------------------------------------------------------------------------------------------
@@ -768,6 +822,23 @@ int osa_nav_env_step(unsigned long long seed, unsigned long long step,
   hipLaunchKernelGGL(osa_nav_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
                      obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs, reward, cost,
                      terminated, truncated, final_obs, ld_final, reset_only);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+int osa_circle_env_step(unsigned long long seed, unsigned long long step,
+                        const unsigned long long* step_base, int N, int obs_dim,
+                        int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                        float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                        uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                        void* stream) {
+  OSA_REQUIRE(N > 0 && obs_dim >= OSA_CIRCLE_OBS && state && steps && obs && ld_obs >= obs_dim);
+  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
+  if (!reset_only)
+    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  hipLaunchKernelGGL(osa_circle_env_kernel, dim3((N + OSA_CIRCLE_PER_WG - 1) / OSA_CIRCLE_PER_WG), dim3(64), 0,
+                     osa_stream(stream), seed, step, step_base, N, obs_dim, horizon, level, state, steps, action,
+                     ld_action, obs, ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only);
   OSA_CHECK_LAUNCH();
   return OSA_OK;
 }

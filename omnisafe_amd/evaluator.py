@@ -5,8 +5,9 @@
 ``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does.
 
 Two paths, one semantics:
-  persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, Synth*-v0): every episode in ONE
-              launch of osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a fresh env.
+  persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, SynthNavCircle*-v0, Synth*-v0):
+              every episode in ONE launch of osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a
+              fresh env.
   per-step    everything else (general networks, host envs, an env object given as ``env=``): the existing launches
               per vector step -- Normalizer.apply, ConstraintActorCritic.step(deterministic=True, nets_mask=1) with
               ActionScale fused, env.step -- and the same float64 sums in the same order.
@@ -36,13 +37,16 @@ from .normalizer import Normalizer
 from .spaces import Box
 
 TIME_LIMIT = 1000  # evaluator.py:179-180
-DEVICE_ENVS = (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv, envs_mod.NavGoalVectorEnv)
+DEVICE_ENVS = (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv, envs_mod.NavGoalVectorEnv,
+               envs_mod.NavCircleVectorEnv)
 
 
 def _env_kind(env) -> int:
-    """env_kind of osa_eval_episodes: OSA_EVAL_ENV_SYNTH / _REACH / _NAV0 + level."""
+    """env_kind of osa_eval_episodes: OSA_EVAL_ENV_SYNTH / _REACH / _NAV0 + level / _CIRCLE0 + level."""
     if isinstance(env, envs_mod.NavGoalVectorEnv):
         return 16 + env.level
+    if isinstance(env, envs_mod.NavCircleVectorEnv):
+        return 32 + env.level
     return 1 if isinstance(env, envs_mod.ReachVectorEnv) else 0
 
 
@@ -91,6 +95,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             return (int(self._user_env.observation_space.shape[0]), int(self._user_env.action_space.shape[0]))
         if self._env_id == 'SynthReach-v0' or self._env_id in envs_mod.NAV_LEVELS:
             return 60, 2
+        if self._env_id in envs_mod.CIRCLE_LEVELS:
+            return 28, 2
         if self._env_id in envs_mod.SYNTH_DIMS:
             return envs_mod.SYNTH_DIMS[self._env_id]
         env = envs_mod.make(self._env_id, num_envs=1, device=self._device, **self._env_cfgs)
@@ -202,7 +208,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS
         max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
         state_w = 6 if isinstance(env, envs_mod.ReachVectorEnv) else (
-            64 if isinstance(env, envs_mod.NavGoalVectorEnv) else 0)  # state floats of a trace record
+            64 if isinstance(env, envs_mod.NavGoalVectorEnv) else (
+                8 if isinstance(env, envs_mod.NavCircleVectorEnv) else 0))  # state floats of a trace record
         f64 = dict(dtype=torch.float64, device=dev)
         ret, cost = torch.zeros(K, **f64), torch.zeros(K, **f64)
         length = torch.zeros(K, dtype=torch.int32, device=dev)

@@ -95,6 +95,10 @@ def install(algorithms: tuple[str, ...] | None = None) -> list[str]:
     if nav_ids:
         reg._class['OmnisafeAmdNavGoalVectorEnv'] = amd_envs.NavGoalVectorEnv  # noqa: SLF001
         reg._support_envs['OmnisafeAmdNavGoalVectorEnv'] = nav_ids  # noqa: SLF001
+    circle_ids = [e for e in amd_envs.NavCircleVectorEnv._support_envs if e not in known]  # noqa: SLF001
+    if circle_ids:
+        reg._class['OmnisafeAmdNavCircleVectorEnv'] = amd_envs.NavCircleVectorEnv  # noqa: SLF001
+        reg._support_envs['OmnisafeAmdNavCircleVectorEnv'] = circle_ids  # noqa: SLF001
     del omnisafe
     return swapped
 

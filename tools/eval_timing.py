@@ -3,8 +3,8 @@ initialised PPOLag checkpoint with an active observation normaliser.
 
     python tools/eval_timing.py [--ks 16,1024,16384] [--reps 3]
 
-Cases: SynthReach-v0, SynthPointGoal1-v0, SynthHumanoid-v0 and SynthNavGoal1-v0, all at horizon 1000 (--cases picks
-some by id).  One warm-up call per
+Cases: SynthReach-v0, SynthPointGoal1-v0, SynthHumanoid-v0, SynthNavGoal1-v0 and SynthNavCircle1-v0, all at horizon
+1000 (--cases picks some by id).  One warm-up call per
 (case, K, path), then the median of --reps timed calls (host clock around evaluate() + device synchronisation).
 Prints one JSON line."""
 from __future__ import annotations
@@ -31,7 +31,8 @@ from omnisafe_amd.spaces import Box  # noqa: E402
 
 DEV = 'cuda:0'
 CASES = [('SynthReach-v0', {'horizon': 1000}), ('SynthPointGoal1-v0', {'horizon': 1000}),
-         ('SynthHumanoid-v0', {'horizon': 1000}), ('SynthNavGoal1-v0', {'horizon': 1000})]
+         ('SynthHumanoid-v0', {'horizon': 1000}), ('SynthNavGoal1-v0', {'horizon': 1000}),
+         ('SynthNavCircle1-v0', {'horizon': 1000})]
 
 
 def checkpoint(root: str, env_id: str, env_cfgs: dict) -> str:
@@ -40,7 +41,8 @@ def checkpoint(root: str, env_id: str, env_cfgs: dict) -> str:
     os.makedirs(os.path.join(root, 'torch_save'), exist_ok=True)
     with open(os.path.join(root, 'config.json'), 'w', encoding='utf-8') as f:
         json.dump(d, f)
-    obs_dim, act_dim = dict(SYNTH_DIMS, **{'SynthReach-v0': (60, 2), 'SynthNavGoal1-v0': (60, 2)})[env_id]
+    obs_dim, act_dim = dict(SYNTH_DIMS, **{'SynthReach-v0': (60, 2), 'SynthNavGoal1-v0': (60, 2),
+                                           'SynthNavCircle1-v0': (28, 2)})[env_id]
     torch.manual_seed(0)
     ac = ConstraintActorCritic(Box(-np.inf, np.inf, (obs_dim,)), Box(-1.0, 1.0, (act_dim,)),
                                Config.dict2config(d).model_cfgs, epochs=1, device=DEV)
