@@ -794,6 +794,40 @@ int osa_circle_env_step(unsigned long long seed, unsigned long long step,
                         uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                         void* stream);
 
+/* The Car on the two tasks above: "SynthNavCarGoal{0,1,2}-v0" (obs_dim >= 72, 2 actions; stand-in for the
+ * Safety-Gymnasium CarGoal tasks behind omnisafe/envs/safety_gymnasium_env.py:160-210 step / reset -- SafetyCarGoal1-v0
+ * is the env of BASELINE config 3 -- whose MuJoCo physics is third-party CPU code outside the reference repo; a
+ * specification of this package, not a port).  The Car has two independently driven wheels: under
+ * a = clip(action,-1,1), a0 the left and a1 the right wheel, w_l <- 0.9 w_l + 0.02 a0, w_r <- 0.9 w_r + 0.02 a1,
+ * f <- 0.5 (w_l + w_r), t <- 0.375 (w_r - w_l); then osa_nav_env_step's motion with that f and t (u turned by the
+ * rational rotation of parameter t and renormalised, p <- clip(p + f u, -2, 2)) and its reward, goal resampling,
+ * hazards, vases, costs and levels.  state: N x 64 floats owned by the caller, updated in place: osa_nav_env_step's row
+ * with three of its zero slots in use, [7] t_prev, [10] w_l, [11] w_r.  A reset is osa_nav_env_step's, under the SAME
+ * Philox key and draw allocation (the arena of seed s equals SynthNavGoal's of seed s, so that robots can be compared
+ * on identical layouts), with w_l = w_r = t_prev = 0.  obs row = [f, f - f_prev, t, u, w_l, w_r, t - t_prev, 0 (16),
+ * goal lidar (16), hazard lidar (16), vase lidar (16), 0...].  float32 without fused multiply-adds: a numpy twin
+ * reproduces every bit.  Launch: one wave per env; lanes 0 - 7 also write columns 64 - 71. */
+int osa_car_goal_env_step(unsigned long long seed, unsigned long long step,
+                          const unsigned long long* step_base, int N, int obs_dim,
+                          int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                          float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                          uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                          void* stream);
+
+/* "SynthNavCarCircle{0,1,2}-v0" (obs_dim >= 40, 2 actions; stand-in for the Safety-Gymnasium CarCircle tasks behind
+ * omnisafe/envs/safety_gymnasium_env.py:160-210 step / reset; a specification of this package, not a port): the Car of
+ * osa_car_goal_env_step with the reward, corridor cost and levels of osa_circle_env_step.  state: N x 12 floats owned
+ * by the caller, updated in place: p(2) u(2) f f_prev t t_prev 0 0 w_l w_r (the first twelve of osa_car_goal_env_step's
+ * row).  A reset is osa_circle_env_step's under the same Philox key, with w_l = w_r = t_prev = 0.  obs row = [f,
+ * f - f_prev, t, u, w_l, w_r, t - t_prev, 0 (16), lidar of the origin (16), 0...].  Launch: half a wave per env (two
+ * envs per 64-lane workgroup), the 40 columns in two rounds of the half-wave. */
+int osa_car_circle_env_step(unsigned long long seed, unsigned long long step,
+                            const unsigned long long* step_base, int N, int obs_dim,
+                            int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                            float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                            uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                            void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Trust-region machinery (NaturalPG / TRPO / TRPOLag / CPO actor update)
  *
@@ -869,15 +903,20 @@ int osa_shuffle_rows(const long long* row_seeds, int rows, long M, long long* pe
  * env_kind: OSA_EVAL_ENV_SYNTH (osa_synth_env_step; cost_p used), OSA_EVAL_ENV_REACH (osa_reach_env_step: obs_dim
  * >= 6, act_dim >= 2), OSA_EVAL_ENV_NAV0 + level (osa_nav_env_step: obs_dim >= 60, act_dim >= 2, policy input <= 928
  * columns) or OSA_EVAL_ENV_CIRCLE0 + level (osa_circle_env_step: obs_dim >= 28, act_dim >= 2; the state stays in
+ * registers), OSA_EVAL_ENV_CARGOAL0 + level (osa_car_goal_env_step: obs_dim >= 72, act_dim >= 2, policy input <= 928
+ * columns) or OSA_EVAL_ENV_CARCIRCLE0 + level (osa_car_circle_env_step: obs_dim >= 40, act_dim >= 2; the state stays in
  * registers); anything else OSA_EUNSUPPORTED.  Outputs: ep_ret, ep_cost double[K], ep_len int32[K].
  * trace (NULL in production): float[max_steps][K][osa_eval_trace_floats(...)], zero-initialised by the caller; the
  * record of (step, episode) is written while the episode plays: policy input row, env action, reward, cost, 1.0
  * (alive), and the state before the step (SynthReach: 6 floats, SynthNavGoal: the 64-float row,
- * SynthNavCircle: the 8-float row).  Arguments are checked before any launch. */
+ * SynthNavCircle: the 8-float row, SynthNavCarGoal: the 64-float row, SynthNavCarCircle: the 12-float row).  Arguments
+ * are checked before any launch. */
 #define OSA_EVAL_ENV_SYNTH 0
 #define OSA_EVAL_ENV_REACH 1
 #define OSA_EVAL_ENV_NAV0 16 /* + level 0 .. 2 */
 #define OSA_EVAL_ENV_CIRCLE0 32 /* + level 0 .. 2 */
+#define OSA_EVAL_ENV_CARGOAL0 48 /* + level 0 .. 2 */
+#define OSA_EVAL_ENV_CARCIRCLE0 64 /* + level 0 .. 2 */
 int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden, const float* params,
                       const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
                       const float* old_min, const float* old_max, float min_action, float max_action,

@@ -131,6 +131,10 @@ SIGNATURES: dict[str, tuple] = {
     'osa_reach_env_step': (_I, [_U, _U, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     'osa_nav_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     'osa_circle_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'osa_car_goal_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I,
+                                   _P]),
+    'osa_car_circle_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I,
+                                     _P]),
     'osa_eval_episodes': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _F, _F, _U, _I, _F, _I, _I, _F, _F,
                                _I, _D, _D, _P, _P, _P, _P, _P]),
     'osa_eval_trace_floats': (_I, [_I, _I, _I, _I]),

@@ -19,6 +19,8 @@ reference's (step, env) order, so the window-100 statistics and the Lagrange upd
 """
 from __future__ import annotations
 
+import gc
+
 import torch
 
 from . import _lib
@@ -203,8 +205,19 @@ class OnPolicyAdapter:  # pylint: disable=too-many-instance-attributes
         elif st['graph'] is None and not st['failed']:
             try:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):  # records the launches without executing them
-                    self._rollout_device(T, agent, buffer)
+                # A dead reference cycle that owns a captured graph (an earlier Agent of the process) must not be
+                # finalised by the cyclic collector in the middle of this capture: destroying a graph synchronises
+                # the current stream, which a capturing stream refuses, and an error in a destructor ends the
+                # process.  Collect before the capture and keep the collector off while it lasts.
+                gc_was_enabled = gc.isenabled()
+                gc.collect()
+                gc.disable()
+                try:
+                    with torch.cuda.graph(g):  # records the launches without executing them
+                        self._rollout_device(T, agent, buffer)
+                finally:
+                    if gc_was_enabled:
+                        gc.enable()
                 st['graph'] = g
                 buffer.ptr = 0
                 g.replay()

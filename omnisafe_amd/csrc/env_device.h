@@ -1,6 +1,6 @@
 // Per-env transitions of the device-resident vector envs, shared by their per-step kernels
-// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_nav_env_kernel, osa_circle_env_kernel) and the
-// persistent evaluation kernel (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream
+// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_nav_env_kernel, osa_circle_env_kernel,
+// osa_car_goal_env_kernel, osa_car_circle_env_kernel) and the persistent evaluation kernel (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream
 // position `step`, env index n), so a caller that replays env n at positions 0, 1, 2, ... sees the same episode as the
 // per-step launches.
 #pragma once
@@ -195,15 +195,11 @@ __device__ __forceinline__ void osa_nav_fresh(unsigned long long key, unsigned l
   osa_nav_pick_goal(c, row, level, d[8], d[9]);
 }
 
-// The motion of a transition under the (unclamped) env action (a0, a1): f <- 0.9 f + 0.02 a0, the heading turned by the
-// rational rotation of parameter t = 0.15 a1 and renormalised, p <- clip(p + m, -2, 2) with m = f u the attempted
-// displacement.  Shared by SynthNavGoal and SynthNavCircle.
-__device__ __forceinline__ void osa_nav_move(float (&d)[OSA_NAV_DYN], float a0_in, float a1_in, float& mx, float& my) {
-  const float a0 = fminf(fmaxf(a0_in, -1.f), 1.f);
-  const float a1 = fminf(fmaxf(a1_in, -1.f), 1.f);
-  const float fa = 0.9f * d[4], fb = 0.02f * a0;
-  const float f2 = fa + fb;
-  const float t = 0.15f * a1;
+// The motion of a transition from `tt = t * t` on, for a robot that has settled its forward speed f2 and its turn
+// parameter t: the heading turned by the rational rotation of parameter t and renormalised, p <- clip(p + m, -2, 2)
+// with m = f2 u the attempted displacement.  The point robot (osa_nav_move) and the Car (osa_car_move) differ only in how
+// they arrive at (f2, t).
+__device__ __forceinline__ void osa_nav_turn_and_go(float (&d)[OSA_NAV_DYN], float f2, float t, float& mx, float& my) {
   const float tt = t * t;
   const float den = 1.f + tt;
   const float cs = (1.f - tt) / den;
@@ -224,14 +220,43 @@ __device__ __forceinline__ void osa_nav_move(float (&d)[OSA_NAV_DYN], float a0_i
   d[6] = t;
 }
 
-// One transition of env n at position `pos` under the (unclamped) env action (a0, a1), all but its cost (which is a
-// function of the new position: osa_nav_cost, or the caller's own walk over the objects).
-__device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
-                                                float a0_in, float a1_in, unsigned long long key,
-                                                unsigned long long pos, int n, float& r) {
-  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
-  float mx, my;
-  osa_nav_move(d, a0_in, a1_in, mx, my);
+// The motion of a transition under the (unclamped) env action (a0, a1): f <- 0.9 f + 0.02 a0, the heading turned by the
+// rational rotation of parameter t = 0.15 a1 and renormalised, p <- clip(p + m, -2, 2) with m = f u the attempted
+// displacement.  Shared by SynthNavGoal and SynthNavCircle.
+__device__ __forceinline__ void osa_nav_move(float (&d)[OSA_NAV_DYN], float a0_in, float a1_in, float& mx, float& my) {
+  const float a0 = fminf(fmaxf(a0_in, -1.f), 1.f);
+  const float a1 = fminf(fmaxf(a1_in, -1.f), 1.f);
+  const float fa = 0.9f * d[4], fb = 0.02f * a0;
+  const float f2 = fa + fb;
+  const float t = 0.15f * a1;
+  osa_nav_turn_and_go(d, f2, t, mx, my);
+}
+
+// The Car's motion under the (unclamped) env action (a0, a1) = (left wheel, right wheel): each wheel speed lags its
+// command, w <- 0.9 w + 0.02 a; the forward speed is the wheels' mean, f = 0.5 (w_l + w_r), and the turn parameter
+// their difference, t = 0.375 (w_r - w_l); from there on the point robot's motion.  `d` is a SynthNavGoal `d` whose
+// slot 7 holds t_prev, `w` the wheel speeds (w_l, w_r).  Shared by SynthNavCarGoal, SynthNavCarCircle and the
+// evaluation kernel.
+__device__ __forceinline__ void osa_car_move(float (&d)[OSA_NAV_DYN], float (&w)[2], float a0_in, float a1_in,
+                                             float& mx, float& my) {
+  const float a0 = fminf(fmaxf(a0_in, -1.f), 1.f);
+  const float a1 = fminf(fmaxf(a1_in, -1.f), 1.f);
+  const float la = 0.9f * w[0], lb = 0.02f * a0;
+  const float ra = 0.9f * w[1], rb = 0.02f * a1;
+  w[0] = la + lb;
+  w[1] = ra + rb;
+  const float sum = w[0] + w[1], dif = w[1] - w[0];
+  const float f2 = 0.5f * sum;
+  const float t = 0.375f * dif;
+  d[7] = d[6];
+  osa_nav_turn_and_go(d, f2, t, mx, my);
+}
+
+// What a SynthNavGoal transition does after the robot has moved: the reward from the distance to the goal before (d0)
+// and after, and a new goal when the old one is reached.
+__device__ __forceinline__ void osa_nav_arrive(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
+                                               float d0, unsigned long long key, unsigned long long pos, int n,
+                                               float& r) {
   const float d1 = osa_reach_dist(d[0], d[1], d[8], d[9]);
   const bool reached = d1 < 0.3f;
   r = (d0 - d1) + (reached ? 1.f : 0.f);
@@ -241,6 +266,17 @@ __device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const f
     for (int i = 0; i < 8; ++i) cand[i] = osa_nav_uniform(key, pos, n, 14, i);
     osa_nav_pick_goal(cand, row, level, d[8], d[9]);
   }
+}
+
+// One transition of env n at position `pos` under the (unclamped) env action (a0, a1), all but its cost (which is a
+// function of the new position: osa_nav_cost, or the caller's own walk over the objects).
+__device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
+                                                float a0_in, float a1_in, unsigned long long key,
+                                                unsigned long long pos, int n, float& r) {
+  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
+  float mx, my;
+  osa_nav_move(d, a0_in, a1_in, mx, my);
+  osa_nav_arrive(d, row, level, d0, key, pos, n, r);
 }
 
 // An object o seen from the state: body-frame coordinates (bx, by) of r = o - p and |r|.
@@ -350,12 +386,10 @@ __device__ __forceinline__ void osa_circle_fresh(unsigned long long key, unsigne
   d[4] = d[5] = d[6] = d[7] = d[8] = d[9] = 0.f;
 }
 
-// One transition under the (unclamped) env action (a0, a1).  Reward: the tangential part of the attempted
-// displacement m at the new position q, counter-clockwise positive, (m x q) / |q|, damped by 1 + ||q| - 1|.
-__device__ __forceinline__ void osa_circle_transition(float (&d)[OSA_NAV_DYN], int level, float a0_in, float a1_in,
-                                                      float& r, float& c) {
-  float mx, my;
-  osa_nav_move(d, a0_in, a1_in, mx, my);
+// Reward and cost of a transition that attempted the displacement m and led to the state d.  Reward: the tangential
+// part of m at the new position q, counter-clockwise positive, (m x q) / |q|, damped by 1 + ||q| - 1|.
+__device__ __forceinline__ void osa_circle_pay(const float (&d)[OSA_NAV_DYN], int level, float mx, float my, float& r,
+                                               float& c) {
   const float qx = d[0], qy = d[1];
   const float a = my * qx, b = mx * qy;
   const float num = a - b;
@@ -367,6 +401,14 @@ __device__ __forceinline__ void osa_circle_transition(float (&d)[OSA_NAV_DYN], i
   c = out ? 1.f : 0.f;
 }
 
+// One transition under the (unclamped) env action (a0, a1).
+__device__ __forceinline__ void osa_circle_transition(float (&d)[OSA_NAV_DYN], int level, float a0_in, float a1_in,
+                                                      float& r, float& c) {
+  float mx, my;
+  osa_nav_move(d, a0_in, a1_in, mx, my);
+  osa_circle_pay(d, level, mx, my, r, c);
+}
+
 // Column `col` of the observation row: 0 - 11 osa_nav_sensor_col, 12 - 27 the lidar of the origin (bin k reads
 // max(0, 1 - |p| / 3) when the origin lies in sector k; at p = (0, 0) no bin does), 0 past them.
 __device__ __forceinline__ float osa_circle_obs_col(const float (&d)[OSA_NAV_DYN], int col) {
@@ -374,5 +416,75 @@ __device__ __forceinline__ float osa_circle_obs_col(const float (&d)[OSA_NAV_DYN
   float bx, by, dist;
   osa_nav_see(d, 0.f, 0.f, bx, by, dist);
   return osa_nav_in_bin(col - 12, bx, by) ? osa_nav_reading(dist) : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------
+// SynthNavCarGoal{0,1,2}-v0 and SynthNavCarCircle{0,1,2}-v0: the two tasks above driven by the Car, whose two wheels
+// are commanded independently (osa_car_move); everything but the motion and the sensor columns is the point task's.
+// State row of a CarGoal env, 64 floats: SynthNavGoal's row with three of its zero slots in use,
+//   [7] t_prev  [10] w_l  [11] w_r
+// and of a CarCircle env, 12 floats: the first twelve of that row (the goal slots [8:10] stay 0: the circle's centre).
+// The callers keep a SynthNavGoal `d` (d[7] = t_prev) and the wheel speeds `w`.
+// A reset takes the POINT task's Philox key and draw allocation (OSA_NAV_KEY / OSA_CIRCLE_KEY, osa_nav_fresh /
+// osa_circle_fresh) and starts the wheels and t_prev at 0: on purpose, so that SynthNavCarGoal<l> with seed s has the
+// arena of SynthNavGoal<l> with seed s (robots compared on identical layouts, one reset in the numpy twins).
+// Observation: 24 sensor columns (osa_car_sensor_col), then the task's lidars.  The numpy twin is tests/car_twin.py.
+// ------------------------------------------------------------------------------------------------
+#define OSA_CAR_SENSORS 24       // sensor columns of the Car
+#define OSA_CAR_GOAL_OBS 72      // observation columns of SynthNavCarGoal
+#define OSA_CAR_CIRCLE_OBS 40    // observation columns of SynthNavCarCircle
+#define OSA_CAR_CIRCLE_STATE 12  // floats per state row of SynthNavCarCircle
+#define OSA_CAR_WHEELS 10        // column of w_l in either state row
+
+// Sensor columns: 0 f, 1 f - f_prev, 2 t, 3 u_x, 4 u_y, 5 w_l, 6 w_r, 7 t - t_prev, 0 past them.
+__device__ __forceinline__ float osa_car_sensor_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2], int col) {
+  float v = osa_nav_sensor_col(d, col);
+  if (col == 5) v = w[0];
+  if (col == 6) v = w[1];
+  if (col == 7) v = d[6] - d[7];
+  return v;
+}
+
+// One SynthNavCarGoal transition of env n at position `pos`, all but its cost (as osa_nav_advance).
+__device__ __forceinline__ void osa_car_goal_advance(float (&d)[OSA_NAV_DYN], float (&w)[2],
+                                                     const float* __restrict__ row, int level, float a0_in,
+                                                     float a1_in, unsigned long long key, unsigned long long pos,
+                                                     int n, float& r) {
+  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
+  float mx, my;
+  osa_car_move(d, w, a0_in, a1_in, mx, my);
+  osa_nav_arrive(d, row, level, d0, key, pos, n, r);
+}
+
+// One SynthNavCarCircle transition.
+__device__ __forceinline__ void osa_car_circle_transition(float (&d)[OSA_NAV_DYN], float (&w)[2], int level,
+                                                          float a0_in, float a1_in, float& r, float& c) {
+  float mx, my;
+  osa_car_move(d, w, a0_in, a1_in, mx, my);
+  osa_circle_pay(d, level, mx, my, r, c);
+}
+
+// Column `col` of the SynthNavCarGoal observation row, one lane for the whole row (eval_kernels.hip): 0 - 23
+// osa_car_sensor_col, 24 - 71 the three lidars (columns 12 - 59 of osa_nav_obs_col), 0 past them.
+__device__ __forceinline__ float osa_car_goal_obs_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
+                                                      const float* __restrict__ row, int level, int col) {
+  if (col < OSA_CAR_SENSORS || col >= OSA_CAR_GOAL_OBS) return osa_car_sensor_col(d, w, col);
+  return osa_nav_obs_col(d, row, level, col - (OSA_CAR_SENSORS - 12));
+}
+
+// Column `col` of the SynthNavCarCircle observation row: 0 - 23 osa_car_sensor_col, 24 - 39 the lidar of the origin
+// (osa_circle_obs_col's), 0 past them.
+__device__ __forceinline__ float osa_car_circle_obs_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2], int col) {
+  if (col < OSA_CAR_SENSORS || col >= OSA_CAR_CIRCLE_OBS) return osa_car_sensor_col(d, w, col);
+  return osa_circle_obs_col(d, col - (OSA_CAR_SENSORS - 12));
+}
+
+// Column `col` of the current SynthNavCarGoal state row (`row`: the objects, as osa_nav_state_col).
+__device__ __forceinline__ float osa_car_state_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
+                                                   const float* __restrict__ row, int col) {
+  float v = osa_nav_state_col(d, row, col);
+  if (col == OSA_CAR_WHEELS) v = w[0];
+  if (col == OSA_CAR_WHEELS + 1) v = w[1];
+  return v;
 }
 #pragma clang fp contract(fast)

@@ -29,7 +29,7 @@ struct OsaEvalArgs {
   int* ep_len;
   float* trace;
   int rec;  // floats per trace record
-  int level;  // SynthNavGoal / SynthNavCircle level (env kinds OSA_EVAL_ENV_NAV0 + level, OSA_EVAL_ENV_CIRCLE0 + level)
+  int level;  // level of a SynthNav* env (env kinds OSA_EVAL_ENV_NAV0 / _CIRCLE0 / _CARGOAL0 / _CARCIRCLE0 + level)
 };
 
 #define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
@@ -76,6 +76,20 @@ __device__ __forceinline__ void osa_eval_obs_circle(const OsaEvalArgs& a, bool n
   for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_circle_obs_col(d, c), c);
 }
 
+// SynthNavCarGoal: as osa_eval_obs_nav, with the wheel speeds w.
+__device__ __forceinline__ void osa_eval_obs_car_goal(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow,
+                                                      int g, const float (&d)[OSA_NAV_DYN], const float (&w)[2],
+                                                      const float* __restrict__ srow) {
+  for (int c = g; c < a.obs_dim; c += 4)
+    xrow[c] = osa_eval_norm(a, norm_on, osa_car_goal_obs_col(d, w, srow, a.level, c), c);
+}
+
+// SynthNavCarCircle: as osa_eval_obs_circle, with the wheel speeds w.
+__device__ __forceinline__ void osa_eval_obs_car_circle(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow,
+                                                        int g, const float (&d)[OSA_NAV_DYN], const float (&w)[2]) {
+  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_car_circle_obs_col(d, w, c), c);
+}
+
 template <int HT, int OT, int ENV>
 __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
   extern __shared__ f32x4 osa_eval_lds[];
@@ -95,19 +109,31 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
     osa_philox(a.seed ^ OSA_REACH_KEY, 0, ((unsigned long long)k << 20) + 2, w1);
     osa_reach_fresh(w0, w1, s);
   }
-  // SynthNavGoal: the state row of episode k in LDS behind the action rows, its first ten floats in registers
+  // SynthNavGoal, SynthNavCarGoal: the state row of episode k in LDS behind the action rows, its first ten floats (and
+  // the Car's wheel speeds cw) in registers
   float* __restrict__ srow =
       reinterpret_cast<float*>(osa_eval_lds) + 16 * (INP + OSA_EVAL_ACT_LD) + j * OSA_NAV_STATE;
   float d[OSA_NAV_DYN] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (ENV == OSA_EVAL_ENV_NAV0) {
+  float cw[2] = {0.f, 0.f};  // a reset leaves the Car's wheels at rest
+  if (ENV == OSA_EVAL_ENV_NAV0 || ENV == OSA_EVAL_ENV_CARGOAL0) {
     for (int c = OSA_NAV_DYN + g; c < OSA_NAV_STATE; c += 4)
       srow[c] = valid ? osa_nav_fresh_obj(a.seed ^ OSA_NAV_KEY, 0, k, a.level, c) : 0.f;
     __syncthreads();  // the row's hazards are in LDS (osa_nav_fresh places the goal away from them)
     osa_nav_fresh(a.seed ^ OSA_NAV_KEY, 0, k, a.level, srow, d);
-    if (valid) osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
-  } else if (ENV == OSA_EVAL_ENV_CIRCLE0) {  // the whole state in registers, no LDS row
+    if (valid) {
+      if (ENV == OSA_EVAL_ENV_NAV0)
+        osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
+      else
+        osa_eval_obs_car_goal(a, norm_on, xrow, g, d, cw, srow);
+    }
+  } else if (ENV == OSA_EVAL_ENV_CIRCLE0 || ENV == OSA_EVAL_ENV_CARCIRCLE0) {  // the whole state in registers
     osa_circle_fresh(a.seed ^ OSA_CIRCLE_KEY, 0, k, d);
-    if (valid) osa_eval_obs_circle(a, norm_on, xrow, g, d);
+    if (valid) {
+      if (ENV == OSA_EVAL_ENV_CIRCLE0)
+        osa_eval_obs_circle(a, norm_on, xrow, g, d);
+      else
+        osa_eval_obs_car_circle(a, norm_on, xrow, g, d, cw);
+    }
   } else if (valid) {
     osa_eval_obs<ENV>(a, norm_on, xrow, g, k, 0, s);
   }
@@ -150,6 +176,20 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
         for (int q = 0; q < OSA_CIRCLE_STATE; ++q) rec[in_w + nd.act_dim + 3 + q] = d[q];
       }
       osa_circle_transition(d, a.level, arow[0], arow[1], rw, cs);
+    } else if (ENV == OSA_EVAL_ENV_CARGOAL0) {
+      if (rec)
+        for (int q = g; q < OSA_NAV_STATE; q += 4)
+          rec[in_w + nd.act_dim + 3 + q] = osa_car_state_col(d, cw, srow, q);
+      osa_car_goal_advance(d, cw, srow, a.level, arow[0], arow[1], a.seed ^ OSA_NAV_KEY, pos, k, rw);
+      cs = osa_nav_cost(d, srow, a.level);
+    } else if (ENV == OSA_EVAL_ENV_CARCIRCLE0) {
+      if (rec && g == 0) {
+#pragma unroll
+        for (int q = 0; q < OSA_NAV_DYN; ++q) rec[in_w + nd.act_dim + 3 + q] = d[q];
+        rec[in_w + nd.act_dim + 3 + OSA_CAR_WHEELS] = cw[0];
+        rec[in_w + nd.act_dim + 3 + OSA_CAR_WHEELS + 1] = cw[1];
+      }
+      osa_car_circle_transition(d, cw, a.level, arow[0], arow[1], rw, cs);
     } else if (ENV == OSA_EVAL_ENV_REACH) {
       if (rec && g == 0)
         for (int q = 0; q < 6; ++q) rec[in_w + nd.act_dim + 3 + q] = s[q];
@@ -188,6 +228,10 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
           osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
         else if (ENV == OSA_EVAL_ENV_CIRCLE0)
           osa_eval_obs_circle(a, norm_on, xrow, g, d);
+        else if (ENV == OSA_EVAL_ENV_CARGOAL0)
+          osa_eval_obs_car_goal(a, norm_on, xrow, g, d, cw, srow);
+        else if (ENV == OSA_EVAL_ENV_CARCIRCLE0)
+          osa_eval_obs_car_circle(a, norm_on, xrow, g, d, cw);
         else
           osa_eval_obs<ENV>(a, norm_on, xrow, g, k, pos, s);
         if (a.saute && g == 0) xrow[a.obs_dim] = z;
@@ -217,17 +261,22 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   OSA_REQUIRE(!saute || (saute_budget != 0.f && saute_gamma != 0.f));
   const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
   const bool circle = env_kind >= OSA_EVAL_ENV_CIRCLE0 && env_kind <= OSA_EVAL_ENV_CIRCLE0 + 2;
-  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH && !nav && !circle) return OSA_EUNSUPPORTED;
+  const bool car_goal = env_kind >= OSA_EVAL_ENV_CARGOAL0 && env_kind <= OSA_EVAL_ENV_CARGOAL0 + 2;
+  const bool car_circle = env_kind >= OSA_EVAL_ENV_CARCIRCLE0 && env_kind <= OSA_EVAL_ENV_CARCIRCLE0 + 2;
+  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH && !nav && !circle && !car_goal && !car_circle)
+    return OSA_EUNSUPPORTED;
   if (env_kind == OSA_EVAL_ENV_REACH) OSA_REQUIRE(obs_dim >= 6 && act_dim >= 2);
   if (nav) OSA_REQUIRE(obs_dim >= OSA_NAV_OBS && act_dim >= 2);
   if (circle) OSA_REQUIRE(obs_dim >= OSA_CIRCLE_OBS && act_dim >= 2);
+  if (car_goal) OSA_REQUIRE(obs_dim >= OSA_CAR_GOAL_OBS && act_dim >= 2);
+  if (car_circle) OSA_REQUIRE(obs_dim >= OSA_CAR_CIRCLE_OBS && act_dim >= 2);
   const int in_w = obs_dim + (saute ? 1 : 0);
   const int rc = osa_check_dims(in_w, act_dim, hidden);
   if (rc != OSA_OK) return rc;
   OsaEvalArgs a;
   a.nd = osa_make_net(in_w, act_dim, hidden);
-  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (nav ? OSA_NAV_STATE : 0)) * sizeof(float);
-  if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns (928 with a SynthNavGoal state)
+  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (nav || car_goal ? OSA_NAV_STATE : 0)) * sizeof(float);
+  if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns (928 with a 64-float state row)
   a.params = params;
   a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
   a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
@@ -238,6 +287,8 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len; a.trace = trace;
   a.rec = osa_eval_trace_floats(env_kind, obs_dim, act_dim, saute);
   a.level = nav ? env_kind - OSA_EVAL_ENV_NAV0 : (circle ? env_kind - OSA_EVAL_ENV_CIRCLE0 : 0);
+  if (car_goal) a.level = env_kind - OSA_EVAL_ENV_CARGOAL0;
+  if (car_circle) a.level = env_kind - OSA_EVAL_ENV_CARCIRCLE0;
   const dim3 grid((unsigned)((K + 15) / 16));
 #define OSA_CALL(HT, OT, NSB)                                                                                   \
   do {                                                                                                          \
@@ -246,6 +297,12 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
                          osa_stream(stream), a);                                                                \
     else if (circle)                                                                                            \
       hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CIRCLE0>), grid, dim3(64), lds,         \
+                         osa_stream(stream), a);                                                                \
+    else if (car_goal)                                                                                          \
+      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CARGOAL0>), grid, dim3(64), lds,        \
+                         osa_stream(stream), a);                                                                \
+    else if (car_circle)                                                                                        \
+      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CARCIRCLE0>), grid, dim3(64), lds,      \
                          osa_stream(stream), a);                                                                \
     else if (env_kind == OSA_EVAL_ENV_REACH)                                                                    \
       hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_REACH>), grid, dim3(64), lds,           \
@@ -264,7 +321,11 @@ int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute) {
   if (obs_dim < 1 || act_dim < 1) return 0;
   const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
   const bool circle = env_kind >= OSA_EVAL_ENV_CIRCLE0 && env_kind <= OSA_EVAL_ENV_CIRCLE0 + 2;
-  const int state = env_kind == OSA_EVAL_ENV_REACH ? 6 : (nav ? OSA_NAV_STATE : (circle ? OSA_CIRCLE_STATE : 0));
+  const bool car_goal = env_kind >= OSA_EVAL_ENV_CARGOAL0 && env_kind <= OSA_EVAL_ENV_CARGOAL0 + 2;
+  const bool car_circle = env_kind >= OSA_EVAL_ENV_CARCIRCLE0 && env_kind <= OSA_EVAL_ENV_CARCIRCLE0 + 2;
+  int state = env_kind == OSA_EVAL_ENV_REACH ? 6 : (nav ? OSA_NAV_STATE : (circle ? OSA_CIRCLE_STATE : 0));
+  if (car_goal) state = OSA_NAV_STATE;
+  if (car_circle) state = OSA_CAR_CIRCLE_STATE;
   return obs_dim + (saute ? 1 : 0) + act_dim + 3 + state;
 }
 

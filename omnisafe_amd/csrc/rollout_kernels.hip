@@ -529,6 +529,173 @@ __global__ __launch_bounds__(64) void osa_circle_env_kernel(
     }
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// "SynthNavCarGoal{0,1,2}" (env_device.h): state[n][64], 72 observation columns.  One wave per env and the object
+// staging of osa_nav_env_kernel (one lane per object into seen[3][33], a ballot for the cost).  The row is wider than
+// the wave, so a lane is no longer "its column": lane l computes column l and lanes 0 - 7 also column 64 + l, the last
+// eight vase bins.  The second column is a second walk over the vases for the whole wave (eight lanes active), which is
+// what level 2 pays above the ratio of the row bytes (7.66 us against SynthNavGoal2's 6.16 at N = 4096, 1.24 x for
+// 1.2 x the bytes; levels 0 / 1, with 0 / 1 vases: 1.10 / 1.09 x).  Columns 72 .. D - 1 of a wider row are zeros.
+// ------------------------------------------------------------------------------------------------
+// Column `col` of the observation row from the staged objects.
+__device__ __forceinline__ float osa_car_seen_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
+                                                  const float (&seen)[3][OSA_NAV_SEEN], int level, int col) {
+  float v = osa_car_sensor_col(d, w, col);
+  if (col >= OSA_CAR_SENSORS && col < OSA_CAR_GOAL_OBS) {
+    const int cls = (col - OSA_CAR_SENSORS) >> 4, k = (col - OSA_CAR_SENSORS) & 15;
+    const int cnt = cls == 0 ? 1 : (cls == 1 ? osa_nav_hazards(level) : osa_nav_vases(level));
+    const int first = cls == 0 ? 32 : (cls == 1 ? 0 : 16);
+    for (int i = first; i < first + cnt; ++i)
+      if (osa_nav_in_bin(k, seen[0][i], seen[1][i])) v = fmaxf(v, seen[2][i]);
+  }
+  return v;
+}
+
+// Columns `lane` (v0) and, in lanes 0 - 7, 64 + lane (v1; 0 in the other lanes) of the observation row of state
+// (d, w, row) and, wave-uniform, whether the position costs.
+__device__ __forceinline__ void osa_car_wave_obs(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
+                                                 const float* __restrict__ row, float (&seen)[3][OSA_NAV_SEEN],
+                                                 int level, int lane, bool& hit, float& v0, float& v1) {
+  const int cls_o = lane == 32 ? 0 : (lane < 16 ? 1 : 2), i_o = lane & 15;
+  const bool object = lane == 32 || (lane < 16 && i_o < osa_nav_hazards(level)) ||
+                      (lane >= 16 && lane < 32 && i_o < osa_nav_vases(level));
+  bool mine = false;
+  if (object) {
+    const float* __restrict__ o = row + (cls_o == 1 ? OSA_NAV_HAZ : OSA_NAV_VASE) + 2 * i_o;
+    float bx, by, dist;
+    osa_nav_see(d, cls_o == 0 ? d[8] : o[0], cls_o == 0 ? d[9] : o[1], bx, by, dist);
+    mine = osa_nav_hit(level, cls_o, dist);
+    seen[0][lane] = bx;
+    seen[1][lane] = by;
+    seen[2][lane] = osa_nav_reading(dist);
+  }
+  hit = __ballot(mine) != 0;
+  __syncthreads();
+  v0 = osa_car_seen_col(d, w, seen, level, lane);
+  v1 = lane < OSA_CAR_GOAL_OBS - 64 ? osa_car_seen_col(d, w, seen, level, 64 + lane) : 0.f;
+  __syncthreads();  // (the slots are written again on a truncating step)
+}
+
+__global__ __launch_bounds__(64) void osa_car_goal_env_kernel(
+    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
+    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
+    const float* __restrict__ action, int ld_a,
+    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
+    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
+    int ld_f, int reset_only) {
+  __shared__ float row[OSA_NAV_STATE];
+  __shared__ float seen[3][OSA_NAV_SEEN];
+  if (step_base) step += *step_base;
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const unsigned long long key = seed ^ OSA_NAV_KEY;  // the point task's key: the same arena (env_device.h)
+  float* __restrict__ srow = state + (long)n * OSA_NAV_STATE;
+  row[lane] = srow[lane];
+  __syncthreads();
+  float d[OSA_NAV_DYN];
+#pragma unroll
+  for (int k = 0; k < OSA_NAV_DYN; ++k) d[k] = row[k];
+  float w[2] = {row[OSA_CAR_WHEELS], row[OSA_CAR_WHEELS + 1]};
+  uint8_t trunc = 0;
+  float r = 0.f, v0 = 0.f, v1 = 0.f;
+  bool hit = false;
+  if (!reset_only) {
+    osa_car_goal_advance(d, w, row, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], key, step, n, r);
+    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
+    osa_car_wave_obs(d, w, row, seen, level, lane, hit, v0, v1);
+    if (trunc && final_obs)
+      for (int k = lane; k < D; k += 64)
+        final_obs[(long)n * ld_f + k] = k < 64 ? v0 : (k < OSA_CAR_GOAL_OBS ? v1 : 0.f);
+  }
+  if (reset_only || trunc) {  // (uniform over the workgroup)
+    if (lane >= OSA_NAV_HAZ) {
+      const float o = osa_nav_fresh_obj(key, step, n, level, lane);
+      row[lane] = o;
+      srow[lane] = o;
+    }
+    __syncthreads();
+    osa_nav_fresh(key, step, n, level, row, d);  // (d[7], the Car's t_prev, starts at 0 with the point robot's pad)
+    w[0] = w[1] = 0.f;
+    bool unused;
+    osa_car_wave_obs(d, w, row, seen, level, lane, unused, v0, v1);
+  }
+  for (int k = lane; k < D; k += 64) obs[(long)n * ld + k] = k < 64 ? v0 : (k < OSA_CAR_GOAL_OBS ? v1 : 0.f);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < OSA_NAV_DYN; ++k) srow[k] = d[k];
+    srow[OSA_CAR_WHEELS] = w[0];
+    srow[OSA_CAR_WHEELS + 1] = w[1];
+    if (reset_only) {
+      steps[n] = 0;
+    } else {
+      reward[n] = r;
+      cost[n] = hit ? 1.f : 0.f;
+      terminated[n] = 0;
+      truncated[n] = trunc;
+      steps[n] = trunc ? 0 : steps[n] + 1;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// "SynthNavCarCircle{0,1,2}" (env_device.h): state[n][12], 40 observation columns, no objects.  The half-wave mapping
+// of osa_circle_env_kernel: two envs per 64-lane workgroup, every lane of a half computes the whole transition from
+// the 48-byte state row, and the strided column loop covers the 40 columns in two rounds (lane l writes column l and,
+// for l < 8, column 32 + l; columns past 39 of a wider row are zeros in the same loop).  No LDS, no barrier, no
+// cross-lane operation.  (OSA_CAR_CIRCLE_LANES = 64 builds one wave per env for comparison: tools/car_env_timing.py.)
+// ------------------------------------------------------------------------------------------------
+#ifndef OSA_CAR_CIRCLE_LANES
+#define OSA_CAR_CIRCLE_LANES 32  // lanes per env
+#endif
+#define OSA_CAR_CIRCLE_PER_WG (64 / OSA_CAR_CIRCLE_LANES)  // envs per workgroup
+__global__ __launch_bounds__(64) void osa_car_circle_env_kernel(
+    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
+    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
+    const float* __restrict__ action, int ld_a,
+    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
+    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
+    int ld_f, int reset_only) {
+  if (step_base) step += *step_base;
+  const int n = OSA_CAR_CIRCLE_PER_WG * blockIdx.x + threadIdx.x / OSA_CAR_CIRCLE_LANES;
+  const int lane = threadIdx.x % OSA_CAR_CIRCLE_LANES;
+  if (n >= N) return;
+  const unsigned long long key = seed ^ OSA_CIRCLE_KEY;  // the point task's key: the same start (env_device.h)
+  float* __restrict__ srow = state + (long)n * OSA_CAR_CIRCLE_STATE;
+  float d[OSA_NAV_DYN];
+#pragma unroll
+  for (int k = 0; k < OSA_CIRCLE_STATE; ++k) d[k] = srow[k];
+  d[8] = d[9] = 0.f;  // the lidar's object: the circle's centre
+  float w[2] = {srow[OSA_CAR_WHEELS], srow[OSA_CAR_WHEELS + 1]};
+  uint8_t trunc = 0;
+  float r = 0.f, c = 0.f;
+  if (!reset_only) {
+    osa_car_circle_transition(d, w, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], r, c);
+    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
+    if (trunc && final_obs)
+      for (int k = lane; k < D; k += OSA_CAR_CIRCLE_LANES)
+        final_obs[(long)n * ld_f + k] = osa_car_circle_obs_col(d, w, k);
+  }
+  if (reset_only || trunc) {
+    osa_circle_fresh(key, step, n, d);  // (d[7], the Car's t_prev, starts at 0 with the point robot's pad)
+    w[0] = w[1] = 0.f;
+  }
+  for (int k = lane; k < D; k += OSA_CAR_CIRCLE_LANES) obs[(long)n * ld + k] = osa_car_circle_obs_col(d, w, k);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < OSA_NAV_DYN; ++k) srow[k] = d[k];
+    srow[OSA_CAR_WHEELS] = w[0];
+    srow[OSA_CAR_WHEELS + 1] = w[1];
+    if (reset_only) {
+      steps[n] = 0;
+    } else {
+      reward[n] = r;
+      cost[n] = c;
+      terminated[n] = 0;
+      truncated[n] = trunc;
+      steps[n] = trunc ? 0 : steps[n] + 1;
+    }
+  }
+}
 #pragma clang fp contract(fast)
 
 // ------------------------------------------------------------------------------------------------
@@ -839,6 +1006,41 @@ int osa_circle_env_step(unsigned long long seed, unsigned long long step,
   hipLaunchKernelGGL(osa_circle_env_kernel, dim3((N + OSA_CIRCLE_PER_WG - 1) / OSA_CIRCLE_PER_WG), dim3(64), 0,
                      osa_stream(stream), seed, step, step_base, N, obs_dim, horizon, level, state, steps, action,
                      ld_action, obs, ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+int osa_car_goal_env_step(unsigned long long seed, unsigned long long step,
+                          const unsigned long long* step_base, int N, int obs_dim,
+                          int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                          float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                          uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                          void* stream) {
+  OSA_REQUIRE(N > 0 && obs_dim >= OSA_CAR_GOAL_OBS && state && steps && obs && ld_obs >= obs_dim);
+  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
+  if (!reset_only)
+    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  hipLaunchKernelGGL(osa_car_goal_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
+                     obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs, reward, cost,
+                     terminated, truncated, final_obs, ld_final, reset_only);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+int osa_car_circle_env_step(unsigned long long seed, unsigned long long step,
+                            const unsigned long long* step_base, int N, int obs_dim,
+                            int horizon, int level, float* state, int* steps, const float* action, int ld_action,
+                            float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                            uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                            void* stream) {
+  OSA_REQUIRE(N > 0 && obs_dim >= OSA_CAR_CIRCLE_OBS && state && steps && obs && ld_obs >= obs_dim);
+  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
+  if (!reset_only)
+    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  hipLaunchKernelGGL(osa_car_circle_env_kernel,
+                     dim3((N + OSA_CAR_CIRCLE_PER_WG - 1) / OSA_CAR_CIRCLE_PER_WG), dim3(64), 0, osa_stream(stream),
+                     seed, step, step_base, N, obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs,
+                     reward, cost, terminated, truncated, final_obs, ld_final, reset_only);
   OSA_CHECK_LAUNCH();
   return OSA_OK;
 }

@@ -432,3 +432,199 @@ class NavCircleVectorEnv:  # pylint: disable=too-many-instance-attributes
 
     def close(self) -> None:
         return None
+
+
+CAR_GOAL_LEVELS = {'SynthNavCarGoal0-v0': 0, 'SynthNavCarGoal1-v0': 1, 'SynthNavCarGoal2-v0': 2}
+
+
+@env_register
+class NavCarGoalVectorEnv:  # pylint: disable=too-many-instance-attributes
+    """SynthNavGoal driven by the Car (osa_car_goal_env_step), with the structure of the Safety-Gymnasium CarGoal
+    tasks: the two actions command the left and the right wheel, whose speeds lag the commands; the forward speed is
+    the wheels' mean and the turn rate their difference.  Goal, hazards, vases, reward, costs and levels are
+    SynthNavGoal's, and so is the reset: the same seed gives the same arena as ``SynthNavGoal<level>-v0``.
+    Observation/action dims of SafetyCarGoal (72 / 2): 24 sensor columns (f, f - f_prev, t, heading, wheel speeds,
+    t - t_prev, zeros) and the three 16-bin lidars.  ``state`` is the (N, 64) state matrix laid out as
+    include/omnisafe_amd.h states."""
+
+    _support_envs = list(CAR_GOAL_LEVELS)
+    need_auto_reset_wrapper = False
+    need_time_limit_wrapper = False
+    need_evaluation = False
+
+    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 1000,
+                 seed: int = 0, **_unused) -> None:
+        self._lib = _lib.load(require_gpu=True)
+        self._env_id = env_id
+        self._level = CAR_GOAL_LEVELS[env_id]
+        self._num_envs = int(num_envs)
+        self._device = torch.device(device)
+        self._obs_dim, self._act_dim = 72, 2
+        self._horizon = int(horizon)
+        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
+        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
+        self._seed = int(seed)
+        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
+        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._since_reset = 0
+        N, dev = self._num_envs, self._device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.state = torch.zeros(N, 64, **f32)
+        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
+        self._final = torch.zeros(N, self._obs_dim, **f32)
+        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
+        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._flip = 0
+
+    num_envs = property(lambda self: self._num_envs)
+    observation_space = property(lambda self: self._observation_space)
+    action_space = property(lambda self: self._action_space)
+    max_episode_steps = property(lambda self: self._horizon)
+    level = property(lambda self: self._level)
+
+    def set_seed(self, seed: int) -> None:
+        self._seed = int(seed)
+
+    def _launch(self, obs, action, reset_only: int) -> None:
+        ld_a = action.stride(0) if action is not None else 0
+        _lib.check(self._lib.osa_car_goal_env_step(
+            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
+            self._horizon, self._level, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a,
+            _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
+            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
+            _lib.stream_ptr()), 'osa_car_goal_env_step')
+        self._t += 1
+
+    def reset(self, seed: int | None = None, options: dict | None = None):
+        if seed is not None:
+            self.set_seed(seed)
+        self._flip ^= 1
+        obs = self._obs[self._flip]
+        self._launch(obs, None, 1)
+        self._since_reset = 0
+        return obs, {}
+
+    def step(self, action: torch.Tensor):
+        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
+            and action.stride(1) == 1
+        self._flip ^= 1
+        obs = self._obs[self._flip]
+        self._launch(obs, action, 0)
+        self._since_reset += 1
+        info: dict[str, Any] = {}
+        if self._since_reset % self._horizon == 0:  # every env truncates on this step
+            info['final_observation'] = self._final
+            info['_final_observation'] = self._trunc
+        return obs, self._reward, self._cost, self._term, self._trunc, info
+
+    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
+
+    def commit(self) -> None:
+        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
+        self._t_base += self._t
+        self._t = 0
+
+    def render(self):
+        return None
+
+    def close(self) -> None:
+        return None
+
+
+CAR_CIRCLE_LEVELS = {'SynthNavCarCircle0-v0': 0, 'SynthNavCarCircle1-v0': 1, 'SynthNavCarCircle2-v0': 2}
+
+
+@env_register
+class NavCarCircleVectorEnv:  # pylint: disable=too-many-instance-attributes
+    """SynthNavCircle driven by the Car (osa_car_circle_env_step), with the structure of the Safety-Gymnasium
+    CarCircle tasks: the two actions command the left and the right wheel (see :class:`NavCarGoalVectorEnv`); reward,
+    corridor cost, levels and reset are SynthNavCircle's (the same seed gives the same start).  Observation/action
+    dims 40 / 2: the Car's 24 sensor columns and a 16-bin lidar of the circle's centre.  ``state`` is the (N, 12)
+    state matrix laid out as include/omnisafe_amd.h states."""
+
+    _support_envs = list(CAR_CIRCLE_LEVELS)
+    need_auto_reset_wrapper = False
+    need_time_limit_wrapper = False
+    need_evaluation = False
+
+    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 500,
+                 seed: int = 0, **_unused) -> None:
+        self._lib = _lib.load(require_gpu=True)
+        self._env_id = env_id
+        self._level = CAR_CIRCLE_LEVELS[env_id]
+        self._num_envs = int(num_envs)
+        self._device = torch.device(device)
+        self._obs_dim, self._act_dim = 40, 2
+        self._horizon = int(horizon)
+        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
+        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
+        self._seed = int(seed)
+        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
+        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._since_reset = 0
+        N, dev = self._num_envs, self._device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.state = torch.zeros(N, 12, **f32)
+        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
+        self._final = torch.zeros(N, self._obs_dim, **f32)
+        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
+        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._flip = 0
+
+    num_envs = property(lambda self: self._num_envs)
+    observation_space = property(lambda self: self._observation_space)
+    action_space = property(lambda self: self._action_space)
+    max_episode_steps = property(lambda self: self._horizon)
+    level = property(lambda self: self._level)
+
+    def set_seed(self, seed: int) -> None:
+        self._seed = int(seed)
+
+    def _launch(self, obs, action, reset_only: int) -> None:
+        ld_a = action.stride(0) if action is not None else 0
+        _lib.check(self._lib.osa_car_circle_env_step(
+            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
+            self._horizon, self._level, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a,
+            _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
+            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
+            _lib.stream_ptr()), 'osa_car_circle_env_step')
+        self._t += 1
+
+    def reset(self, seed: int | None = None, options: dict | None = None):
+        if seed is not None:
+            self.set_seed(seed)
+        self._flip ^= 1
+        obs = self._obs[self._flip]
+        self._launch(obs, None, 1)
+        self._since_reset = 0
+        return obs, {}
+
+    def step(self, action: torch.Tensor):
+        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
+            and action.stride(1) == 1
+        self._flip ^= 1
+        obs = self._obs[self._flip]
+        self._launch(obs, action, 0)
+        self._since_reset += 1
+        info: dict[str, Any] = {}
+        if self._since_reset % self._horizon == 0:  # every env truncates on this step
+            info['final_observation'] = self._final
+            info['_final_observation'] = self._trunc
+        return obs, self._reward, self._cost, self._term, self._trunc, info
+
+    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
+
+    def commit(self) -> None:
+        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
+        self._t_base += self._t
+        self._t = 0
+
+    def render(self):
+        return None
+
+    def close(self) -> None:
+        return None

@@ -5,7 +5,8 @@
 ``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does.
 
 Two paths, one semantics:
-  persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, SynthNavCircle*-v0, Synth*-v0):
+  persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, SynthNavCircle*-v0,
+              SynthNavCarGoal*-v0, SynthNavCarCircle*-v0, Synth*-v0):
               every episode in ONE launch of osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a
               fresh env.
   per-step    everything else (general networks, host envs, an env object given as ``env=``): the existing launches
@@ -38,15 +39,20 @@ from .spaces import Box
 
 TIME_LIMIT = 1000  # evaluator.py:179-180
 DEVICE_ENVS = (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv, envs_mod.NavGoalVectorEnv,
-               envs_mod.NavCircleVectorEnv)
+               envs_mod.NavCircleVectorEnv, envs_mod.NavCarGoalVectorEnv, envs_mod.NavCarCircleVectorEnv)
 
 
 def _env_kind(env) -> int:
-    """env_kind of osa_eval_episodes: OSA_EVAL_ENV_SYNTH / _REACH / _NAV0 + level / _CIRCLE0 + level."""
+    """env_kind of osa_eval_episodes: OSA_EVAL_ENV_SYNTH / _REACH / _NAV0 + level / _CIRCLE0 + level / _CARGOAL0 +
+    level / _CARCIRCLE0 + level."""
     if isinstance(env, envs_mod.NavGoalVectorEnv):
         return 16 + env.level
     if isinstance(env, envs_mod.NavCircleVectorEnv):
         return 32 + env.level
+    if isinstance(env, envs_mod.NavCarGoalVectorEnv):
+        return 48 + env.level
+    if isinstance(env, envs_mod.NavCarCircleVectorEnv):
+        return 64 + env.level
     return 1 if isinstance(env, envs_mod.ReachVectorEnv) else 0
 
 
@@ -97,6 +103,10 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             return 60, 2
         if self._env_id in envs_mod.CIRCLE_LEVELS:
             return 28, 2
+        if self._env_id in envs_mod.CAR_GOAL_LEVELS:
+            return 72, 2
+        if self._env_id in envs_mod.CAR_CIRCLE_LEVELS:
+            return 40, 2
         if self._env_id in envs_mod.SYNTH_DIMS:
             return envs_mod.SYNTH_DIMS[self._env_id]
         env = envs_mod.make(self._env_id, num_envs=1, device=self._device, **self._env_cfgs)
@@ -208,8 +218,9 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS
         max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
         state_w = 6 if isinstance(env, envs_mod.ReachVectorEnv) else (
-            64 if isinstance(env, envs_mod.NavGoalVectorEnv) else (
-                8 if isinstance(env, envs_mod.NavCircleVectorEnv) else 0))  # state floats of a trace record
+            64 if isinstance(env, (envs_mod.NavGoalVectorEnv, envs_mod.NavCarGoalVectorEnv)) else (
+                8 if isinstance(env, envs_mod.NavCircleVectorEnv) else (
+                    12 if isinstance(env, envs_mod.NavCarCircleVectorEnv) else 0)))  # state floats of a trace record
         f64 = dict(dtype=torch.float64, device=dev)
         ret, cost = torch.zeros(K, **f64), torch.zeros(K, **f64)
         length = torch.zeros(K, dtype=torch.int32, device=dev)

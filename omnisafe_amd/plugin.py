@@ -99,6 +99,14 @@ def install(algorithms: tuple[str, ...] | None = None) -> list[str]:
     if circle_ids:
         reg._class['OmnisafeAmdNavCircleVectorEnv'] = amd_envs.NavCircleVectorEnv  # noqa: SLF001
         reg._support_envs['OmnisafeAmdNavCircleVectorEnv'] = circle_ids  # noqa: SLF001
+    car_goal_ids = [e for e in amd_envs.NavCarGoalVectorEnv._support_envs if e not in known]  # noqa: SLF001
+    if car_goal_ids:
+        reg._class['OmnisafeAmdNavCarGoalVectorEnv'] = amd_envs.NavCarGoalVectorEnv  # noqa: SLF001
+        reg._support_envs['OmnisafeAmdNavCarGoalVectorEnv'] = car_goal_ids  # noqa: SLF001
+    car_circle_ids = [e for e in amd_envs.NavCarCircleVectorEnv._support_envs if e not in known]  # noqa: SLF001
+    if car_circle_ids:
+        reg._class['OmnisafeAmdNavCarCircleVectorEnv'] = amd_envs.NavCarCircleVectorEnv  # noqa: SLF001
+        reg._support_envs['OmnisafeAmdNavCarCircleVectorEnv'] = car_circle_ids  # noqa: SLF001
     del omnisafe
     return swapped
 
