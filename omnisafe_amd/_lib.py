@@ -19,6 +19,8 @@ c_ptr = C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/omnisafe_amd.h one to one.
 _I, _L, _F, _D, _P, _U = C.c_int, C.c_long, C.c_float, C.c_double, C.c_void_p, C.c_ulonglong
+# the env entry points that take a level: osa_reach_env_step's arguments with `level` after `horizon`
+_LEVEL_ENV_STEP = (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P])
 SIGNATURES: dict[str, tuple] = {
     'osa_strerror': (C.c_char_p, [_I]),
     'osa_version': (_I, []),
@@ -129,12 +131,10 @@ SIGNATURES: dict[str, tuple] = {
     'osa_rollout_post_step': (_I, [_I, _I] + [_P] * 21),
     'osa_synth_env_step': (_I, [_U, _U, _P, _I, _I, _I, _F, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     'osa_reach_env_step': (_I, [_U, _U, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
-    'osa_nav_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
-    'osa_circle_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
-    'osa_car_goal_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I,
-                                   _P]),
-    'osa_car_circle_env_step': (_I, [_U, _U, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I,
-                                     _P]),
+    'osa_nav_env_step': _LEVEL_ENV_STEP,
+    'osa_circle_env_step': _LEVEL_ENV_STEP,
+    'osa_car_goal_env_step': _LEVEL_ENV_STEP,
+    'osa_car_circle_env_step': _LEVEL_ENV_STEP,
     'osa_eval_episodes': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _F, _F, _U, _I, _F, _I, _I, _F, _F,
                                _I, _D, _D, _P, _P, _P, _P, _P]),
     'osa_eval_trace_floats': (_I, [_I, _I, _I, _I]),

@@ -246,6 +246,29 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
 }
 #pragma clang fp contract(fast)
 
+// What the host needs to know of an env_kind: one row per family, matched by family <= env_kind <= family + level.
+struct OsaEvalKind {
+  int family;            // the OSA_EVAL_ENV_* constant the kernel is instantiated with; -1: unknown kind
+  int level;             // in the table: the highest level; as returned: env_kind - family
+  int min_obs, min_act;  // least obs_dim and act_dim
+  int state_floats;      // state floats of a trace record
+  bool lds_state;        // the kernel keeps a row of OSA_NAV_STATE floats per episode in LDS
+};
+
+static OsaEvalKind osa_eval_kind(int env_kind) {
+  static const OsaEvalKind kinds[] = {
+      {OSA_EVAL_ENV_SYNTH, 0, 1, 1, 0, false},
+      {OSA_EVAL_ENV_REACH, 0, 6, 2, 6, false},
+      {OSA_EVAL_ENV_NAV0, 2, OSA_NAV_OBS, 2, OSA_NAV_STATE, true},
+      {OSA_EVAL_ENV_CIRCLE0, 2, OSA_CIRCLE_OBS, 2, OSA_CIRCLE_STATE, false},
+      {OSA_EVAL_ENV_CARGOAL0, 2, OSA_CAR_GOAL_OBS, 2, OSA_NAV_STATE, true},
+      {OSA_EVAL_ENV_CARCIRCLE0, 2, OSA_CAR_CIRCLE_OBS, 2, OSA_CAR_CIRCLE_STATE, false}};
+  for (const OsaEvalKind& k : kinds)
+    if (env_kind >= k.family && env_kind <= k.family + k.level)
+      return {k.family, env_kind - k.family, k.min_obs, k.min_act, k.state_floats, k.lds_state};
+  return {-1, 0, 0, 0, 0, false};
+}
+
 extern "C" {
 
 int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden, const float* params,
@@ -259,23 +282,15 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   OSA_REQUIRE(params && old_min && old_max && max_action != min_action && ep_ret && ep_cost && ep_len);
   OSA_REQUIRE((norm_mean == nullptr) == (norm_std == nullptr) && (norm_mean == nullptr) == (norm_count == nullptr));
   OSA_REQUIRE(!saute || (saute_budget != 0.f && saute_gamma != 0.f));
-  const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
-  const bool circle = env_kind >= OSA_EVAL_ENV_CIRCLE0 && env_kind <= OSA_EVAL_ENV_CIRCLE0 + 2;
-  const bool car_goal = env_kind >= OSA_EVAL_ENV_CARGOAL0 && env_kind <= OSA_EVAL_ENV_CARGOAL0 + 2;
-  const bool car_circle = env_kind >= OSA_EVAL_ENV_CARCIRCLE0 && env_kind <= OSA_EVAL_ENV_CARCIRCLE0 + 2;
-  if (env_kind != OSA_EVAL_ENV_SYNTH && env_kind != OSA_EVAL_ENV_REACH && !nav && !circle && !car_goal && !car_circle)
-    return OSA_EUNSUPPORTED;
-  if (env_kind == OSA_EVAL_ENV_REACH) OSA_REQUIRE(obs_dim >= 6 && act_dim >= 2);
-  if (nav) OSA_REQUIRE(obs_dim >= OSA_NAV_OBS && act_dim >= 2);
-  if (circle) OSA_REQUIRE(obs_dim >= OSA_CIRCLE_OBS && act_dim >= 2);
-  if (car_goal) OSA_REQUIRE(obs_dim >= OSA_CAR_GOAL_OBS && act_dim >= 2);
-  if (car_circle) OSA_REQUIRE(obs_dim >= OSA_CAR_CIRCLE_OBS && act_dim >= 2);
+  const OsaEvalKind kind = osa_eval_kind(env_kind);
+  if (kind.family < 0) return OSA_EUNSUPPORTED;
+  OSA_REQUIRE(obs_dim >= kind.min_obs && act_dim >= kind.min_act);
   const int in_w = obs_dim + (saute ? 1 : 0);
   const int rc = osa_check_dims(in_w, act_dim, hidden);
   if (rc != OSA_OK) return rc;
   OsaEvalArgs a;
   a.nd = osa_make_net(in_w, act_dim, hidden);
-  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (nav || car_goal ? OSA_NAV_STATE : 0)) * sizeof(float);
+  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (kind.lds_state ? OSA_NAV_STATE : 0)) * sizeof(float);
   if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns (928 with a 64-float state row)
   a.params = params;
   a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
@@ -286,47 +301,31 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   a.early_terminated = early_terminated ? 1 : 0; a.cost_limit = cost_limit; a.cost_criteria = cost_criteria;
   a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len; a.trace = trace;
   a.rec = osa_eval_trace_floats(env_kind, obs_dim, act_dim, saute);
-  a.level = nav ? env_kind - OSA_EVAL_ENV_NAV0 : (circle ? env_kind - OSA_EVAL_ENV_CIRCLE0 : 0);
-  if (car_goal) a.level = env_kind - OSA_EVAL_ENV_CARGOAL0;
-  if (car_circle) a.level = env_kind - OSA_EVAL_ENV_CARCIRCLE0;
+  a.level = kind.level;
   const dim3 grid((unsigned)((K + 15) / 16));
-#define OSA_CALL(HT, OT, NSB)                                                                                   \
-  do {                                                                                                          \
-    if (nav)                                                                                                    \
-      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_NAV0>), grid, dim3(64), lds,            \
-                         osa_stream(stream), a);                                                                \
-    else if (circle)                                                                                            \
-      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CIRCLE0>), grid, dim3(64), lds,         \
-                         osa_stream(stream), a);                                                                \
-    else if (car_goal)                                                                                          \
-      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CARGOAL0>), grid, dim3(64), lds,        \
-                         osa_stream(stream), a);                                                                \
-    else if (car_circle)                                                                                        \
-      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_CARCIRCLE0>), grid, dim3(64), lds,      \
-                         osa_stream(stream), a);                                                                \
-    else if (env_kind == OSA_EVAL_ENV_REACH)                                                                    \
-      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_REACH>), grid, dim3(64), lds,           \
-                         osa_stream(stream), a);                                                                \
-    else                                                                                                        \
-      hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, OSA_EVAL_ENV_SYNTH>), grid, dim3(64), lds,           \
-                         osa_stream(stream), a);                                                                \
-  } while (0)
+#define OSA_LAUNCH(HT, OT, ENV)                                                                               \
+  case ENV:                                                                                                   \
+    hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, ENV>), grid, dim3(64), lds, osa_stream(stream), a); \
+    break
+#define OSA_CALL(HT, OT, NSB)                     \
+  switch (kind.family) {                          \
+    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_NAV0);        \
+    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_CIRCLE0);     \
+    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_CARGOAL0);    \
+    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_CARCIRCLE0);  \
+    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_REACH);       \
+    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_SYNTH);       \
+  }
   OSA_DISPATCH_OT(a.nd, OSA_CALL);
 #undef OSA_CALL
+#undef OSA_LAUNCH
   OSA_CHECK_LAUNCH();
   return OSA_OK;
 }
 
 int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute) {
   if (obs_dim < 1 || act_dim < 1) return 0;
-  const bool nav = env_kind >= OSA_EVAL_ENV_NAV0 && env_kind <= OSA_EVAL_ENV_NAV0 + 2;
-  const bool circle = env_kind >= OSA_EVAL_ENV_CIRCLE0 && env_kind <= OSA_EVAL_ENV_CIRCLE0 + 2;
-  const bool car_goal = env_kind >= OSA_EVAL_ENV_CARGOAL0 && env_kind <= OSA_EVAL_ENV_CARGOAL0 + 2;
-  const bool car_circle = env_kind >= OSA_EVAL_ENV_CARCIRCLE0 && env_kind <= OSA_EVAL_ENV_CARCIRCLE0 + 2;
-  int state = env_kind == OSA_EVAL_ENV_REACH ? 6 : (nav ? OSA_NAV_STATE : (circle ? OSA_CIRCLE_STATE : 0));
-  if (car_goal) state = OSA_NAV_STATE;
-  if (car_circle) state = OSA_CAR_CIRCLE_STATE;
-  return obs_dim + (saute ? 1 : 0) + act_dim + 3 + state;
+  return obs_dim + (saute ? 1 : 0) + act_dim + 3 + osa_eval_kind(env_kind).state_floats;
 }
 
 }  // extern "C"

@@ -865,6 +865,15 @@ __global__ __launch_bounds__(1024) void osa_gather_mean_kernel(const float* __re
   if (threadIdx.x == 0) *out = (float)(s / (double)n);
 }
 
+// The argument checks of the env entry points that take a level (min_obs: the env's observation columns).
+static bool osa_level_env_ok(int min_obs, int N, int obs_dim, int horizon, int level, float* state, int* steps,
+                             const float* action, int ld_action, float* obs, int ld_obs, float* reward, float* cost,
+                             uint8_t* terminated, uint8_t* truncated, float* final_obs, int ld_final, int reset_only) {
+  if (!(N > 0 && obs_dim >= min_obs && state && steps && obs && ld_obs >= obs_dim)) return false;
+  if (!(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim))) return false;
+  return reset_only || (action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+}
+
 extern "C" {
 
 size_t osa_normalizer_ws_doubles(int N, int D) {
@@ -982,10 +991,8 @@ int osa_nav_env_step(unsigned long long seed, unsigned long long step,
                      float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
                      uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                      void* stream) {
-  OSA_REQUIRE(N > 0 && obs_dim >= OSA_NAV_OBS && state && steps && obs && ld_obs >= obs_dim);
-  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
-  if (!reset_only)
-    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  OSA_REQUIRE(osa_level_env_ok(OSA_NAV_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
+                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
   hipLaunchKernelGGL(osa_nav_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
                      obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs, reward, cost,
                      terminated, truncated, final_obs, ld_final, reset_only);
@@ -999,10 +1006,8 @@ int osa_circle_env_step(unsigned long long seed, unsigned long long step,
                         float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
                         uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                         void* stream) {
-  OSA_REQUIRE(N > 0 && obs_dim >= OSA_CIRCLE_OBS && state && steps && obs && ld_obs >= obs_dim);
-  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
-  if (!reset_only)
-    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  OSA_REQUIRE(osa_level_env_ok(OSA_CIRCLE_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
+                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
   hipLaunchKernelGGL(osa_circle_env_kernel, dim3((N + OSA_CIRCLE_PER_WG - 1) / OSA_CIRCLE_PER_WG), dim3(64), 0,
                      osa_stream(stream), seed, step, step_base, N, obs_dim, horizon, level, state, steps, action,
                      ld_action, obs, ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only);
@@ -1016,10 +1021,8 @@ int osa_car_goal_env_step(unsigned long long seed, unsigned long long step,
                           float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
                           uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                           void* stream) {
-  OSA_REQUIRE(N > 0 && obs_dim >= OSA_CAR_GOAL_OBS && state && steps && obs && ld_obs >= obs_dim);
-  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
-  if (!reset_only)
-    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  OSA_REQUIRE(osa_level_env_ok(OSA_CAR_GOAL_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
+                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
   hipLaunchKernelGGL(osa_car_goal_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
                      obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs, reward, cost,
                      terminated, truncated, final_obs, ld_final, reset_only);
@@ -1033,10 +1036,8 @@ int osa_car_circle_env_step(unsigned long long seed, unsigned long long step,
                             float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
                             uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                             void* stream) {
-  OSA_REQUIRE(N > 0 && obs_dim >= OSA_CAR_CIRCLE_OBS && state && steps && obs && ld_obs >= obs_dim);
-  OSA_REQUIRE(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim));
-  if (!reset_only)
-    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+  OSA_REQUIRE(osa_level_env_ok(OSA_CAR_CIRCLE_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
+                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
   hipLaunchKernelGGL(osa_car_circle_env_kernel,
                      dim3((N + OSA_CAR_CIRCLE_PER_WG - 1) / OSA_CAR_CIRCLE_PER_WG), dim3(64), 0, osa_stream(stream),
                      seed, step, step_base, N, obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs,
@@ -1044,7 +1045,6 @@ int osa_car_circle_env_step(unsigned long long seed, unsigned long long step,
   OSA_CHECK_LAUNCH();
   return OSA_OK;
 }
-
 
 size_t osa_episode_flush_ws_doubles(long M) {
   (void)M;

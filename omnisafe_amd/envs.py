@@ -60,225 +60,70 @@ def make(env_id: str, num_envs: int = 1, device='cuda:0', **env_cfgs):
     return env
 
 
-@env_register
-class SynthVectorEnv:  # pylint: disable=too-many-instance-attributes
-    """Zero-cost synthetic vector CMDP living entirely in HBM (osa_synth_env_step)."""
+class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
+    """Host side of a vector CMDP that lives entirely in HBM: one launch of the subclass's entry point per ``reset``
+    / ``step`` on buffers allocated once.  Observations are double-buffered (the caller may still hold the previous
+    one); all envs reset together, so the truncating steps are known on the host and ``info['final_observation']`` /
+    ``info['_final_observation']`` appear on exactly those.  Philox stream position = ``_t_base`` (device) + ``_t``
+    (host, passed by value); ``commit()`` folds the host part into the device part: a captured hipGraph of an epoch
+    replays with the same by-value positions 0..T while the device part advances, so every epoch still draws fresh
+    numbers.
 
-    _support_envs = list(SYNTH_DIMS)
+    A subclass states class-level facts only: ``entry_point``, ``levels`` (id -> level, empty without levels),
+    ``obs_act_dims``, ``state_width`` (floats per row of ``state``; 0: no state matrix), ``default_horizon``, and for
+    the evaluator ``eval_kind_base`` (OSA_EVAL_ENV_* of level 0) and ``trace_state_floats`` (leading state floats in a
+    trace record)."""
+
+    entry_point: str
+    levels: dict[str, int] = {}
+    obs_act_dims = (60, 2)
+    state_width = 0
+    default_horizon = 1000
+    eval_kind_base = 0
+    trace_state_floats = 0
     need_auto_reset_wrapper = False
     need_time_limit_wrapper = False
     need_evaluation = False
-
-    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 1000,
-                 cost_p: float = 0.05, seed: int = 0, **_unused) -> None:
-        self._lib = _lib.load(require_gpu=True)
-        self._env_id = env_id
-        self._num_envs = int(num_envs)
-        self._device = torch.device(device)
-        self._obs_dim, self._act_dim = SYNTH_DIMS[env_id]
-        self._horizon, self._cost_p = int(horizon), float(cost_p)
-        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
-        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
-        self._seed = int(seed)
-        # Philox stream position = *_t_base (device) + _t (host, passed by value).  commit() folds the host part
-        # into the device part: a captured hipGraph of an epoch replays with the same by-value positions
-        # 0..T while the device part advances, so every epoch still draws fresh numbers
-        self._t = 0
-        self._t_base = torch.zeros(1, dtype=torch.int64, device=torch.device(device))
-        self._since_reset = 0  # all envs reset together -> truncation steps are known on the host
-        N, dev = self._num_envs, self._device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
-        self._final = torch.zeros(N, self._obs_dim, **f32)
-        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
-        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._flip = 0
-
-    num_envs = property(lambda self: self._num_envs)
-    observation_space = property(lambda self: self._observation_space)
-    action_space = property(lambda self: self._action_space)
-    max_episode_steps = property(lambda self: self._horizon)
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-
-    def _launch(self, obs, reset_only: int) -> None:
-        _lib.check(self._lib.osa_synth_env_step(
-            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
-            self._horizon, self._cost_p, _lib.ptr(self._steps), _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward),
-            _lib.ptr(self._cost), _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._final),
-            self._obs_dim, reset_only, _lib.stream_ptr()), 'osa_synth_env_step')
-        self._t += 1
-
-    def reset(self, seed: int | None = None, options: dict | None = None):
-        if seed is not None:
-            self.set_seed(seed)
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, 1)
-        self._since_reset = 0
-        return obs, {}
-
-    def step(self, action: torch.Tensor):
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, 0)
-        self._since_reset += 1
-        info: dict[str, Any] = {}
-        if self._since_reset % self._horizon == 0:  # every env truncates on this step
-            info['final_observation'] = self._final
-            info['_final_observation'] = self._trunc
-        return obs, self._reward, self._cost, self._term, self._trunc, info
-
-
     graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
+    _cost_p = 0.0
 
-    def commit(self) -> None:
-        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
-        self._t_base += self._t
-        self._t = 0
+    @classmethod
+    def dims(cls, env_id: str) -> tuple[int, int]:
+        """(obs_dim, act_dim) of a registered id; needs neither the library nor a GPU."""
+        return cls.obs_act_dims
 
-    def render(self):
-        return None
+    @classmethod
+    def eval_kind(cls, env_id: str) -> int:
+        """env_kind of osa_eval_episodes."""
+        return cls.eval_kind_base + cls.levels.get(env_id, 0)
 
-    def close(self) -> None:
-        return None
-
-
-@env_register
-class ReachVectorEnv:  # pylint: disable=too-many-instance-attributes
-    """Learnable synthetic vector CMDP in HBM (osa_reach_env_step): a point reaches resampled goals
-    (reward = progress, +1 per goal) past a hazard disc (cost 1 inside).  Observation/action dims of
-    SafetyPointGoal1 (60 / 2).  Used for learning-curve comparisons against the reference, which trains
-    on the CPU twin of this env kept with the test harness under oracle/."""
-
-    _support_envs = ['SynthReach-v0']
-    need_auto_reset_wrapper = False
-    need_time_limit_wrapper = False
-    need_evaluation = False
-
-    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 50,
+    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int | None = None,
                  seed: int = 0, **_unused) -> None:
         self._lib = _lib.load(require_gpu=True)
-        self._num_envs = int(num_envs)
-        self._device = torch.device(device)
-        self._obs_dim, self._act_dim = 60, 2
-        self._horizon = int(horizon)
-        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
-        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
-        self._seed = int(seed)
-        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
-        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
-        self._since_reset = 0
-        N, dev = self._num_envs, self._device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.state = torch.zeros(N, 8, **f32)  # p, goal, hazard, pad
-        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
-        self._final = torch.zeros(N, self._obs_dim, **f32)
-        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
-        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._flip = 0
-
-    num_envs = property(lambda self: self._num_envs)
-    observation_space = property(lambda self: self._observation_space)
-    action_space = property(lambda self: self._action_space)
-    max_episode_steps = property(lambda self: self._horizon)
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-
-    def _launch(self, obs, action, reset_only: int) -> None:
-        ld_a = action.stride(0) if action is not None else 0
-        _lib.check(self._lib.osa_reach_env_step(
-            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
-            self._horizon, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a, _lib.ptr(obs),
-            self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
-            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
-            _lib.stream_ptr()), 'osa_reach_env_step')
-        self._t += 1
-
-    def reset(self, seed: int | None = None, options: dict | None = None):
-        if seed is not None:
-            self.set_seed(seed)
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, None, 1)
-        self._since_reset = 0
-        return obs, {}
-
-    def step(self, action: torch.Tensor):
-        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
-            and action.stride(1) == 1
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, action, 0)
-        self._since_reset += 1
-        info: dict[str, Any] = {}
-        if self._since_reset % self._horizon == 0:  # every env truncates on this step
-            info['final_observation'] = self._final
-            info['_final_observation'] = self._trunc
-        return obs, self._reward, self._cost, self._term, self._trunc, info
-
-
-    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
-
-    def commit(self) -> None:
-        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
-        self._t_base += self._t
-        self._t = 0
-
-    def render(self):
-        return None
-
-    def close(self) -> None:
-        return None
-
-
-NAV_LEVELS = {'SynthNavGoal0-v0': 0, 'SynthNavGoal1-v0': 1, 'SynthNavGoal2-v0': 2}
-
-
-@env_register
-class NavGoalVectorEnv:  # pylint: disable=too-many-instance-attributes
-    """Lidar navigation vector CMDP in HBM (osa_nav_env_step), with the structure of the Safety-Gymnasium Goal
-    tasks: a point robot with heading and inertia drives to resampled goals (reward = progress, +1 per goal)
-    between hazard discs (cost 1 inside) and vases (cost on level 2), which it sees only through three egocentric
-    16-bin lidars.  Levels 0 / 1 / 2: 0 / 8 / 10 hazards, 0 / 1 / 10 vases.  Observation/action dims of
-    SafetyPointGoal (60 / 2).  ``state`` is the (N, 64) state matrix laid out as include/omnisafe_amd.h states."""
-
-    _support_envs = list(NAV_LEVELS)
-    need_auto_reset_wrapper = False
-    need_time_limit_wrapper = False
-    need_evaluation = False
-
-    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 1000,
-                 seed: int = 0, **_unused) -> None:
-        self._lib = _lib.load(require_gpu=True)
+        self._step_fn = getattr(self._lib, self.entry_point)
         self._env_id = env_id
-        self._level = NAV_LEVELS[env_id]
+        self._level = self.levels.get(env_id, 0)
         self._num_envs = int(num_envs)
         self._device = torch.device(device)
-        self._obs_dim, self._act_dim = 60, 2
-        self._horizon = int(horizon)
+        self._obs_dim, self._act_dim = self.dims(env_id)
+        self._horizon = int(self.default_horizon if horizon is None else horizon)
         self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
         self._action_space = Box(-1.0, 1.0, (self._act_dim,))
         self._seed = int(seed)
-        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
-        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
+        self._t = 0
         self._since_reset = 0
+        self._flip = 0
         N, dev = self._num_envs, self._device
         f32 = dict(dtype=torch.float32, device=dev)
-        self.state = torch.zeros(N, 64, **f32)
+        self._t_base = torch.zeros(1, dtype=torch.int64, device=dev)
+        if self.state_width:
+            self.state = torch.zeros(N, self.state_width, **f32)
         self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
         self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
         self._final = torch.zeros(N, self._obs_dim, **f32)
         self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
         self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._flip = 0
 
     num_envs = property(lambda self: self._num_envs)
     observation_space = property(lambda self: self._observation_space)
@@ -289,39 +134,42 @@ class NavGoalVectorEnv:  # pylint: disable=too-many-instance-attributes
     def set_seed(self, seed: int) -> None:
         self._seed = int(seed)
 
-    def _launch(self, obs, action, reset_only: int) -> None:
-        ld_a = action.stride(0) if action is not None else 0
-        _lib.check(self._lib.osa_nav_env_step(
+    def _middle_args(self, action) -> tuple:
+        """The entry point's arguments between ``horizon`` and ``obs``: [level,] state, steps, action, ld_action."""
+        ld_a = 0
+        if action is not None:
+            assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
+                and action.stride(1) == 1
+            ld_a = action.stride(0)
+        mid = (_lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a)
+        return (self._level, *mid) if self.levels else mid
+
+    def _launch(self, middle: tuple, reset_only: int) -> torch.Tensor:
+        self._flip ^= 1
+        obs = self._obs[self._flip]
+        _lib.check(self._step_fn(
             self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
-            self._horizon, self._level, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a,
-            _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
-            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
-            _lib.stream_ptr()), 'osa_nav_env_step')
+            self._horizon, *middle, _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost),
+            _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
+            _lib.stream_ptr()), self.entry_point)
         self._t += 1
+        return obs
 
     def reset(self, seed: int | None = None, options: dict | None = None):
         if seed is not None:
             self.set_seed(seed)
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, None, 1)
+        obs = self._launch(self._middle_args(None), 1)
         self._since_reset = 0
         return obs, {}
 
     def step(self, action: torch.Tensor):
-        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
-            and action.stride(1) == 1
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, action, 0)
+        obs = self._launch(self._middle_args(action), 0)
         self._since_reset += 1
         info: dict[str, Any] = {}
         if self._since_reset % self._horizon == 0:  # every env truncates on this step
             info['final_observation'] = self._final
             info['_final_observation'] = self._trunc
         return obs, self._reward, self._cost, self._term, self._trunc, info
-
-    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
 
     def commit(self) -> None:
         """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
@@ -335,11 +183,64 @@ class NavGoalVectorEnv:  # pylint: disable=too-many-instance-attributes
         return None
 
 
+@env_register
+class SynthVectorEnv(DeviceVectorEnv):
+    """Zero-cost synthetic vector CMDP living entirely in HBM (osa_synth_env_step)."""
+
+    _support_envs = list(SYNTH_DIMS)
+    entry_point = 'osa_synth_env_step'
+
+    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 1000,
+                 cost_p: float = 0.05, seed: int = 0, **_unused) -> None:
+        super().__init__(env_id, num_envs, device, horizon, seed)
+        self._cost_p = float(cost_p)
+
+    @classmethod
+    def dims(cls, env_id: str) -> tuple[int, int]:
+        return SYNTH_DIMS[env_id]
+
+    def _middle_args(self, action) -> tuple:  # noise: the action is not read
+        return self._cost_p, _lib.ptr(self._steps)
+
+
+@env_register
+class ReachVectorEnv(DeviceVectorEnv):
+    """Learnable synthetic vector CMDP in HBM (osa_reach_env_step): a point reaches resampled goals
+    (reward = progress, +1 per goal) past a hazard disc (cost 1 inside).  Observation/action dims of
+    SafetyPointGoal1 (60 / 2).  Used for learning-curve comparisons against the reference, which trains
+    on the CPU twin of this env kept with the test harness under oracle/."""
+
+    _support_envs = ['SynthReach-v0']
+    entry_point = 'osa_reach_env_step'
+    state_width = 8  # p, goal, hazard, pad
+    default_horizon = 50
+    eval_kind_base = 1
+    trace_state_floats = 6
+
+
+NAV_LEVELS = {'SynthNavGoal0-v0': 0, 'SynthNavGoal1-v0': 1, 'SynthNavGoal2-v0': 2}
+
+
+@env_register
+class NavGoalVectorEnv(DeviceVectorEnv):
+    """Lidar navigation vector CMDP in HBM (osa_nav_env_step), with the structure of the Safety-Gymnasium Goal
+    tasks: a point robot with heading and inertia drives to resampled goals (reward = progress, +1 per goal)
+    between hazard discs (cost 1 inside) and vases (cost on level 2), which it sees only through three egocentric
+    16-bin lidars.  Levels 0 / 1 / 2: 0 / 8 / 10 hazards, 0 / 1 / 10 vases.  Observation/action dims of
+    SafetyPointGoal (60 / 2).  ``state`` is the (N, 64) state matrix laid out as include/omnisafe_amd.h states."""
+
+    _support_envs = list(NAV_LEVELS)
+    entry_point = 'osa_nav_env_step'
+    levels = NAV_LEVELS
+    state_width = trace_state_floats = 64
+    eval_kind_base = 16
+
+
 CIRCLE_LEVELS = {'SynthNavCircle0-v0': 0, 'SynthNavCircle1-v0': 1, 'SynthNavCircle2-v0': 2}
 
 
 @env_register
-class NavCircleVectorEnv:  # pylint: disable=too-many-instance-attributes
+class NavCircleVectorEnv(DeviceVectorEnv):
     """Circle-running vector CMDP in HBM (osa_circle_env_step), with the structure of the Safety-Gymnasium Circle
     tasks: the point robot of SynthNavGoal is paid for running round the origin on the circle of radius 1
     (reward = tangential progress, damped away from the circle) and charged for leaving a corridor narrower than the
@@ -349,96 +250,19 @@ class NavCircleVectorEnv:  # pylint: disable=too-many-instance-attributes
     include/omnisafe_amd.h states."""
 
     _support_envs = list(CIRCLE_LEVELS)
-    need_auto_reset_wrapper = False
-    need_time_limit_wrapper = False
-    need_evaluation = False
-
-    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 500,
-                 seed: int = 0, **_unused) -> None:
-        self._lib = _lib.load(require_gpu=True)
-        self._env_id = env_id
-        self._level = CIRCLE_LEVELS[env_id]
-        self._num_envs = int(num_envs)
-        self._device = torch.device(device)
-        self._obs_dim, self._act_dim = 28, 2
-        self._horizon = int(horizon)
-        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
-        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
-        self._seed = int(seed)
-        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
-        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
-        self._since_reset = 0
-        N, dev = self._num_envs, self._device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.state = torch.zeros(N, 8, **f32)
-        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
-        self._final = torch.zeros(N, self._obs_dim, **f32)
-        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
-        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._flip = 0
-
-    num_envs = property(lambda self: self._num_envs)
-    observation_space = property(lambda self: self._observation_space)
-    action_space = property(lambda self: self._action_space)
-    max_episode_steps = property(lambda self: self._horizon)
-    level = property(lambda self: self._level)
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-
-    def _launch(self, obs, action, reset_only: int) -> None:
-        ld_a = action.stride(0) if action is not None else 0
-        _lib.check(self._lib.osa_circle_env_step(
-            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
-            self._horizon, self._level, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a,
-            _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
-            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
-            _lib.stream_ptr()), 'osa_circle_env_step')
-        self._t += 1
-
-    def reset(self, seed: int | None = None, options: dict | None = None):
-        if seed is not None:
-            self.set_seed(seed)
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, None, 1)
-        self._since_reset = 0
-        return obs, {}
-
-    def step(self, action: torch.Tensor):
-        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
-            and action.stride(1) == 1
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, action, 0)
-        self._since_reset += 1
-        info: dict[str, Any] = {}
-        if self._since_reset % self._horizon == 0:  # every env truncates on this step
-            info['final_observation'] = self._final
-            info['_final_observation'] = self._trunc
-        return obs, self._reward, self._cost, self._term, self._trunc, info
-
-    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
-
-    def commit(self) -> None:
-        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
-        self._t_base += self._t
-        self._t = 0
-
-    def render(self):
-        return None
-
-    def close(self) -> None:
-        return None
+    entry_point = 'osa_circle_env_step'
+    levels = CIRCLE_LEVELS
+    obs_act_dims = (28, 2)
+    state_width = trace_state_floats = 8
+    default_horizon = 500
+    eval_kind_base = 32
 
 
 CAR_GOAL_LEVELS = {'SynthNavCarGoal0-v0': 0, 'SynthNavCarGoal1-v0': 1, 'SynthNavCarGoal2-v0': 2}
 
 
 @env_register
-class NavCarGoalVectorEnv:  # pylint: disable=too-many-instance-attributes
+class NavCarGoalVectorEnv(DeviceVectorEnv):
     """SynthNavGoal driven by the Car (osa_car_goal_env_step), with the structure of the Safety-Gymnasium CarGoal
     tasks: the two actions command the left and the right wheel, whose speeds lag the commands; the forward speed is
     the wheels' mean and the turn rate their difference.  Goal, hazards, vases, reward, costs and levels are
@@ -448,96 +272,18 @@ class NavCarGoalVectorEnv:  # pylint: disable=too-many-instance-attributes
     include/omnisafe_amd.h states."""
 
     _support_envs = list(CAR_GOAL_LEVELS)
-    need_auto_reset_wrapper = False
-    need_time_limit_wrapper = False
-    need_evaluation = False
-
-    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 1000,
-                 seed: int = 0, **_unused) -> None:
-        self._lib = _lib.load(require_gpu=True)
-        self._env_id = env_id
-        self._level = CAR_GOAL_LEVELS[env_id]
-        self._num_envs = int(num_envs)
-        self._device = torch.device(device)
-        self._obs_dim, self._act_dim = 72, 2
-        self._horizon = int(horizon)
-        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
-        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
-        self._seed = int(seed)
-        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
-        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
-        self._since_reset = 0
-        N, dev = self._num_envs, self._device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.state = torch.zeros(N, 64, **f32)
-        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
-        self._final = torch.zeros(N, self._obs_dim, **f32)
-        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
-        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._flip = 0
-
-    num_envs = property(lambda self: self._num_envs)
-    observation_space = property(lambda self: self._observation_space)
-    action_space = property(lambda self: self._action_space)
-    max_episode_steps = property(lambda self: self._horizon)
-    level = property(lambda self: self._level)
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-
-    def _launch(self, obs, action, reset_only: int) -> None:
-        ld_a = action.stride(0) if action is not None else 0
-        _lib.check(self._lib.osa_car_goal_env_step(
-            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
-            self._horizon, self._level, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a,
-            _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
-            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
-            _lib.stream_ptr()), 'osa_car_goal_env_step')
-        self._t += 1
-
-    def reset(self, seed: int | None = None, options: dict | None = None):
-        if seed is not None:
-            self.set_seed(seed)
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, None, 1)
-        self._since_reset = 0
-        return obs, {}
-
-    def step(self, action: torch.Tensor):
-        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
-            and action.stride(1) == 1
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, action, 0)
-        self._since_reset += 1
-        info: dict[str, Any] = {}
-        if self._since_reset % self._horizon == 0:  # every env truncates on this step
-            info['final_observation'] = self._final
-            info['_final_observation'] = self._trunc
-        return obs, self._reward, self._cost, self._term, self._trunc, info
-
-    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
-
-    def commit(self) -> None:
-        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
-        self._t_base += self._t
-        self._t = 0
-
-    def render(self):
-        return None
-
-    def close(self) -> None:
-        return None
+    entry_point = 'osa_car_goal_env_step'
+    levels = CAR_GOAL_LEVELS
+    obs_act_dims = (72, 2)
+    state_width = trace_state_floats = 64
+    eval_kind_base = 48
 
 
 CAR_CIRCLE_LEVELS = {'SynthNavCarCircle0-v0': 0, 'SynthNavCarCircle1-v0': 1, 'SynthNavCarCircle2-v0': 2}
 
 
 @env_register
-class NavCarCircleVectorEnv:  # pylint: disable=too-many-instance-attributes
+class NavCarCircleVectorEnv(DeviceVectorEnv):
     """SynthNavCircle driven by the Car (osa_car_circle_env_step), with the structure of the Safety-Gymnasium
     CarCircle tasks: the two actions command the left and the right wheel (see :class:`NavCarGoalVectorEnv`); reward,
     corridor cost, levels and reset are SynthNavCircle's (the same seed gives the same start).  Observation/action
@@ -545,86 +291,9 @@ class NavCarCircleVectorEnv:  # pylint: disable=too-many-instance-attributes
     state matrix laid out as include/omnisafe_amd.h states."""
 
     _support_envs = list(CAR_CIRCLE_LEVELS)
-    need_auto_reset_wrapper = False
-    need_time_limit_wrapper = False
-    need_evaluation = False
-
-    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int = 500,
-                 seed: int = 0, **_unused) -> None:
-        self._lib = _lib.load(require_gpu=True)
-        self._env_id = env_id
-        self._level = CAR_CIRCLE_LEVELS[env_id]
-        self._num_envs = int(num_envs)
-        self._device = torch.device(device)
-        self._obs_dim, self._act_dim = 40, 2
-        self._horizon = int(horizon)
-        self._observation_space = Box(-np.inf, np.inf, (self._obs_dim,))
-        self._action_space = Box(-1.0, 1.0, (self._act_dim,))
-        self._seed = int(seed)
-        self._t = 0            # host part of the Philox stream position (see SynthVectorEnv)
-        self._t_base = torch.zeros(1, dtype=torch.int64, device=self._device)
-        self._since_reset = 0
-        N, dev = self._num_envs, self._device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.state = torch.zeros(N, 12, **f32)
-        self._steps = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._obs = [torch.empty(N, self._obs_dim, **f32) for _ in range(2)]
-        self._final = torch.zeros(N, self._obs_dim, **f32)
-        self._reward, self._cost = torch.empty(N, **f32), torch.empty(N, **f32)
-        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._flip = 0
-
-    num_envs = property(lambda self: self._num_envs)
-    observation_space = property(lambda self: self._observation_space)
-    action_space = property(lambda self: self._action_space)
-    max_episode_steps = property(lambda self: self._horizon)
-    level = property(lambda self: self._level)
-
-    def set_seed(self, seed: int) -> None:
-        self._seed = int(seed)
-
-    def _launch(self, obs, action, reset_only: int) -> None:
-        ld_a = action.stride(0) if action is not None else 0
-        _lib.check(self._lib.osa_car_circle_env_step(
-            self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
-            self._horizon, self._level, _lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a,
-            _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost), _lib.ptr(self._term),
-            _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
-            _lib.stream_ptr()), 'osa_car_circle_env_step')
-        self._t += 1
-
-    def reset(self, seed: int | None = None, options: dict | None = None):
-        if seed is not None:
-            self.set_seed(seed)
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, None, 1)
-        self._since_reset = 0
-        return obs, {}
-
-    def step(self, action: torch.Tensor):
-        assert action.dtype == torch.float32 and action.shape == (self._num_envs, self._act_dim) \
-            and action.stride(1) == 1
-        self._flip ^= 1
-        obs = self._obs[self._flip]
-        self._launch(obs, action, 0)
-        self._since_reset += 1
-        info: dict[str, Any] = {}
-        if self._since_reset % self._horizon == 0:  # every env truncates on this step
-            info['final_observation'] = self._final
-            info['_final_observation'] = self._trunc
-        return obs, self._reward, self._cost, self._term, self._trunc, info
-
-    graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
-
-    def commit(self) -> None:
-        """Fold the host part of the stream position into the device part (end of an epoch; capturable)."""
-        self._t_base += self._t
-        self._t = 0
-
-    def render(self):
-        return None
-
-    def close(self) -> None:
-        return None
+    entry_point = 'osa_car_circle_env_step'
+    levels = CAR_CIRCLE_LEVELS
+    obs_act_dims = (40, 2)
+    state_width = trace_state_floats = 12
+    default_horizon = 500
+    eval_kind_base = 64

@@ -38,22 +38,13 @@ from .normalizer import Normalizer
 from .spaces import Box
 
 TIME_LIMIT = 1000  # evaluator.py:179-180
-DEVICE_ENVS = (envs_mod.SynthVectorEnv, envs_mod.ReachVectorEnv, envs_mod.NavGoalVectorEnv,
-               envs_mod.NavCircleVectorEnv, envs_mod.NavCarGoalVectorEnv, envs_mod.NavCarCircleVectorEnv)
+DEVICE_ENVS = tuple(envs_mod.DeviceVectorEnv.__subclasses__())
 
 
 def _env_kind(env) -> int:
-    """env_kind of osa_eval_episodes: OSA_EVAL_ENV_SYNTH / _REACH / _NAV0 + level / _CIRCLE0 + level / _CARGOAL0 +
-    level / _CARCIRCLE0 + level."""
-    if isinstance(env, envs_mod.NavGoalVectorEnv):
-        return 16 + env.level
-    if isinstance(env, envs_mod.NavCircleVectorEnv):
-        return 32 + env.level
-    if isinstance(env, envs_mod.NavCarGoalVectorEnv):
-        return 48 + env.level
-    if isinstance(env, envs_mod.NavCarCircleVectorEnv):
-        return 64 + env.level
-    return 1 if isinstance(env, envs_mod.ReachVectorEnv) else 0
+    """env_kind of osa_eval_episodes (OSA_EVAL_ENV_* of the family + level); an env of the caller's own counts as
+    OSA_EVAL_ENV_SYNTH, whose trace record has no state floats."""
+    return env.eval_kind(env._env_id) if isinstance(env, DEVICE_ENVS) else 0
 
 
 class Evaluator:  # pylint: disable=too-many-instance-attributes
@@ -99,16 +90,9 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     def _env_dims(self) -> tuple[int, int]:
         if self._user_env is not None:
             return (int(self._user_env.observation_space.shape[0]), int(self._user_env.action_space.shape[0]))
-        if self._env_id == 'SynthReach-v0' or self._env_id in envs_mod.NAV_LEVELS:
-            return 60, 2
-        if self._env_id in envs_mod.CIRCLE_LEVELS:
-            return 28, 2
-        if self._env_id in envs_mod.CAR_GOAL_LEVELS:
-            return 72, 2
-        if self._env_id in envs_mod.CAR_CIRCLE_LEVELS:
-            return 40, 2
-        if self._env_id in envs_mod.SYNTH_DIMS:
-            return envs_mod.SYNTH_DIMS[self._env_id]
+        cls = envs_mod.ENV_REGISTRY.get(self._env_id)
+        if cls in DEVICE_ENVS:
+            return cls.dims(self._env_id)
         env = envs_mod.make(self._env_id, num_envs=1, device=self._device, **self._env_cfgs)
         dims = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
         env.close()
@@ -185,7 +169,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             kind, K, obs_dim, act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(nm._mean) if nm else None,
             _lib.ptr(nm._std) if nm else None, _lib.ptr(nm._count) if nm else None,
             float(nm._clip_value) if nm else 0.0, _lib.ptr(lo), _lib.ptr(hi), -1.0, 1.0,
-            env._seed & 0xFFFFFFFFFFFFFFFF, horizon, float(getattr(env, '_cost_p', 0.0)), horizon,
+            env._seed & 0xFFFFFFFFFFFFFFFF, horizon, env._cost_p, horizon,
             int(self._saute), self._budget if self._saute else 0.0, self._saute_gamma if self._saute else 0.0,
             int(self._early_terminated), self._cost_limit, cost_criteria, _lib.ptr(ret), _lib.ptr(cost),
             _lib.ptr(length), _lib.ptr(tr), _lib.stream_ptr()), 'osa_eval_episodes')
@@ -217,10 +201,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         lo, hi = self._scale_bounds(env)
         device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS
         max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
-        state_w = 6 if isinstance(env, envs_mod.ReachVectorEnv) else (
-            64 if isinstance(env, (envs_mod.NavGoalVectorEnv, envs_mod.NavCarGoalVectorEnv)) else (
-                8 if isinstance(env, envs_mod.NavCircleVectorEnv) else (
-                    12 if isinstance(env, envs_mod.NavCarCircleVectorEnv) else 0)))  # state floats of a trace record
+        state_w = getattr(env, 'trace_state_floats', 0)  # state floats of a trace record
         f64 = dict(dtype=torch.float64, device=dev)
         ret, cost = torch.zeros(K, **f64), torch.zeros(K, **f64)
         length = torch.zeros(K, dtype=torch.int32, device=dev)

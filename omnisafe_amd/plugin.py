@@ -83,30 +83,11 @@ def install(algorithms: tuple[str, ...] | None = None) -> list[str]:
     # make the synthetic ids valid env ids for the reference's config checks (envs/core.py:362-386)
     reg = ref_env_core.ENV_REGISTRY
     known = set(reg.support_envs())
-    new_ids = [e for e in amd_envs.SYNTH_DIMS if e not in known]
-    if new_ids:
-        reg._class['OmnisafeAmdSynthVectorEnv'] = amd_envs.SynthVectorEnv  # noqa: SLF001
-        reg._support_envs['OmnisafeAmdSynthVectorEnv'] = new_ids  # noqa: SLF001
-    reach_ids = [e for e in amd_envs.ReachVectorEnv._support_envs if e not in known]  # noqa: SLF001
-    if reach_ids:
-        reg._class['OmnisafeAmdReachVectorEnv'] = amd_envs.ReachVectorEnv  # noqa: SLF001
-        reg._support_envs['OmnisafeAmdReachVectorEnv'] = reach_ids  # noqa: SLF001
-    nav_ids = [e for e in amd_envs.NavGoalVectorEnv._support_envs if e not in known]  # noqa: SLF001
-    if nav_ids:
-        reg._class['OmnisafeAmdNavGoalVectorEnv'] = amd_envs.NavGoalVectorEnv  # noqa: SLF001
-        reg._support_envs['OmnisafeAmdNavGoalVectorEnv'] = nav_ids  # noqa: SLF001
-    circle_ids = [e for e in amd_envs.NavCircleVectorEnv._support_envs if e not in known]  # noqa: SLF001
-    if circle_ids:
-        reg._class['OmnisafeAmdNavCircleVectorEnv'] = amd_envs.NavCircleVectorEnv  # noqa: SLF001
-        reg._support_envs['OmnisafeAmdNavCircleVectorEnv'] = circle_ids  # noqa: SLF001
-    car_goal_ids = [e for e in amd_envs.NavCarGoalVectorEnv._support_envs if e not in known]  # noqa: SLF001
-    if car_goal_ids:
-        reg._class['OmnisafeAmdNavCarGoalVectorEnv'] = amd_envs.NavCarGoalVectorEnv  # noqa: SLF001
-        reg._support_envs['OmnisafeAmdNavCarGoalVectorEnv'] = car_goal_ids  # noqa: SLF001
-    car_circle_ids = [e for e in amd_envs.NavCarCircleVectorEnv._support_envs if e not in known]  # noqa: SLF001
-    if car_circle_ids:
-        reg._class['OmnisafeAmdNavCarCircleVectorEnv'] = amd_envs.NavCarCircleVectorEnv  # noqa: SLF001
-        reg._support_envs['OmnisafeAmdNavCarCircleVectorEnv'] = car_circle_ids  # noqa: SLF001
+    for cls in amd_envs.DeviceVectorEnv.__subclasses__():
+        new_ids = [e for e in cls._support_envs if e not in known]  # noqa: SLF001
+        if new_ids:
+            reg._class['OmnisafeAmd' + cls.__name__] = cls  # noqa: SLF001
+            reg._support_envs['OmnisafeAmd' + cls.__name__] = new_ids  # noqa: SLF001
     del omnisafe
     return swapped
 
