@@ -878,6 +878,17 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     }
 
     PTICK(2);
+    f32x4 w3f0[HT], w3f1[HT];
+    if constexpr (SO) {
+      // the small-output backward's two W3 rows: all eight reads in flight before the prefetch issue and the dO
+      // tiles (next to their use, every pair of them was a round trip of its own: four per step)
+#pragma unroll
+      for (int t = 0; t < HT; ++t) {
+        w3f0[t] = *reinterpret_cast<const f32x4*>(sW3 + 16 * t + 4 * g);
+        w3f1[t] = *reinterpret_cast<const f32x4*>(sW3 + PSLD + 16 * t + 4 * g);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     fetch_s(row_nxt, cur);  // the loss has consumed the per-sample scalars: next chunk's, in place
     cur.valid = pos_ok(cidx + 1);
     row_nxt = row_of(cidx + 2);
@@ -928,8 +939,14 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
       load_w2t(0, wt[0]);  // first W2^T block, in flight meanwhile
 #pragma unroll
       for (int t = 0; t < HT; ++t) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(sW3 + 16 * t + 4 * g);
-        const f32x4 w1 = *reinterpret_cast<const f32x4*>(sW3 + PSLD + 16 * t + 4 * g);
+        f32x4 w0, w1;
+        if constexpr (SO) {
+          w0 = w3f0[t];
+          w1 = w3f1[t];
+        } else {
+          w0 = *reinterpret_cast<const f32x4*>(sW3 + 16 * t + 4 * g);
+          w1 = *reinterpret_cast<const f32x4*>(sW3 + PSLD + 16 * t + 4 * g);
+        }
         z2[t] = w0 * d0 + w1 * d1;
       }
     } else {
@@ -1110,38 +1127,81 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
       xbase = a.dp_slabs + (((long)((mb - a.mb0) & 1) * 3 + net) * a.dp_world + (chunked ? crank * cw : 0)) * XS;
       xs4 = reinterpret_cast<f32x4*>(xbase + (long)(chunked ? cchunk : rk) * XS);
     }
+    // Plain pass: the actor has no L2 term (c2 == 0: g + w * 0 is g up to the sign of a zero) and its sum of squared
+    // parameters is stored nowhere -- st[4 + net] belongs to the critics -- so the block that ends the launch skips
+    // both: ONE block-uniform branch at the phase boundary around the terms in w, the squared norm of the gradient in
+    // common code behind it (in-place updates of g inside the branch: no copies where the paths join; two whole
+    // bodies of this phase under an if / else cost 18 register-pair moves on the actor).  The cooperative and the
+    // gradient-only modes publish psq in their slabs and keep the one fused loop.
+    constexpr bool ACTOR_PSQ = COOP || DPS;
     f32x4 acc_g = {0.f, 0.f, 0.f, 0.f}, acc_p = {0.f, 0.f, 0.f, 0.f};
+    float psq = 0.f;
+    if constexpr (ACTOR_PSQ) {
 #pragma unroll
-    for (int ti = 0; ti < HT; ++ti) {
-      const f32x4 w = w2r[ti];
-      g2[ti] = g2[ti] + w * c2;
-      if constexpr (coop && !P2P) xs4[ti * 256 + tid] = g2[ti];  // (P2P: the own gradient stays in registers)
-      acc_p = acc_p + w * w;
-      acc_g = acc_g + g2[ti] * g2[ti];
-    }
+      for (int ti = 0; ti < HT; ++ti) {
+        const f32x4 w = w2r[ti];
+        g2[ti] = g2[ti] + w * c2;
+        if constexpr (coop && !P2P) xs4[ti * 256 + tid] = g2[ti];  // (P2P: the own gradient stays in registers)
+        acc_p = acc_p + w * w;
+        acc_g = acc_g + g2[ti] * g2[ti];
+      }
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      const f32x4 w = w1r[kb];
-      g1[kb] = g1[kb] + w * c2;
-      if constexpr (coop && !P2P) xs4[(HT + kb) * 256 + tid] = g1[kb];
-      acc_p = acc_p + w * w;
-      acc_g = acc_g + g1[kb] * g1[kb];
-    }
+      for (int kb = 0; kb < KB; ++kb) {
+        const f32x4 w = w1r[kb];
+        g1[kb] = g1[kb] + w * c2;
+        if constexpr (coop && !P2P) xs4[(HT + kb) * 256 + tid] = g1[kb];
+        acc_p = acc_p + w * w;
+        acc_g = acc_g + g1[kb] * g1[kb];
+      }
 #pragma unroll
-    for (int o = 0; o < OT; ++o) {
-      const f32x4 w = w3r[o];
-      g3[o] = g3[o] + w * c2;
-      if constexpr (coop && !P2P) xs4[(HT + KB + o) * 256 + tid] = g3[o];
-      acc_p = acc_p + w * w;
-      acc_g = acc_g + g3[o] * g3[o];
+      for (int o = 0; o < OT; ++o) {
+        const f32x4 w = w3r[o];
+        g3[o] = g3[o] + w * c2;
+        if constexpr (coop && !P2P) xs4[(HT + KB + o) * 256 + tid] = g3[o];
+        acc_p = acc_p + w * w;
+        acc_g = acc_g + g3[o] * g3[o];
+      }
+      psq = (acc_p.x + acc_p.y) + (acc_p.z + acc_p.w);
+      if (boff >= 0) {
+        gb += c2 * wb;
+        psq += wb * wb;
+      }
+    } else {
+      if (critic) {
+#pragma unroll
+        for (int ti = 0; ti < HT; ++ti) {
+          const f32x4 w = w2r[ti];
+          g2[ti] = g2[ti] + w * c2;
+          acc_p = acc_p + w * w;
+        }
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+          const f32x4 w = w1r[kb];
+          g1[kb] = g1[kb] + w * c2;
+          acc_p = acc_p + w * w;
+        }
+#pragma unroll
+        for (int o = 0; o < OT; ++o) {
+          const f32x4 w = w3r[o];
+          g3[o] = g3[o] + w * c2;
+          acc_p = acc_p + w * w;
+        }
+        psq = (acc_p.x + acc_p.y) + (acc_p.z + acc_p.w);
+        if (boff >= 0) {
+          gb += c2 * wb;
+          psq += wb * wb;
+        }
+        psq = osa_wave_sum_dpp(psq);
+      }
+#pragma unroll
+      for (int ti = 0; ti < HT; ++ti) acc_g = acc_g + g2[ti] * g2[ti];
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) acc_g = acc_g + g1[kb] * g1[kb];
+#pragma unroll
+      for (int o = 0; o < OT; ++o) acc_g = acc_g + g3[o] * g3[o];
     }
     float gsq = (acc_g.x + acc_g.y) + (acc_g.z + acc_g.w);
-    float psq = (acc_p.x + acc_p.y) + (acc_p.z + acc_p.w);
-    if (boff >= 0) {
-      gb += c2 * wb;
-      psq += wb * wb;
-      gsq += gb * gb;
-    }
+    if (boff >= 0) gsq += gb * gb;
     if constexpr (coop && !P2P) reinterpret_cast<float*>(xs4)[NT * 1024 + tid] = (boff >= 0) ? gb : 0.f;
     if constexpr (P2P) {
       // the same tiles into every OTHER rank's buffer (posted writes: over xGMI where the peer is another device);
@@ -1161,7 +1221,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     }
     // ---- block reduction of (gsq, psq, loss, ratio): wave shuffles, then a fixed-order sum
     gsq = osa_wave_sum_dpp(gsq);
-    psq = osa_wave_sum_dpp(psq);
+    if constexpr (ACTOR_PSQ) psq = osa_wave_sum_dpp(psq);  // (plain pass: reduced above, by the critics only)
     loss_part = osa_wave_sum_dpp(loss_part);
     ratio_part = osa_wave_sum_dpp(ratio_part);
     if (lane == 0) {
