@@ -1,0 +1,533 @@
+"""A plain float64 statement of ONE optimiser step of PolicyGradient._update -- a module, not a test (as
+tests/rollout_twin.py and tests/nav_twin.py are for the rollout side).
+
+What the 64-row step kernels (csrc/ppo_pass_body.h through osa_ppo_pass(_ext), the per-step kernel of
+csrc/mlp_kernels.hip through osa_ppo_minibatch(_ext)) compute, written as the obvious formula on CPU torch with
+autograd for the backward, nothing of the kernels' schedule:
+
+  networks   three tanh MLPs obs -> 64 -> 64 -> {act_dim | 1 | 1}; the actor is Normal(mean(obs), exp(log_std)) with a
+             state-independent log_std (reference: models/actor/gaussian_learning_actor.py, models/critic/v_critic.py)
+  actor      _update_actor (algorithms/on_policy/base/policy_gradient.py:514-524) on the surrogate advantage
+             (adv_r - lam adv_c) / (1 + lam) (naive_lagrange/ppo_lag.py:101-102);
+             loss_kind 0: -mean(min(r A, clamp(r, 1 - clip, 1 + clip) A)) (base/ppo.py:66-78),
+             loss_kind 1: -mean(r A) (policy_gradient.py:574-578);  - entropy_coef Normal.entropy().mean()
+  extension  osa_surrogate_ext: KL(pi_theta || pi_old) per sample, the trust mask 1[KL <= eta] with the reference's
+             (B, 1) x (B,) broadcast (first_order/focops.py:103-108: the surrogate term sees the minibatch MEAN of the
+             mask), ratio_scale, and P3O's kappa relu(mean(r adv_c) + excess) (penalty_function/p3o.py:76-84)
+  critics    _update_reward_critic / _update_cost_critic (policy_gradient.py:428-445, 468-485): mse_loss
+             + critic_norm_coef sum(p^2) when use_critic_norm
+  clip       clip_grad_norm_ per network: the norm over THAT network's gradient, L2 term included; factor
+             min(1, max_grad_norm / (norm + 1e-6))
+  Adam       torch.optim.Adam's update for given m, v and step count t (the count AFTER the step):
+             m' = b1 m + (1 - b1) g,  v' = b2 v + (1 - b2) g^2,  p' = p - lr / (1 - b1^t) m' / (sqrt(v') / sqrt(1 - b2^t) + eps)
+  ragged     a last minibatch of n < B rows is a minibatch of n rows: every mean is over n
+
+`step(..., dtype=torch.float32)` runs the identical code in float32.  That run is the measuring stick of the GPU
+tests' tolerances (what ONE other float32 evaluation of the same formula loses), not a second reference.
+
+`make_case` builds seeded inputs (numpy.random.RandomState streams only) and arranges that every branch of the losses
+carries rows; `check_coverage` asserts it on the CPU so that no case can pass vacuously.  Every float32 input --
+parameters, moments, data, hyper-parameters, the multiplier -- is rounded to float32 first and widened afterwards: the
+twin and the kernels see the same numbers.
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+H = 64
+NETS = ('actor', 'reward_critic', 'cost_critic')
+F32 = np.float32
+
+
+def tensor_shapes(net: str, obs_dim: int, act_dim: int) -> 'OrderedDict[str, tuple]':
+    """The reference's named_parameters of one network, in its order (log_std first: a module's own parameters come
+    before its sub-modules')."""
+    out = act_dim if net == 'actor' else 1
+    pre = 'mean' if net == 'actor' else 'critic_0'
+    sh = OrderedDict()
+    if net == 'actor':
+        sh['log_std'] = (act_dim,)
+    for j, (o, i) in zip((0, 2, 4), ((H, obs_dim), (H, H), (out, H))):
+        sh[f'{pre}.{j}.weight'] = (o, i)
+        sh[f'{pre}.{j}.bias'] = (o,)
+    return sh
+
+
+def _f32(x) -> float:
+    """A hyper-parameter as the kernels receive it: rounded to float32, then widened."""
+    return float(F32(x))
+
+
+def _mlp(p: dict, pre: str, x: torch.Tensor) -> torch.Tensor:
+    h = torch.tanh(x @ p[f'{pre}.0.weight'].T + p[f'{pre}.0.bias'])
+    h = torch.tanh(h @ p[f'{pre}.2.weight'].T + p[f'{pre}.2.bias'])
+    return h @ p[f'{pre}.4.weight'].T + p[f'{pre}.4.bias']
+
+
+DEFAULT_HP = dict(clip=0.2, entropy_coef=0.0, critic_norm_coef=0.001, max_grad_norm=40.0, lr_actor=3e-4, lr_critic=3e-4,
+                  beta1=0.9, beta2=0.999, adam_eps=1e-8, use_critic_norm=1, use_max_grad_norm=1)
+
+
+def bias_corrections(lr: float, b1: float, b2: float, t: int) -> tuple:
+    """Adam's two bias-correction factors at step count t, float64: lr / (1 - b1^t) and 1 / sqrt(1 - b2^t)."""
+    return lr / (1.0 - b1 ** t), 1.0 / math.sqrt(1.0 - b2 ** t)
+
+
+def adam(p, m, v, g, lr: float, b1: float, b2: float, eps: float, t: int):
+    """torch.optim.Adam (amsgrad off, no weight decay) for one tensor; t = the step count after this step."""
+    m1 = b1 * m + (1.0 - b1) * g
+    v1 = b2 * v + (1.0 - b2) * g * g
+    step_size, inv_bc2_sqrt = bias_corrections(lr, b1, b2, t)
+    return p - step_size * m1 / (torch.sqrt(v1) * inv_bc2_sqrt + eps), m1, v1
+
+
+def step(state: dict, batch: dict, hp: dict, lam: float, loss_kind: int, ext: dict | None = None,
+         dtype=torch.float64, nets=NETS) -> dict:
+    """One optimiser step of the networks in `nets` on the rows of `batch`.
+
+    state   {'params' | 'm' | 'v': {net: {tensor name: array}}, 't': {net: steps taken so far}}
+    batch   obs (n, D), act (n, A), logp, target_value_r, target_value_c, adv_r, adv_c (n,); with an extension that
+            looks at the behaviour policy also old_mean (n, A) and old_log_std (A,)
+    hp      the fields of osa_ppo_hparams (DEFAULT_HP for what is missing)
+    ext     None or the scalar fields of osa_surrogate_ext
+
+    Returns {net: {...}} with the losses, (actor) mean ratio / entropy / penalty, sum p^2, the UNCLIPPED gradient per
+    reference tensor, its norm, the clip factor, p', m', v', the new step count and the two bias-correction factors;
+    the actor's entry also carries the per-row ratio, surrogate advantage, KL and mask (for coverage checks)."""
+    hp = dict(DEFAULT_HP, **hp)
+    f = {k: _f32(hp[k]) for k in ('clip', 'entropy_coef', 'critic_norm_coef', 'max_grad_norm', 'lr_actor',
+                                  'lr_critic', 'beta1', 'beta2', 'adam_eps')}
+    lam = _f32(lam)
+    as_t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)  # noqa: E731
+    b = {k: as_t(v) for k, v in batch.items()}
+    out = {}
+    for net in nets:
+        p = OrderedDict((k, as_t(v).clone().requires_grad_(True)) for k, v in state['params'][net].items())
+        r = {}
+        if net == 'actor':
+            dist = torch.distributions.Normal(_mlp(p, 'mean', b['obs']), torch.exp(p['log_std']))
+            logp_ = dist.log_prob(b['act']).sum(-1)
+            ratio = torch.exp(logp_ - b['logp'])
+            adv = (b['adv_r'] - lam * b['adv_c']) / (1.0 + lam)
+            if loss_kind == 0:
+                surr = -torch.min(ratio * adv, torch.clamp(ratio, 1.0 - f['clip'], 1.0 + f['clip']) * adv)
+            else:
+                surr = -(ratio * adv)
+            penalty = torch.zeros((), dtype=dtype)
+            kl = torch.zeros(len(ratio), 1, dtype=dtype)
+            mask = torch.ones(len(ratio), 1, dtype=dtype)
+            if ext is None:
+                loss = surr.mean()
+            else:
+                e = {k: _f32(ext.get(k, d)) for k, d in (('kl_coef', 0.0), ('kl_mask_eta', -1.0), ('ratio_scale', 1.0),
+                                                         ('cost_kappa', 0.0), ('cost_excess', 0.0))}
+                if e['kl_coef'] != 0.0 or e['kl_mask_eta'] >= 0.0:
+                    old = torch.distributions.Normal(b['old_mean'], torch.exp(b['old_log_std']))
+                    kl = torch.distributions.kl_divergence(dist, old).sum(-1, keepdim=True)
+                if e['kl_mask_eta'] >= 0.0:
+                    mask = (kl.detach() <= e['kl_mask_eta']).to(dtype)
+                # (n, 1) KL and mask against the (n,) surrogate: an (n, n) matrix, as the reference forms it
+                loss = ((e['kl_coef'] * kl + e['ratio_scale'] * surr) * mask).mean()
+                if e['cost_kappa'] > 0.0:
+                    penalty = e['cost_kappa'] * torch.relu((ratio * b['adv_c']).mean() + e['cost_excess'])
+            entropy = dist.entropy().mean()
+            loss = loss - f['entropy_coef'] * entropy
+            total = loss + penalty
+            r.update(loss=loss.detach(), ratio_mean=ratio.mean().detach(), entropy=entropy.detach(),
+                     penalty=penalty.detach(), ratio=ratio.detach(), adv=adv.detach(), kl=kl.detach()[:, 0],
+                     mask=mask[:, 0], cost_surrogate=(ratio * b['adv_c']).mean().detach())
+            lr = f['lr_actor']
+        else:
+            v = torch.squeeze(_mlp(p, 'critic_0', b['obs']), -1)
+            mse = torch.nn.functional.mse_loss(v, b['target_value_r' if net == 'reward_critic' else 'target_value_c'])
+            total = mse
+            if hp['use_critic_norm']:
+                for w in p.values():
+                    total = total + w.pow(2).sum() * f['critic_norm_coef']
+            r.update(loss=total.detach(), mse=mse.detach(), value=v.detach())
+            lr = f['lr_critic']
+        grads = torch.autograd.grad(total, list(p.values()))
+        gnorm = torch.sqrt(sum((g * g).sum() for g in grads))
+        coef = torch.clamp(f['max_grad_norm'] / (gnorm + 1e-6), max=1.0) if hp['use_max_grad_norm'] else torch.ones(
+            (), dtype=dtype)
+        t = int(state['t'][net]) + 1
+        new_p, new_m, new_v = OrderedDict(), OrderedDict(), OrderedDict()
+        for (k, w), g in zip(p.items(), grads):
+            new_p[k], new_m[k], new_v[k] = adam(w.detach(), as_t(state['m'][net][k]), as_t(state['v'][net][k]), g * coef,
+                                                lr, f['beta1'], f['beta2'], f['adam_eps'], t)
+        ss, ib = bias_corrections(lr, f['beta1'], f['beta2'], t)
+        r.update(psq=sum(w.detach().pow(2).sum() for w in p.values()), grads=OrderedDict(zip(p.keys(), grads)),
+                 gnorm=gnorm, coef=coef, p=new_p, m=new_m, v=new_v, t=t, step_size=ss, inv_bc2_sqrt=ib)
+        out[net] = r
+    return out
+
+
+def advance(state: dict, res: dict) -> dict:
+    """The state after the step whose result is `res` (networks outside `res` keep theirs)."""
+    new = {k: dict(state[k]) for k in ('params', 'm', 'v', 't')}
+    for net, r in res.items():
+        new['params'][net], new['m'][net], new['v'][net], new['t'][net] = r['p'], r['m'], r['v'], r['t']
+    return new
+
+
+def minibatches(M: int, B: int) -> list:
+    return [(s, min(B, M - s)) for s in range(0, M, B)]
+
+
+def rows(data: dict, idx) -> dict:
+    """The rows `idx` of the per-sample arrays (old_log_std is per dimension)."""
+    return {k: (v if k == 'old_log_std' else np.asarray(v)[np.asarray(idx)]) for k, v in data.items()}
+
+
+def case_nets(case: dict) -> tuple:
+    """The networks a case updates: PPOUpdater's nets mask."""
+    nets = ('actor',) if case['update_actor'] else ()
+    if case['update_critics']:
+        nets += ('reward_critic', 'cost_critic') if case['use_cost'] else ('reward_critic',)
+    return nets
+
+
+def case_step(case: dict, state: dict, k: int, dtype=torch.float64, order=None) -> dict:
+    """Minibatch k of the case's pass, taken from `state` (`order`: its rows in another order -- the same step)."""
+    s, n = minibatches(case['M'], case['B'])[k]
+    idx = case['perm'][s:s + n]
+    return step(state, rows(case['data'], idx if order is None else idx[order]), case['hp'], case['lam'],
+                case['loss_kind'], case['ext'], dtype, case_nets(case))
+
+
+def run_pass(case: dict, dtype=torch.float64, state: dict | None = None) -> tuple:
+    """The whole pass: ceil(M / B) dependent steps over the case's permutation -> ([step results], final state)."""
+    state = case['state'] if state is None else state
+    res = []
+    for k in range(len(minibatches(case['M'], case['B']))):
+        res.append(case_step(case, state, k, dtype))
+        state = advance(state, res[-1])
+    return res, state
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# seeded inputs with arranged branch coverage
+# ---------------------------------------------------------------------------------------------------------------------
+# log-ratios of the issue's probe at clip 0.2: two per range (below, inside, above); other clips scale the same picture
+def log_ratios(clip: float) -> np.ndarray:
+    if abs(clip - 0.2) < 1e-9:
+        return np.array([-0.5, -0.35, -0.1, 0.1, 0.35, 0.5])
+    return np.log([(1 - clip) * 0.75, (1 - clip) * 0.9, 1 - clip / 2, 1 + clip / 2, (1 + clip) * 1.15, (1 + clip) * 1.35])
+
+
+def _zero_like_state(shapes: dict) -> dict:
+    return {net: OrderedDict((k, np.zeros(s, F32)) for k, s in sh.items()) for net, sh in shapes.items()}
+
+
+def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kind: int = 0, clip: float = 0.2,
+              lam: float = 0.37, entropy_coef: float = 0.01, use_critic_norm: int = 1, critic_norm_coef: float = 0.001,
+              norm_clip=None, use_max_grad_norm: int = 1, use_cost: bool = True, update_actor: bool = True,
+              update_critics: bool = True, seeded_moments: bool = False, t0=(0, 0, 0), lr_actor: float = 3e-4,
+              lr_critic: float = 3e-4, ext: dict | None = None, trust: bool = False, p3o: str | None = None) -> dict:
+    """One case of the GPU table.
+
+    norm_clip  None: max_grad_norm = 1000 bites nowhere (the clip code runs, its factor is 1);  (net index | 'all', factor): max_grad_norm = factor x the
+               twin's float64 gradient norm of that network on the first minibatch ('all': of the smallest of the three)
+    trust      prescribe old_mean / old_log_std so that the per-sample KL sits at 0.4 eta or 2 eta (ext['kl_mask_eta'])
+    p3o        'active' / 'inactive': cost_excess puts mean(r adv_c) + excess of every minibatch at >= +0.05 / <= -0.05
+    """
+    rs = np.random.RandomState(20240 + 131 * obs_dim + 17 * act_dim + 7 * B + M)
+    shapes = {net: tensor_shapes(net, obs_dim, act_dim) for net in NETS}
+    params = {net: OrderedDict((k, rs.uniform(-0.2, 0.2, s).astype(F32)) for k, s in sh.items())
+              for net, sh in shapes.items()}
+    params['actor']['log_std'] = np.linspace(-0.5, 0.3, act_dim).astype(F32)
+    m, v = _zero_like_state(shapes), _zero_like_state(shapes)
+    # (the streams are drawn whether used or not: a case and its zero-moment twin share every other number)
+    for net in NETS:
+        for k, s in shapes[net].items():
+            mm = (1e-3 * rs.randn(*s)).astype(F32)
+            vv = (1e-5 * rs.uniform(0.1, 1.0, s)).astype(F32)
+            if seeded_moments:
+                m[net][k], v[net][k] = mm, vv
+    state = {'params': params, 'm': m, 'v': v, 't': dict(zip(NETS, (int(t) for t in t0)))}
+    perm = rs.permutation(M).astype(np.int64)
+    data = dict(obs=rs.randn(M, obs_dim).astype(F32), act=(0.5 * rs.randn(M, act_dim)).astype(F32),
+                target_value_r=(0.1 * rs.randn(M)).astype(F32), target_value_c=(5.0 * rs.randn(M)).astype(F32),
+                adv_r=rs.randn(M).astype(F32), adv_c=rs.randn(M).astype(F32))
+    # The three gradient norms are kept well apart (about 0.2 : 1.5 : 7), so that a clip factor taken from another
+    # network's norm is a visible error and the reward critic's L2 term can dominate its norm: the reward critic's
+    # targets sit close to its own float64 values, the advantages are scaled (below, by a power of two) until the
+    # actor's norm is near 1.5, the cost critic's targets are wide.
+    obs64 = torch.from_numpy(data['obs'].astype(np.float64))
+    with torch.no_grad():
+        vr = _mlp({k: torch.from_numpy(w.astype(np.float64)) for k, w in params['reward_critic'].items()}, 'critic_0', obs64)
+    data['target_value_r'] = (vr[:, 0].numpy() + data['target_value_r']).astype(F32)
+    # ---- clip cells: position k of the permutation gets cell k mod 6 = (range, sign of A); the two log-ratios of a
+    # range alternate from one group of six to the next
+    lam32 = _f32(lam)
+    pos = np.empty(M, np.int64)
+    pos[perm] = np.arange(M)  # position of row i in the pass
+    cell = pos % 6
+    want_pos = cell % 2 == 0
+    A = (data['adv_r'].astype(np.float64) - lam32 * data['adv_c']) / (1 + lam32)
+    flip = (A > 0) != want_pos
+    data['adv_r'][flip] *= -1
+    data['adv_c'][flip] *= -1
+    lr_tab = log_ratios(clip)
+    delta = lr_tab[2 * (cell // 2) + (pos // 6) % 2]
+    with torch.no_grad():
+        p64 = {k: torch.from_numpy(w.astype(np.float64)) for k, w in params['actor'].items()}
+        mean = _mlp(p64, 'mean', torch.from_numpy(data['obs'].astype(np.float64)))
+        dist = torch.distributions.Normal(mean, torch.exp(p64['log_std']))
+        logp_new = dist.log_prob(torch.from_numpy(data['act'].astype(np.float64))).sum(-1).numpy()
+    data['logp'] = (logp_new - delta).astype(F32)
+    hp = dict(clip=clip, entropy_coef=entropy_coef, critic_norm_coef=critic_norm_coef, max_grad_norm=1000.0,
+              lr_actor=lr_actor, lr_critic=lr_critic, beta1=0.9, beta2=0.999, adam_eps=1e-8,
+              use_critic_norm=int(use_critic_norm), use_max_grad_norm=int(use_max_grad_norm))
+    ext = None if ext is None else dict(ext)
+    if ext is not None:
+        # the behaviour policy: old_log_std a little wider than log_std, old_mean at a prescribed KL from the mean
+        old_ls = (params['actor']['log_std'].astype(np.float64) + 0.05).astype(F32)
+        data['old_log_std'] = old_ls
+        s0, s1 = np.exp(old_ls.astype(np.float64)), np.exp(params['actor']['log_std'].astype(np.float64))
+        floor = float(np.sum(np.log(s0 / s1) + s1 ** 2 / (2 * s0 ** 2) - 0.5))  # KL at equal means
+        if trust:
+            eta = _f32(ext['kl_mask_eta'])
+            assert 0.4 * eta > floor, (floor, eta)
+            inside = rs.permutation(M) % 2 == 0
+            target = np.where(inside, 0.4 * eta, 2.0 * eta)
+        else:
+            rs.permutation(M)
+            target = floor + 0.05 + 0.1 * (pos % 3)
+        sign = np.where(rs.rand(M, act_dim) < 0.5, -1.0, 1.0)
+        dmu = sign * s0[None, :] * np.sqrt(2 * (target - floor) / act_dim)[:, None]
+        data['old_mean'] = (mean.numpy() + dmu).astype(F32)
+    case = dict(obs_dim=obs_dim, act_dim=act_dim, B=B, M=M, state=state, data=data, perm=perm, hp=hp, lam=lam32,
+                loss_kind=loss_kind, ext=ext, use_cost=bool(use_cost), update_actor=bool(update_actor),
+                update_critics=bool(update_critics), seeded_moments=bool(seeded_moments), trust=bool(trust), p3o=p3o,
+                norm_clip=norm_clip)
+    if update_actor:
+        g0 = float(case_step(dict(case, update_critics=False, ext=None), state, 0)['actor']['gnorm'])
+        scale = F32(2.0 ** round(math.log2(1.5 / g0)))
+        data['adv_r'] *= scale
+        data['adv_c'] *= scale
+    if p3o is not None:
+        # mean(r adv_c) of every minibatch at the case's initial parameters, then an excess clear of all of them
+        ext['cost_excess'] = 0.0
+        cs = [float(case_step(case, state, k)['actor']['cost_surrogate']) for k in range(len(minibatches(M, B)))]
+        ext['cost_excess'] = _f32(-min(cs) + 0.5 if p3o == 'active' else -max(cs) - 0.5)
+    if norm_clip is not None:
+        which, factor = norm_clip
+        all_nets = dict(case, update_actor=True, update_critics=True, use_cost=True)
+        r0 = case_step(all_nets, state, 0)
+        norms = [float(r0[net]['gnorm']) for net in NETS]
+        hp['max_grad_norm'] = _f32(factor * (min(norms) if which == 'all' else norms[which]))
+        case['norms0'] = norms
+    return case
+
+
+def check_coverage(case: dict) -> dict:
+    """Asserts that the case reaches the branches it is in the table for -- on the float64 chain of its pass, so for
+    every minibatch at the parameters that minibatch meets.  Returns what it counted."""
+    res, _ = run_pass(case)
+    clip = _f32(case['hp']['clip'])
+    seen = set()
+    info = {'cells': [], 'edge': np.inf}
+    for k, r in enumerate(res):
+        if 'actor' not in r:
+            continue
+        a = r['actor']
+        ratio, adv = a['ratio'].numpy(), a['adv'].numpy()
+        n = len(ratio)
+        edge = np.minimum(np.abs(ratio - (1 - clip)), np.abs(ratio - (1 + clip))).min()
+        info['edge'] = min(info['edge'], float(edge))
+        assert edge >= 1e-3, (k, edge)  # float32 and float64 take the same branch
+        assert np.abs(adv).min() > 0
+        rng = np.where(ratio < 1 - clip, 0, np.where(ratio > 1 + clip, 2, 1))
+        cells = {(int(g), bool(s)) for g, s in zip(rng, adv > 0)}
+        info['cells'].append(len(cells))
+        seen |= cells
+        # six cells wherever six rows exist; a shorter minibatch (B = 5, a tail of one or two rows) cannot hold six
+        # and must put every row into a cell of its own
+        assert len(cells) == min(n, 6), (k, n, sorted(cells))
+        if case['trust']:
+            eta = _f32(case['ext']['kl_mask_eta'])
+            kl = a['kl'].numpy()
+            assert np.abs(kl - eta).min() >= 0.01 * eta, (k, np.abs(kl - eta).min())
+            if n >= 8:
+                inside = int((kl <= eta).sum())
+                assert inside >= n / 4 and n - inside >= n / 4, (k, inside, n)
+            info.setdefault('inside', []).append(int((kl <= eta).sum()))
+        if case['p3o'] is not None:
+            val = float(a['cost_surrogate']) + _f32(case['ext']['cost_excess'])
+            assert (val >= 0.05) if case['p3o'] == 'active' else (val <= -0.05), (k, val)
+            assert (float(a['penalty']) > 0) == (case['p3o'] == 'active')
+            info.setdefault('penalty_arg', []).append(val)
+    if case['update_actor']:
+        assert len(seen) == 6, sorted(seen)  # over the pass every cell is reached, whatever the minibatch size
+    if case['norm_clip'] is not None:
+        which, factor = case['norm_clip']
+        mg, norms = _f32(case['hp']['max_grad_norm']), case['norms0']
+        for i, net in enumerate(NETS):
+            own = which == 'all' or i == which
+            if own and which != 'all':
+                assert abs(mg / norms[i] - factor) < 1e-6
+            elif not own:  # the other networks: far from the threshold, on whichever side
+                assert not (1 / 1.5 < mg / norms[i] < 1.5), (net, mg, norms)
+        r0 = res[0]
+        active = [net for net in r0 if float(r0[net]['coef']) < 1.0]
+        info['clipped'] = active
+        if factor < 1.0:
+            assert (set(active) == set(r0)) if which == 'all' else (NETS[which] in active or NETS[which] not in r0)
+    elif case['hp']['use_max_grad_norm']:
+        assert all(float(r[net]['coef']) == 1.0 for r in res for net in r)
+    return info
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the table of the GPU tests (tests/test_step_oracle_gpu.py) and of the float32 measuring stick
+# ---------------------------------------------------------------------------------------------------------------------
+SHAPES = [(1, 1), (16, 2), (17, 3), (60, 2), (64, 16), (65, 17), (80, 32), (96, 16)]
+VARIANT_SHAPES = [(60, 2), (65, 17)]
+EXT_SHAPES = [(60, 2), (28, 8)]
+BATCHES = [(64, 64), (64, 65), (64, 127), (32, 80), (48, 100), (5, 12)]  # (B, M)
+FOCOPS = dict(kl_coef=1.0, kl_mask_eta=0.5, ratio_scale=1.0 / 1.5)
+
+
+def case_table() -> 'OrderedDict[str, dict]':
+    """name -> make_case keyword arguments.  Every entry changes ONE thing from the base configuration (loss_kind 0,
+    clip 0.2, lam 0.37, entropy_coef 0.01, critic L2 on at 0.001, norm clip inactive, B 64, M 100)."""
+    t = OrderedDict()
+    for od, ad in SHAPES:
+        t[f'base-{od}x{ad}'] = dict(obs_dim=od, act_dim=ad)
+    for od, ad in VARIANT_SHAPES:
+        s = f'{od}x{ad}'
+        kw = dict(obs_dim=od, act_dim=ad)
+        for B, M in BATCHES:
+            t[f'mb-B{B}-M{M}-{s}'] = dict(kw, B=B, M=M)
+        for net in range(3):
+            for fac in (0.5, 0.999, 1.001, 2.0):
+                t[f'normclip-{NETS[net]}-{fac}-{s}'] = dict(kw, norm_clip=(net, fac))
+        t[f'normclip-all-{s}'] = dict(kw, norm_clip=('all', 0.5))
+        t[f'normclip-off-{s}'] = dict(kw, use_max_grad_norm=0)
+        t[f'l2-off-{s}'] = dict(kw, use_critic_norm=0)
+        t[f'l2-0.05-{s}'] = dict(kw, critic_norm_coef=0.05)
+        # (with the L2 term dominating the critics' norms, a norm taken before the term would not clip)
+        t[f'l2-0.05-clipped-{s}'] = dict(kw, critic_norm_coef=0.05, norm_clip=(1, 0.5))
+        t[f'entropy-0-{s}'] = dict(kw, entropy_coef=0.0)
+        t[f'entropy-0.05-{s}'] = dict(kw, entropy_coef=0.05)
+        t[f'losskind1-{s}'] = dict(kw, loss_kind=1)
+        t[f'lam-0-{s}'] = dict(kw, lam=0.0)
+        t[f'lam-50-{s}'] = dict(kw, lam=50.0)
+        t[f'nocost-{s}'] = dict(kw, use_cost=False)
+        t[f'actor-off-{s}'] = dict(kw, update_actor=False)
+        t[f'critics-off-{s}'] = dict(kw, update_critics=False)
+        t[f'clip-0.05-{s}'] = dict(kw, clip=0.05)
+        t[f'clip-0.4-{s}'] = dict(kw, clip=0.4)
+        t[f'seeded-{s}'] = dict(kw, seeded_moments=True, t0=(3, 5, 7))
+        for t0 in (0, 9, 999, 250000):
+            t[f't0-{t0}-{s}'] = dict(kw, seeded_moments=True, t0=(t0, t0, t0))
+        t[f'lr-{s}'] = dict(kw, lr_actor=3e-4, lr_critic=1e-3, seeded_moments=True, t0=(3, 5, 7))
+    for od, ad in EXT_SHAPES:
+        s = f'{od}x{ad}'
+        kw = dict(obs_dim=od, act_dim=ad, update_critics=False)
+        t[f'focops-mask-{s}'] = dict(kw, loss_kind=1, ext=FOCOPS, trust=True)
+        t[f'focops-nomask-{s}'] = dict(kw, loss_kind=1, ext=dict(FOCOPS, kl_mask_eta=-1.0))
+        t[f'cup-{s}'] = dict(kw, loss_kind=1, ext=dict(kl_coef=1.0), entropy_coef=0.0)
+        t[f'p3o-active-{s}'] = dict(kw, ext=dict(cost_kappa=2.0), p3o='active')
+        t[f'p3o-inactive-{s}'] = dict(kw, ext=dict(cost_kappa=2.0), p3o='inactive')
+    return t
+
+
+def zero_moment_twin(kwargs: dict) -> dict:
+    """The same case from zero moments: same inputs, same kernel -- where the clipped gradient is m' / (1 - b1)."""
+    return dict(kwargs, seeded_moments=False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the measuring stick: what one float32 evaluation of the same formula loses against float64
+# ---------------------------------------------------------------------------------------------------------------------
+SCALARS = {'actor': ('loss', 'ratio_mean', 'entropy', 'gnorm', 'penalty'), 'reward_critic': ('mse', 'psq', 'gnorm'),
+           'cost_critic': ('mse', 'psq', 'gnorm')}
+FLOOR = 2.0 ** -22
+# A critic's output-bias gradient is ONE number, 2/n sum_rows (v - target) (+ the L2 term): where the residuals
+# cancel, what a float32 evaluation loses on it is the sum of its n forward-value errors over a small result, and the
+# tensor's own e32 is one draw of that sum (it can come out at a fifth of its typical size).  OUT_BIAS_ROWS records
+# the typical size instead, from the float32 run's forward values: a sum of n independent errors of their rms,
+# (2 / sqrt n) rms_rows(v32 - v64) / |g_64|.  The GPU tests take the larger of the two as this tensor's unit.
+OUT_BIAS, OUT_BIAS_ROWS = 'critic_0.4.bias', 'critic_0.4.bias/rows'
+
+
+def rel_l2(a, b) -> float:
+    """|a - b|_2 / |b|_2 in float64 (0 when both vanish)."""
+    a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
+    den = np.linalg.norm(b)
+    num = np.linalg.norm(a - b)
+    return 0.0 if num == 0.0 else float(num / den) if den > 0 else np.inf
+
+
+ROW_ORDERS = 4
+
+
+def f32_error(case: dict) -> tuple:
+    """Per network: relative L2 error of the float32 run against the float64 run of every minibatch of the case taken
+    from its INITIAL state -- per reference tensor of the unclipped gradient and per scalar.  Returns (worst, single).
+
+    `single` is the float32 run with the rows as drawn, worst over the minibatches.  The rounding error of a sum
+    depends on the order of its terms, and a one-element tensor (an output bias: a sum over the rows of signed
+    residuals) or a scalar shows ONE draw of it per evaluation -- anything between nothing and its full spread.  As a
+    unit of measurement one draw is arbitrary there, so the float32 run is repeated with the minibatch's rows in
+    ROW_ORDERS orders (as drawn, and seeded shuffles of it: the same step, another summation order) and `worst` is
+    the worst over the orders and the minibatches.  That is the unit of the GPU tests; a tensor of many elements
+    averages the draws by itself and the choice matters little there.  Both are recorded, and
+    profiles/step_twin_error.md states the kernels' worst ratios against both."""
+    worst, single = {}, {}
+    for k, (_, n) in enumerate(minibatches(case['M'], case['B'])):
+        r64 = case_step(case, case['state'], k)
+        rs = np.random.RandomState(977 + k)
+        for order in [None] + [rs.permutation(n) for _ in range(ROW_ORDERS - 1)]:
+            r32 = case_step(case, case['state'], k, torch.float32, order)
+            for net in r64:
+                errs = {name: rel_l2(r32[net]['grads'][name].numpy(), g.numpy()) for name, g in r64[net]['grads'].items()}
+                errs.update((sc, rel_l2(float(r32[net][sc]), float(r64[net][sc]))) for sc in SCALARS[net])
+                if net != 'actor':
+                    v64 = r64[net]['value'].numpy() if order is None else r64[net]['value'].numpy()[order]
+                    rms = float(np.sqrt(np.mean((r32[net]['value'].numpy().astype(np.float64) - v64) ** 2)))
+                    errs[OUT_BIAS_ROWS] = 2.0 / math.sqrt(n) * rms / abs(float(r64[net]['grads'][OUT_BIAS]))
+                for dst in (worst,) if order is not None else (worst, single):
+                    o = dst.setdefault(net, {})
+                    for name, e in errs.items():
+                        o[name] = max(o.get(name, 0.0), e)
+    return worst, single
+
+
+def pack_f32_error(table: dict) -> dict:
+    """{case: (worst, single)} -> the layout of tests/golden/step_twin_f32_error.json: every distinct per-network
+    block once (cases that share a network's inputs share its figures), as [worst..., single...] in the order of
+    `keys`; `cases` maps case and network to a block."""
+    keys, blocks, index, cases = {}, [], {}, {}
+    for name, (worst, single) in table.items():
+        cases[name] = {}
+        for net in worst:
+            keys.setdefault(net, list(worst[net]))
+            assert list(worst[net]) == keys[net] == list(single[net])
+            blk = (net,) + tuple(float(f'{d[k]:.2e}') for d in (worst[net], single[net]) for k in keys[net])
+            if blk not in index:
+                index[blk] = len(blocks)
+                blocks.append(list(blk[1:]))
+            cases[name][net] = index[blk]
+    return {'keys': keys, 'blocks': blocks, 'cases': cases}
+
+
+def load_f32_error(path: str) -> tuple:
+    """-> (worst, single), each {case: {network: {tensor or scalar: error}}}."""
+    import json
+
+    blob = json.load(open(path))
+    worst, single = {}, {}
+    for name, nets in blob['cases'].items():
+        worst[name], single[name] = {}, {}
+        for net, b in nets.items():
+            ks, row = blob['keys'][net], blob['blocks'][b]
+            worst[name][net] = dict(zip(ks, row[:len(ks)]))
+            single[name][net] = dict(zip(ks, row[len(ks):]))
+    return worst, single
