@@ -172,6 +172,20 @@ __device__ __forceinline__ f32x4 osa_dact4(f32x4 h, int act) {
   return r;
 }
 
+// tanh'(z) from h = tanh(z): 1 - h h, one fma per element (the contraction of the plain vector expression, which the
+// .xy half still is).  On the whole f32x4 the compiler gives the packed fma of .xy the sign of -h as an operand modifier
+// and forms it with two v_xor for .zw -- 16 plain VALU instructions per step of the 64-row pass; with .zw written as
+// scalar fmas it packs them again, with the modifier.  (All four as scalar fmas come back as the vector form, xors included.)
+// Bit-equality of the two halves, and with the plain expression the other instantiations keep, rests on the compiler
+// contracting 1.f - h * h into one fma, as it does under hipcc's default -ffp-contract=fast (the build sets no other);
+// with contraction off .xy would round h * h first.  tests/test_pass_regs_gpu.py pins the product build.
+__device__ __forceinline__ f32x4 osa_one_minus_sq4(f32x4 h) {
+  f32x4 r = 1.f - h * h;
+  r.z = __builtin_fmaf(-h.z, h.z, 1.f);
+  r.w = __builtin_fmaf(-h.w, h.w, 1.f);
+  return r;
+}
+
 // One Adam step of one parameter (torch.optim.Adam single-tensor form):
 //   m <- lerp(m, g, 1-b1); v <- b2 v + (1-b2) g^2; w <- w - step_size * m / (sqrt(v)/bc2_sqrt + eps)
 // inv_bc2_sqrt = 1/sqrt(1 - b2^t), step_size = lr/(1 - b1^t) are formed once per step in float64.
@@ -191,6 +205,35 @@ __device__ __forceinline__ f32x4 osa_adam_update4(f32x4 g, f32x4& m, f32x4& v, f
                                                   float beta2, float step_size, float inv_bc2_sqrt,
                                                   float eps) {
   m = m + (g - m) * (1.f - beta1);
+  v = v * beta2 + (g * g) * (1.f - beta2);
+  f32x4 sq;
+  sq.x = __builtin_amdgcn_sqrtf(v.x);
+  sq.y = __builtin_amdgcn_sqrtf(v.y);
+  sq.z = __builtin_amdgcn_sqrtf(v.z);
+  sq.w = __builtin_amdgcn_sqrtf(v.w);
+  const f32x4 denom = sq * inv_bc2_sqrt + eps;
+  f32x4 rc;
+  rc.x = __builtin_amdgcn_rcpf(denom.x);
+  rc.y = __builtin_amdgcn_rcpf(denom.y);
+  rc.z = __builtin_amdgcn_rcpf(denom.z);
+  rc.w = __builtin_amdgcn_rcpf(denom.w);
+  return w - (m * step_size) * rc;
+}
+
+// osa_adam_update4(graw * gscale, ...) without its sign flips.  There the compiler contracts (g - m) into
+// fma(graw, gscale, -m) and, in packed math, forms -m with one v_xor per element: 36 plain VALU instructions per step of
+// the 64-row pass.  Here two scalars carry the sign instead, ngscale = -gscale and nomb1 = beta1 - 1 (= -(1 - beta1),
+// exactly): m - g = fma(graw, -gscale, m) is the exact negative of g - m (round to nearest is symmetric), and
+// (m - g) nomb1 is the product of two exact negatives, so m comes out with the same bits; v, the denominator and the
+// weight are formed as above.  Like osa_adam_update4 itself the argument holds for either contraction setting as long
+// as BOTH forms are compiled under the same one (default -ffp-contract=fast: both differences are fmas; off: g is
+// rounded first in both, and m + (-g) is still the exact negative of g - m); mixing settings between translation
+// units would break the equality with the instantiations that keep osa_adam_update4.
+__device__ __forceinline__ f32x4 osa_adam_update4_scaled(f32x4 graw, float gscale, float ngscale, f32x4& m, f32x4& v,
+                                                         f32x4 w, float nomb1, float beta2, float step_size,
+                                                         float inv_bc2_sqrt, float eps) {
+  const f32x4 g = graw * gscale;
+  m = m + (m + graw * ngscale) * nomb1;
   v = v * beta2 + (g * g) * (1.f - beta2);
   f32x4 sq;
   sq.x = __builtin_amdgcn_sqrtf(v.x);

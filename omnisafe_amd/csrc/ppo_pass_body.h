@@ -253,6 +253,12 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
   // operands W2^T[16t+i][k .. k+3] are then ONE 16-byte LDS read instead of four scalar ones (64 -> 16 LDS reads
   // per lane and step); kept in step by the Adam writers.  Only where the LDS budget allows (narrow observations).
   constexpr bool W2T = osa_pass_has_w2t(KB, OT);
+  // The plain small-output pass with one chunk per step (the headline instantiations) forms tanh' and Adam's first moment
+  // without the sign flips the compiler otherwise emits as v_xor (mlp_device.h: osa_one_minus_sq4,
+  // osa_adam_update4_scaled): same bits, 52 plain VALU instructions fewer per step.  Every other mode compiles the
+  // expressions it always had: there the same rewrite moved the register allocation of instantiations that spill
+  // already (more spilled SGPRs in half of them, + 9 to + 12 in the multi-chunk SO ones of KB <= 3, + 2 / + 2 at KB = 6).
+  constexpr bool SIGN_FREE = SO && KB <= 5 && !MULTI && !COOP && !EXT && !HIER && !DPS && !P2P;
   float* sW2T = red + 64;               // [H][PSLD]   (W2T only)
 
 #ifdef OSA_BODY_OPAQUE_TID
@@ -968,7 +974,8 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     }
 #pragma unroll
     for (int t = 0; t < HT; ++t) {
-      z2[t] = z2[t] * (1.f - h2[t] * h2[t]);
+      if constexpr (SIGN_FREE) z2[t] = z2[t] * osa_one_minus_sq4(h2[t]);
+      else z2[t] = z2[t] * (1.f - h2[t] * h2[t]);
       PUT_TILE(sZ2, z2[t], t);
     }
 #pragma unroll
@@ -985,7 +992,8 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     }
 #pragma unroll
     for (int t = 0; t < HT; ++t) {
-      z1[t] = z1[t] * (1.f - h1[t] * h1[t]);
+      if constexpr (SIGN_FREE) z1[t] = z1[t] * osa_one_minus_sq4(h1[t]);
+      else z1[t] = z1[t] * (1.f - h1[t] * h1[t]);
       PUT_TILE(sZ1, z1[t], t);
     }
 #undef PUT_TILE
@@ -1608,6 +1616,7 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     }
     // ================= Adam on the owned parameters; LDS master updated in place =================
     const float gscale = apply_clip ? coef : 1.f;
+    const float ngscale = -gscale, nomb1 = beta1 - 1.f;  // (SIGN_FREE) the signs of (g - m)(1 - beta1)
     auto put_w2 = [&](int ti, f32x4 w) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) sW2[(16 * wave + 4 * g + r) * PSLD + 16 * ti + cc] = w[r];
@@ -1625,7 +1634,10 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     for (int ti = 0; ti < HT; ++ti) {
       {
         f32x4 w = w2r[ti];
-        w = osa_adam_update4(g2[ti] * gscale, m2[ti], v2[ti], w, beta1, beta2, step_size, inv_bc2_sqrt, aeps);
+        if constexpr (SIGN_FREE)
+          w = osa_adam_update4_scaled(g2[ti], gscale, ngscale, m2[ti], v2[ti], w, nomb1, beta2, step_size, inv_bc2_sqrt, aeps);
+        else
+          w = osa_adam_update4(g2[ti] * gscale, m2[ti], v2[ti], w, beta1, beta2, step_size, inv_bc2_sqrt, aeps);
         put_w2(ti, w);
       }
     }
@@ -1633,7 +1645,10 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     for (int kb = 0; kb < KB; ++kb) {
       {
         f32x4 w = w1r[kb];
-        w = osa_adam_update4(g1[kb] * gscale, m1[kb], v1[kb], w, beta1, beta2, step_size, inv_bc2_sqrt, aeps);
+        if constexpr (SIGN_FREE)
+          w = osa_adam_update4_scaled(g1[kb], gscale, ngscale, m1[kb], v1[kb], w, nomb1, beta2, step_size, inv_bc2_sqrt, aeps);
+        else
+          w = osa_adam_update4(g1[kb] * gscale, m1[kb], v1[kb], w, beta1, beta2, step_size, inv_bc2_sqrt, aeps);
         put_w1(kb, w);
       }
     }
@@ -1641,7 +1656,10 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
     for (int o = 0; o < OT; ++o) {
       {
         f32x4 w = w3r[o];
-        w = osa_adam_update4(g3[o] * gscale, m3[o], v3[o], w, beta1, beta2, step_size, inv_bc2_sqrt, aeps);
+        if constexpr (SIGN_FREE)
+          w = osa_adam_update4_scaled(g3[o], gscale, ngscale, m3[o], v3[o], w, nomb1, beta2, step_size, inv_bc2_sqrt, aeps);
+        else
+          w = osa_adam_update4(g3[o] * gscale, m3[o], v3[o], w, beta1, beta2, step_size, inv_bc2_sqrt, aeps);
         put_w3(o, w);
       }
     }

@@ -38,6 +38,10 @@ sources, e.g. csrc/_one.hip:
 (about 5 s), then
 
     python tools/pass_issue_model.py one_clocks.s profiles/pass_trim_phase_clocks.txt --block 1
+
+--classes adds a second table that splits each phase's plain `valu` count into accumulator-register copies, lane moves
+of spilled scalars, moves, address arithmetic and math (profiles/pass_regs_issue_classes.txt), with the opcodes behind
+every cell.
 """
 from __future__ import annotations
 
@@ -116,6 +120,144 @@ def split_phases(asm_text: str, phases=PHASES, skip: int = 1, clock_opcode: str 
     return dict(zip(phases, segs))
 
 
+# ---- what the plain `valu` column is made of (--classes).  Every plain VALU instruction of a phase falls into one of
+#   agpr   accumulator-register copies: a value the allocator parked in an AGPR, read back before a VALU use
+#   lane   lane moves that serve SGPR spills: v_writelane, and v_readlane from a register some v_writelane of the kernel
+#          fills (a v_readlane of lane 63 at the end of a DPP reduction is math: it delivers the sum)
+#   mov    register-to-register and constant moves (DPP moves of a reduction are math: they carry the operand)
+#   addr   integer arithmetic whose result reaches the address operand of an LDS or memory instruction, directly or
+#          through further integer arithmetic, before its register is overwritten
+#   math   everything else
+VALU_CLASSES = ['agpr', 'lane', 'mov', 'addr', 'math']
+_INT_PREFIXES = ('v_add_u32', 'v_sub_u32', 'v_subrev_u32', 'v_add_co', 'v_addc_co', 'v_sub_co', 'v_subb_co', 'v_lshl_add',
+                 'v_add_lshl', 'v_lshl_or', 'v_lshlrev_b', 'v_lshrrev_b', 'v_ashrrev_i', 'v_mul_lo_u32', 'v_mul_u32_u24',
+                 'v_mul_i32_i24', 'v_mad_u32_u24', 'v_mad_i32_i24', 'v_mad_u64_u32', 'v_and_b32', 'v_or_b32', 'v_and_or_b32',
+                 'v_bfe_u32', 'v_add3_u32')
+_MEM_PREFIXES = ('ds_', 'global_', 'flat_', 'scratch_', 'buffer_')
+_VREG = re.compile(r'\bv(\d+)\b|\bv\[(\d+):(\d+)\]')
+
+
+def _vregs(operand: str) -> set:
+    regs = set()
+    for m in _VREG.finditer(operand):
+        if m.group(1) is not None:
+            regs.add(int(m.group(1)))
+        else:
+            regs.update(range(int(m.group(2)), int(m.group(3)) + 1))
+    return regs
+
+
+def _address_regs(op: str, operands: list) -> set:
+    """VGPRs of the address operand of a memory instruction: operand 1 of a load / read, operand 0 otherwise."""
+    load = 'read' in op or 'load' in op
+    idx = 1 if load else 0
+    return _vregs(operands[idx]) if idx < len(operands) else set()
+
+
+def spill_registers(instrs: list) -> set:
+    """VGPRs whose lanes hold spilled SGPRs: every destination of a v_writelane in the kernel."""
+    regs = set()
+    for op, args in instrs:
+        if op.startswith('v_writelane'):
+            regs |= _vregs(args.split(',')[0])
+    return regs
+
+
+def valu_class(op: str, args: str = '', spills: frozenset = frozenset()) -> str:
+    """Class of a plain VALU instruction; integer arithmetic comes back as 'int' and is settled by feeds_address()."""
+    if op.startswith('v_accvgpr'):
+        return 'agpr'
+    if op.startswith('v_writelane'):
+        return 'lane'
+    if op.startswith('v_readlane'):
+        src = args.split(',')[1] if ',' in args else ''
+        return 'lane' if _vregs(src) & spills else 'math'
+    if op.startswith('v_mov') and 'dpp' not in op:
+        return 'mov'
+    if op.startswith(_INT_PREFIXES):
+        return 'int'
+    return 'math'
+
+
+def feeds_address(instrs: list, i: int, window: int = 600, _memo=None) -> bool:
+    """True if the destination of integer instruction i reaches an address operand further down the listing (straight
+    scan, branches ignored: the step loop is one block between its clock reads apart from short uniform branches)."""
+    memo = {} if _memo is None else _memo
+    if i in memo:
+        return memo[i]
+    memo[i] = False
+    op, args = instrs[i]
+    operands = [s.strip() for s in args.split(',')]
+    live = _vregs(operands[0]) if operands else set()
+    for j in range(i + 1, min(len(instrs), i + 1 + window)):
+        if not live:
+            break
+        opj, argsj = instrs[j]
+        opsj = [s.strip() for s in argsj.split(',')]
+        if opj.startswith(_MEM_PREFIXES):
+            if live & _address_regs(opj, opsj):
+                memo[i] = True
+                break
+            if 'read' in opj or 'load' in opj:
+                live -= _vregs(opsj[0])
+            continue
+        if not opj.startswith('v_'):
+            continue
+        srcs = set().union(*[_vregs(s) for s in opsj[1:]]) if len(opsj) > 1 else set()
+        if live & srcs and valu_class(opj) == 'int' and feeds_address(instrs, j, window, memo):
+            memo[i] = True
+            break
+        live -= _vregs(opsj[0])
+    return memo[i]
+
+
+def split_valu(asm_text: str, phases=PHASES, skip: int = 1, clock_opcode: str = CLOCK_OPCODE) -> dict:
+    """phase -> {class: count, 'opcodes': {class: {opcode: count}}} of the plain VALU instructions, cut at the clock
+    reads like split_phases()."""
+    instrs = list(instructions(asm_text))
+    spills = frozenset(spill_registers(instrs))
+    memo = {}
+    segs, cur, nreads = [], None, 0
+    for i, (op, args) in enumerate(instrs):
+        if op == clock_opcode:
+            nreads += 1
+            if nreads > skip:
+                cur = {c: 0 for c in VALU_CLASSES}
+                cur['opcodes'] = {c: {} for c in VALU_CLASSES}
+                segs.append(cur)
+            continue
+        if cur is None or classify(op) != 'valu':
+            continue
+        cls = valu_class(op, args, spills)
+        if cls == 'int':
+            cls = 'addr' if feeds_address(instrs, i, _memo=memo) else 'math'
+        cur[cls] += 1
+        cur['opcodes'][cls][op] = cur['opcodes'][cls].get(op, 0) + 1
+    return dict(zip(phases, segs))
+
+
+def render_valu(split: dict, phases=PHASES, cost: int = COSTS['valu']) -> str:
+    cols = ['valu'] + VALU_CLASSES
+    lines = ['  '.join([f'{"phase":>14s}'] + [f'{c:>6s}' for c in cols]) + '   non-math cycles']
+    tot = {c: 0 for c in cols}
+    for ph in phases:
+        s = split[ph]
+        row = {'valu': sum(s[c] for c in VALU_CLASSES), **{c: s[c] for c in VALU_CLASSES}}
+        for c in cols:
+            tot[c] += row[c]
+        lines.append('  '.join([f'{ph:>14s}'] + [f'{row[c]:>6d}' for c in cols])
+                     + f'   {cost * (row["valu"] - row["math"]):>6d}')
+    lines.append('  '.join([f'{"sum":>14s}'] + [f'{tot[c]:>6d}' for c in cols]) + f'   {cost * (tot["valu"] - tot["math"]):>6d}')
+    lines.append('')
+    for ph in phases:
+        for c in VALU_CLASSES:
+            ops = split[ph]['opcodes'][c]
+            if ops:
+                body = ', '.join(f'{n} {o}' for o, n in sorted(ops.items(), key=lambda kv: -kv[1]))
+                lines.append(f'{ph:>14s}  {c:>5s}: {body}')
+    return '\n'.join(lines)
+
+
 def modelled(counts: dict, costs: dict = COSTS) -> int:
     return sum(counts[c] * costs[c] for c in CLASSES)
 
@@ -184,12 +326,17 @@ def main(argv=None) -> int:
     ap.add_argument('--block', type=int, default=0, help='which pass-kernel block of the clock file (default 0)')
     ap.add_argument('--skip', type=int, default=1, help='clock reads in front of the loop (default 1)')
     ap.add_argument('--json', action='store_true', help='print the rows as JSON instead of a table')
+    ap.add_argument('--classes', action='store_true',
+                    help='also split the plain valu column: AGPR copies, lane moves, moves, address arithmetic, math')
     a = ap.parse_args(argv)
     costs = dict(COSTS)
     if a.costs:
         costs.update(json.load(open(a.costs)))
     rows = table(open(a.assembly).read(), open(a.clocks).read(), costs, a.column, PHASES, a.skip, a.block)
     print(json.dumps(rows) if a.json else render(rows))
+    if a.classes:
+        split = split_valu(open(a.assembly).read(), PHASES, a.skip)
+        print(json.dumps(split) if a.json else '\n' + render_valu(split, cost=costs['valu']))
     return 0
 
 
