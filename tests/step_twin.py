@@ -29,6 +29,10 @@ tests' tolerances (what ONE other float32 evaluation of the same formula loses),
 carries rows; `check_coverage` asserts it on the CPU so that no case can pass vacuously.  Every float32 input --
 parameters, moments, data, hyper-parameters, the multiplier -- is rounded to float32 first and widened afterwards: the
 twin and the kernels see the same numbers.
+
+`case_table()` is the table of the 64-row step (tests/test_step_oracle_gpu.py); `form_table()` that of the other forms
+of the same step -- several blocks + slab reduce, the chunked, wide and split passes, the large-batch partial
+gradients (tests/test_step_forms_gpu.py).  The twin itself is the same for all: a step of n rows is a step of n rows.
 """
 from __future__ import annotations
 
@@ -227,19 +231,31 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
               lam: float = 0.37, entropy_coef: float = 0.01, use_critic_norm: int = 1, critic_norm_coef: float = 0.001,
               norm_clip=None, use_max_grad_norm: int = 1, use_cost: bool = True, update_actor: bool = True,
               update_critics: bool = True, seeded_moments: bool = False, t0=(0, 0, 0), lr_actor: float = 3e-4,
-              lr_critic: float = 3e-4, ext: dict | None = None, trust: bool = False, p3o: str | None = None) -> dict:
+              lr_critic: float = 3e-4, ext: dict | None = None, trust: bool = False, p3o: str | None = None,
+              w1_scale: float = 1.0, target_c_scale: float = 5.0) -> dict:
     """One case of the GPU table.
 
     norm_clip  None: max_grad_norm = 1000 bites nowhere (the clip code runs, its factor is 1);  (net index | 'all', factor): max_grad_norm = factor x the
                twin's float64 gradient norm of that network on the first minibatch ('all': of the smallest of the three)
     trust      prescribe old_mean / old_log_std so that the per-sample KL sits at 0.4 eta or 2 eta (ext['kl_mask_eta'])
     p3o        'active' / 'inactive': cost_excess puts mean(r adv_c) + excess of every minibatch at >= +0.05 / <= -0.05
+    w1_scale   multiplies every network's first-layer weight AFTER it is drawn (no random stream moves).  Weights from
+               U(-0.2, 0.2) on D inputs give first-layer pre-activations of rms 0.115 sqrt(D): 2.2 at D = 376 with 23 %
+               of the units at |tanh| > 0.99, which damps exactly the first-layer gradients the wide kernels exist
+               for; the wide cases pass sqrt(64 / D) (rms 0.92, under 1 % saturated; check_coverage asserts <= 2 %)
+    target_c_scale  spread of the cost critic's targets.  Its gradient is a mean of n signed residuals and shrinks like
+               1 / sqrt n: at n = 2085 the default 5 leaves its norm at 1.63 next to the actor's 1.54, and a clip factor
+               taken from the wrong network would pass; the large-batch cases pass 20 (norm about 6, as at 64 rows)
     """
     rs = np.random.RandomState(20240 + 131 * obs_dim + 17 * act_dim + 7 * B + M)
     shapes = {net: tensor_shapes(net, obs_dim, act_dim) for net in NETS}
     params = {net: OrderedDict((k, rs.uniform(-0.2, 0.2, s).astype(F32)) for k, s in sh.items())
               for net, sh in shapes.items()}
     params['actor']['log_std'] = np.linspace(-0.5, 0.3, act_dim).astype(F32)
+    if w1_scale != 1.0:
+        for net in NETS:
+            k = ('mean' if net == 'actor' else 'critic_0') + '.0.weight'
+            params[net][k] = (params[net][k] * F32(w1_scale)).astype(F32)
     m, v = _zero_like_state(shapes), _zero_like_state(shapes)
     # (the streams are drawn whether used or not: a case and its zero-moment twin share every other number)
     for net in NETS:
@@ -251,7 +267,7 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
     state = {'params': params, 'm': m, 'v': v, 't': dict(zip(NETS, (int(t) for t in t0)))}
     perm = rs.permutation(M).astype(np.int64)
     data = dict(obs=rs.randn(M, obs_dim).astype(F32), act=(0.5 * rs.randn(M, act_dim)).astype(F32),
-                target_value_r=(0.1 * rs.randn(M)).astype(F32), target_value_c=(5.0 * rs.randn(M)).astype(F32),
+                target_value_r=(0.1 * rs.randn(M)).astype(F32), target_value_c=(target_c_scale * rs.randn(M)).astype(F32),
                 adv_r=rs.randn(M).astype(F32), adv_c=rs.randn(M).astype(F32))
     # The three gradient norms are kept well apart (about 0.2 : 1.5 : 7), so that a clip factor taken from another
     # network's norm is a visible error and the reward critic's L2 term can dominate its norm: the reward critic's
@@ -304,7 +320,7 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
     case = dict(obs_dim=obs_dim, act_dim=act_dim, B=B, M=M, state=state, data=data, perm=perm, hp=hp, lam=lam32,
                 loss_kind=loss_kind, ext=ext, use_cost=bool(use_cost), update_actor=bool(update_actor),
                 update_critics=bool(update_critics), seeded_moments=bool(seeded_moments), trust=bool(trust), p3o=p3o,
-                norm_clip=norm_clip)
+                norm_clip=norm_clip, w1_scale=float(w1_scale))
     if update_actor:
         g0 = float(case_step(dict(case, update_critics=False, ext=None), state, 0)['actor']['gnorm'])
         scale = F32(2.0 ** round(math.log2(1.5 / g0)))
@@ -380,7 +396,23 @@ def check_coverage(case: dict) -> dict:
             assert (set(active) == set(r0)) if which == 'all' else (NETS[which] in active or NETS[which] not in r0)
     elif case['hp']['use_max_grad_norm']:
         assert all(float(r[net]['coef']) == 1.0 for r in res for net in r)
+    if case.get('w1_scale', 1.0) != 1.0:
+        info['saturated'] = first_layer_saturation(case)
+        assert max(info['saturated'].values()) <= 0.02, info['saturated']
     return info
+
+
+def first_layer_saturation(case: dict) -> dict:
+    """Per network: the share of first-layer units (over all rows of the case, at its initial parameters) with
+    |tanh| > 0.99 -- units whose derivative, and with it the first-layer gradient, has all but vanished."""
+    obs = torch.from_numpy(case['data']['obs'].astype(np.float64))
+    out = {}
+    for net in NETS:
+        pre = 'mean' if net == 'actor' else 'critic_0'
+        p = {k: torch.from_numpy(np.asarray(w, np.float64)) for k, w in case['state']['params'][net].items()}
+        h = torch.tanh(obs @ p[f'{pre}.0.weight'].T + p[f'{pre}.0.bias'])
+        out[net] = float((h.abs() > 0.99).double().mean())
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -436,6 +468,108 @@ def case_table() -> 'OrderedDict[str, dict]':
         t[f'p3o-active-{s}'] = dict(kw, ext=dict(cost_kappa=2.0), p3o='active')
         t[f'p3o-inactive-{s}'] = dict(kw, ext=dict(cost_kappa=2.0), p3o='inactive')
     return t
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the second table: the forms of the step beyond one 64-row workgroup per network (tests/test_step_forms_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# form -> how PPOUpdater is brought to it and what it reports: persistent flag, environment, PPOUpdater.last_path
+FORMS = OrderedDict([
+    ('per-step', dict(persistent=False, env={}, last_path='per-step')),  # osa_mb_grad_kernel on several blocks + slab reduce
+    ('chunked', dict(persistent=True, env={}, last_path='persistent-chunked')),
+    ('wide', dict(persistent=True, env={'OSA_WIDE_SPLIT': '0'}, last_path='persistent-wide')),
+    ('split', dict(persistent=True, env={}, last_path='persistent-wide-split')),  # local placement, the default
+    ('split-spread', dict(persistent=True, env={'OSA_WIDE_SPLIT': 'spread'}, last_path='persistent-wide-split')),
+    ('balanced', dict(persistent=False, env={}, last_path='per-step')),  # B >= 2048: osa_ppo_part_kernel
+    ('strided', dict(persistent=False, env={'OSA_LARGE_BATCH_BALANCED': '0'}, last_path='per-step')),
+])
+CHUNK_SHAPES = [(60, 2), (65, 17)]
+# (B, M, rows of the tail minibatch, 64-row chunks of the B-row step that the tail leaves EMPTY)
+CHUNK_BATCHES = [(65, 130, 65, 0), (128, 300, 44, 1), (129, 129, 129, 0), (200, 500, 100, 2), (192, 256, 64, 2)]
+WIDE_SHAPES = [(97, 3), (90, 17), (192, 2), (193, 5), (375, 17), (376, 17), (512, 32)]
+WIDE_BATCHES = [(40, 100), (64, 65), (5, 12)]  # on 376x17
+LARGE_TARGET_C = 20.0
+LARGE = [(60, 2, 2048, 2048), (60, 2, 2085, 2085), (60, 2, 2048, 2048 + 37), (72, 17, 6000, 6000), (16, 1, 2048, 2048)]
+# the variants run on ONE shape per family, on the family's first form; SECOND_FORM also on its second
+FORM_VARIANT_SHAPES = [(dict(obs_dim=65, act_dim=17, B=128, M=300), ('chunked', 'per-step')),
+                       (dict(obs_dim=376, act_dim=17, B=64, M=100), ('split', 'wide')),
+                       (dict(obs_dim=60, act_dim=2, B=2085, M=2085), ('balanced', 'strided'))]
+SECOND_FORM = ('losskind1', 'critics-off', 'l2-0.05-clipped', 'seeded')
+
+
+def form_variants() -> 'OrderedDict[str, dict]':
+    v = OrderedDict()
+    v['losskind1'] = dict(loss_kind=1)
+    v['lam-0'] = dict(lam=0.0)
+    v['lam-50'] = dict(lam=50.0)
+    v['nocost'] = dict(use_cost=False)
+    v['actor-off'] = dict(update_actor=False)  # (large batch: the masks move the balanced task boundaries)
+    v['critics-off'] = dict(update_critics=False)
+    v['l2-off'] = dict(use_critic_norm=0)
+    v['l2-0.05'] = dict(critic_norm_coef=0.05)
+    v['l2-0.05-clipped'] = dict(critic_norm_coef=0.05, norm_clip=(1, 0.5))
+    v['entropy-0'] = dict(entropy_coef=0.0)
+    v['clip-0.05'] = dict(clip=0.05)
+    for net in range(3):
+        for fac in (0.5, 0.999, 1.001):
+            v[f'normclip-{NETS[net]}-{fac}'] = dict(norm_clip=(net, fac))
+    v['normclip-all'] = dict(norm_clip=('all', 0.5))
+    v['normclip-off'] = dict(use_max_grad_norm=0)
+    v['seeded'] = dict(seeded_moments=True, t0=(3, 5, 7))
+    v['t0-0'] = dict(seeded_moments=True, t0=(0, 0, 0))
+    v['t0-250000'] = dict(seeded_moments=True, t0=(250000, 250000, 250000))
+    v['lr'] = dict(lr_actor=3e-4, lr_critic=1e-3, seeded_moments=True, t0=(3, 5, 7))
+    return v
+
+
+def form_name(tag: str, kw: dict) -> str:
+    return f"{tag}-{kw['obs_dim']}x{kw['act_dim']}-B{kw['B']}-M{kw['M']}"
+
+
+def wide_kw(od: int, ad: int, B: int = 64, M: int = 100) -> dict:
+    """A case of the wide family: first-layer weights scaled so that the layer does not saturate (make_case)."""
+    return dict(obs_dim=od, act_dim=ad, B=B, M=M, w1_scale=math.sqrt(64.0 / od))
+
+
+def form_table() -> 'OrderedDict[str, dict]':
+    """name -> dict(kw = make_case keyword arguments, paths = the FORMS the case runs on[, tail = (rows, empty chunks)]).
+    As in case_table() an entry changes ONE thing from its family's base configuration; names end in the shape and
+    -B<batch>-M<rows>, which no name of case_table() does."""
+    t = OrderedDict()
+
+    def add(tag, kw, paths, **more):
+        name = form_name(tag, kw)
+        assert name not in t
+        t[name] = dict(kw=kw, paths=tuple(paths), **more)
+
+    # ---- 64 < B <= 1024 on a shape of the narrow pass: cooperating chunk workgroups / several blocks + slab reduce
+    for od, ad in CHUNK_SHAPES:
+        for B, M, tail, empty in CHUNK_BATCHES:
+            add('base', dict(obs_dim=od, act_dim=ad, B=B, M=M), ('per-step', 'chunked'), tail=(tail, empty))
+    add('base', dict(obs_dim=60, act_dim=2, B=1024, M=1025), ('per-step', 'chunked'), tail=(1, 15))  # the upper end
+    # ---- B <= 64 on shapes the narrow pass cannot hold
+    for od, ad in WIDE_SHAPES:
+        add('base', wide_kw(od, ad), ('wide', 'split') + (('split-spread',) if (od, ad) == (376, 17) else ()))
+    for B, M in WIDE_BATCHES:
+        add('base', wide_kw(376, 17, B, M), ('wide', 'split'))
+    # ---- B >= 2048: partial gradients of one minibatch over the whole device
+    for od, ad, B, M in LARGE:
+        add('base', dict(obs_dim=od, act_dim=ad, B=B, M=M, target_c_scale=LARGE_TARGET_C), ('balanced', 'strided'))
+    # ---- the loss / clip / Adam variants on one shape per family
+    for base, forms in FORM_VARIANT_SHAPES:
+        kw0 = (wide_kw(base['obs_dim'], base['act_dim'], base['B'], base['M']) if base['obs_dim'] > 96
+               else dict(base, target_c_scale=LARGE_TARGET_C) if base['B'] >= 2048 else base)
+        for tag, change in form_variants().items():
+            add(tag, dict(kw0, **change), forms if tag in SECOND_FORM else forms[:1])
+    # ---- an extended surrogate above 64 rows: legal on the per-step kernels only, without mask or penalty
+    add('cup', dict(obs_dim=60, act_dim=2, B=128, M=300, update_critics=False, loss_kind=1, ext=dict(kl_coef=1.0),
+                    entropy_coef=0.0), ('per-step',))
+    return t
+
+
+def empty_chunks(B: int, n: int) -> int:
+    """64-row chunks of a B-row step that a minibatch of n rows leaves without a row (chunk c holds rows 64 c ...)."""
+    return (B + 63) // 64 - (n + 63) // 64
 
 
 def zero_moment_twin(kwargs: dict) -> dict:

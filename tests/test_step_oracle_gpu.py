@@ -67,6 +67,8 @@ K_GRAD, K_SCALAR = 16, 16
 
 TABLE = T.case_table()
 PATHS = ('per-step', 'persistent')
+# (the cases of step_twin.form_table() too: tests/test_step_forms_gpu.py runs them through the checks of this file)
+CASES = dict(TABLE, **{_name: _e['kw'] for _name, _e in T.form_table().items()})
 NSTAT = 16
 E32, E32_SINGLE = T.load_f32_error(
     os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'step_twin_f32_error.json'))
@@ -117,7 +119,7 @@ def _figures():
 def reference(name):
     """The case, its zero-moment twin and their float64 results -- computed once, shared by both paths."""
     torch.set_num_threads(1)
-    kw = TABLE[name]
+    kw = CASES[name]
     case = T.make_case(**kw)
     zero = T.make_case(**T.zero_moment_twin(kw)) if case['seeded_moments'] else case
     nmb = len(T.minibatches(case['M'], case['B']))
@@ -135,7 +137,15 @@ def model_cfgs():
 
 
 class Harness:
-    """One case on one path: the device networks, the data, the updater."""
+    """One case on one path: the device networks, the data, the updater.  What depends on the path sits in form()
+    and launch_step(); tests/test_step_forms_gpu.py overrides the two for the other forms of the step."""
+
+    def form(self):
+        """-> (PPOUpdater's persistent flag, the last_path run() must report, whether the form writes the
+        bias-correction columns 10..15, whether a pass is ONE launch -- compared with the twin's float64 chain)."""
+        assert self._lib.load(require_gpu=True).osa_ppo_pass_supported(self.case['obs_dim'], self.case['act_dim'], 64) == 1
+        persistent = self.path == 'persistent'
+        return persistent, self.path, persistent, persistent
 
     def __init__(self, case, path):
         from omnisafe_amd import _lib
@@ -146,7 +156,7 @@ class Harness:
         self._lib = _lib
         self.case, self.path = case, path
         od, ad, M = case['obs_dim'], case['act_dim'], case['M']
-        assert _lib.load(require_gpu=True).osa_ppo_pass_supported(od, ad, 64) == 1
+        persistent, self.last_path, self.bias_columns, self.one_launch = self.form()
         self.ac = ac = ConstraintActorCritic(Box(-np.inf, np.inf, (od,)), Box(-1, 1, (ad,)), model_cfgs(), 4, device=DEV)
         self.views = [getattr(ac, net) for net in T.NETS]
         self.index = [v._flat_index.cpu().numpy() for v in self.views]
@@ -165,7 +175,7 @@ class Harness:
             entropy_coef=hp['entropy_coef'], use_critic_norm=bool(hp['use_critic_norm']),
             critic_norm_coef=hp['critic_norm_coef'], use_max_grad_norm=bool(hp['use_max_grad_norm']),
             max_grad_norm=hp['max_grad_norm'], use_cost=case['use_cost'], loss_kind=case['loss_kind'],
-            update_actor=case['update_actor'], persistent=(path == 'persistent'),
+            update_actor=case['update_actor'], persistent=persistent,
             update_critics=case['update_critics'], ext=ext)
         upd.hp.lr_actor, upd.hp.lr_critic = hp['lr_actor'], hp['lr_critic']
         if ext is not None:  # the PRESCRIBED behaviour policy, not a snapshot of the actor
@@ -205,11 +215,16 @@ class Harness:
     # ---- launches
     def one_step(self, state, k):
         """Minibatch k of the pass as one launch from `state` -> (state before, state after, statistics row)."""
+        self.load(state)
+        before = self.read()
+        stats = self.launch_step(k)
+        return before, self.read(), stats
+
+    def launch_step(self, k):
+        """Launches minibatch k on the state the device holds -> its statistics row."""
         upd, lib = self.upd, self._lib
         s, n = T.minibatches(self.case['M'], self.case['B'])[k]
         idx = self.perm[s:s + n]
-        self.load(state)
-        before = self.read()
         stats = torch.zeros(1, NSTAT, device=DEV)
         if self.path == 'per-step':
             upd.minibatch(self.data, idx, n, self.lam, stats[0])
@@ -223,7 +238,7 @@ class Harness:
                 *upd._operands(self.data, idx, n, self.case['B']), lib.ptr(self.lam), C.byref(upd.hp), upd.loss_kind,
                 self.mask, lib.ptr(stats), ext, lib.stream_ptr()), 'osa_ppo_pass_ext')
         torch.cuda.synchronize()
-        return before, self.read(), stats[0].cpu().numpy()
+        return stats[0].cpu().numpy()
 
     def whole_pass(self, state):
         self.load(state)
@@ -231,7 +246,7 @@ class Harness:
         hp = self.case['hp']
         out = self.upd.run(self.data, self.lam, perms=[self.perm], actor_lr=hp['lr_actor'], critic_lr=hp['lr_critic'])
         torch.cuda.synchronize()
-        assert self.upd.last_path == self.path
+        assert self.upd.last_path == self.last_path, (self.upd.last_path, self.last_path)
         return before, self.read(), out['stats'].cpu().numpy()
 
 
@@ -329,7 +344,7 @@ def check_first_step(name, path, h, ref, k, failures):
         record(name, path, kind + '/moments', net, "v' - (1 - b2) g^2 [ulp]", worst, 4.0)
         if not worst <= 4.0:
             failures.append((kind, net, "v' against (1 - b2) g_kernel^2, ulp", worst))
-    if path == 'persistent':
+    if h.bias_columns:
         check_bias_columns(h, kind, stats, after['t'], failures)
     check_adam(name, path, kind, h, before, after, failures)
     return grads, {net: after['v'][net] for net in h.nets}
@@ -378,7 +393,7 @@ def check_chain(name, path, h, ref, failures):
     rows and final state against the twin's float64 chain."""
     case, e32 = ref['case'], E32[name]
     nmb = len(T.minibatches(case['M'], case['B']))
-    if path == 'per-step':
+    if not h.one_launch:
         state = case['state']
         for k in range(nmb):
             before, after, stats = h.one_step(state, k)
@@ -435,12 +450,10 @@ def check_chain(name, path, h, ref, failures):
                 failures.append(('pass', net, t, 'params', 'final state / per-element tolerance', worst))
 
 
-@pytest.mark.parametrize('path', PATHS)
-@pytest.mark.parametrize('name', list(TABLE))
-def test_step_against_the_float64_twin(name, path):
+def check_case(name, path, h):
+    """Every check of this file on one case and one harness."""
     ref = reference(name)
     case = ref['case']
-    h = Harness(case, path)
     failures = []
     nmb = len(T.minibatches(case['M'], case['B']))
     grads0 = None
@@ -460,3 +473,9 @@ def test_step_against_the_float64_twin(name, path):
                 final['blocks']['params'][T.NETS.index(net)], before['blocks']['params'][T.NETS.index(net)])]
             assert moved == list(h.nets)
     assert not failures, failures
+
+
+@pytest.mark.parametrize('path', PATHS)
+@pytest.mark.parametrize('name', list(TABLE))
+def test_step_against_the_float64_twin(name, path):
+    check_case(name, path, Harness(reference(name)['case'], path))

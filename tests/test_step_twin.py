@@ -7,7 +7,10 @@ tests/test_step_oracle_gpu.py compare the 64-row step kernels with.
     agrees with oracle/np_oracle.py's actor_step / critic_step (the reference's own torch calls) at the golden's
     inputs: YAML defaults, a norm clip that bites, a non-zero entropy bonus.  This ties the twin to the real
     reference, not to this project's reading of it;
-  * the coverage conditions of step_twin.make_case hold for every case of the GPU table;
+  * the coverage conditions of step_twin.make_case hold for every case of the GPU table -- and of form_table(), the
+    table of tests/test_step_forms_gpu.py, where they include that a scaled first layer does not saturate, that the
+    named ragged tails leave the named chunk workgroups empty and that the shapes select the forms they are listed for;
+  * the cases of case_table() keep the entries of the measuring stick they had before form_table() joined the file;
   * the ragged tail of a pass is the step of its rows as a minibatch of their own;
   * the measuring stick tests/golden/step_twin_f32_error.json (float32 run against float64 run of the same code, per
     case, network and tensor) reproduces within a factor 2.
@@ -37,7 +40,11 @@ import step_twin as T  # noqa: E402
 
 ERR_FILE = os.path.join(HERE, 'golden', 'step_twin_f32_error.json')
 TABLE = T.case_table()
+FORM_TABLE = T.form_table()  # the forms beyond one 64-row workgroup per network (tests/test_step_forms_gpu.py)
+CASES = dict(TABLE, **{name: e['kw'] for name, e in FORM_TABLE.items()})
 RTOL, ATOL = 2e-6, 2e-6
+# sha256 of the measuring stick's entries for case_table(), as they stood before form_table() was added to the file
+NARROW_E32_SHA256 = '9e8ff14f4dbb9ff74d5aef64304c90645c71e6629dd5eabb2748713761d1da71'
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -209,7 +216,7 @@ def cases():
 
     def get(name):
         if name not in cache:
-            cache[name] = T.make_case(**TABLE[name])
+            cache[name] = T.make_case(**CASES[name])
         return cache[name]
 
     return get
@@ -224,10 +231,51 @@ def test_table_shapes_are_on_the_narrow_pass():
         assert lib.osa_ppo_pass_supported(od, ad, 64) == 1, (od, ad)
 
 
-@pytest.mark.parametrize('name', list(TABLE))
+def test_form_table_shapes_select_their_forms():
+    """The host-side conditions of PPOUpdater.run's selection, per family of form_table(): the chunked and large-batch
+    cases sit on shapes of the narrow pass with 64 < B <= 1024 / B >= 2048, the wide cases on shapes it refuses and
+    both wide kernels take, with B <= 64.  (That the device then accepts the form is asserted on the GPU.)"""
+    from omnisafe_amd import _lib
+
+    lib = _lib.load()
+    assert not set(FORM_TABLE) & set(TABLE)
+    for name, e in FORM_TABLE.items():
+        kw = e['kw']
+        od, ad, B = kw['obs_dim'], kw['act_dim'], kw['B']
+        assert set(e['paths']) <= set(T.FORMS), name
+        narrow = lib.osa_ppo_pass_supported(od, ad, 64) == 1
+        if set(e['paths']) & {'wide', 'split', 'split-spread'}:
+            assert not narrow and B <= 64 and set(e['paths']) <= {'wide', 'split', 'split-spread'}, name
+            assert lib.osa_ppo_wide_pass_supported(od, ad, 64) == 1 and lib.osa_ppo_split_pass_supported(od, ad, 64) == 1
+            assert kw['w1_scale'] == (64.0 / od) ** 0.5
+        elif set(e['paths']) & {'balanced', 'strided'}:
+            assert narrow and B >= 2048 and set(e['paths']) <= {'balanced', 'strided'}, name
+        else:
+            assert narrow and 64 < B <= 1024 and set(e['paths']) <= {'per-step', 'chunked'}, name
+            assert kw.get('ext') is None or e['paths'] == ('per-step',), name
+
+
+@pytest.mark.parametrize('name', list(CASES))
 def test_case_reaches_its_branches(cases, name):
-    info = T.check_coverage(cases(name))
+    case = cases(name)
+    info = T.check_coverage(case)
     print(name, info)
+    if name in FORM_TABLE and 'tail' in FORM_TABLE[name]:
+        # the ragged tail the entry names: its rows, and the 64-row chunk workgroups of the chunked pass it leaves empty
+        rows, empty = FORM_TABLE[name]['tail']
+        n = T.minibatches(case['M'], case['B'])[-1][1]
+        assert (n, T.empty_chunks(case['B'], n)) == (rows, empty), (name, n, T.empty_chunks(case['B'], n))
+
+
+def test_narrow_cases_keep_their_measuring_stick():
+    """form_table()'s cases were ADDED to tests/golden/step_twin_f32_error.json: every case of case_table() still maps,
+    network by network, to the figures it had (w1_scale = 1 leaves make_case's numbers and streams where they were)."""
+    import hashlib
+
+    blob = json.load(open(ERR_FILE))
+    old = {name: {net: blob['blocks'][b] for net, b in sorted(blob['cases'][name].items())} for name in TABLE}
+    digest = hashlib.sha256(json.dumps([blob['keys'], old], sort_keys=True).encode()).hexdigest()
+    assert digest == NARROW_E32_SHA256
 
 
 def test_ragged_tail_is_a_minibatch_of_its_own(cases):
@@ -259,8 +307,8 @@ def test_f32_measuring_stick_reproduces(cases):
     the worst of ROW_ORDERS row orders (the GPU tests' unit) and the single run with the rows as drawn.
     (`python tests/test_step_twin.py` rewrites the file.)"""
     want = T.load_f32_error(ERR_FILE)
-    assert sorted(want[0]) == sorted(TABLE)
-    for name in TABLE:
+    assert sorted(want[0]) == sorted(CASES)
+    for name in CASES:
         got = T.f32_error(cases(name))
         for which, g, w in zip(('worst', 'single'), got, want):
             assert sorted(g) == sorted(w[name]), name
@@ -271,9 +319,15 @@ def test_f32_measuring_stick_reproduces(cases):
                     assert a <= 2 * b and b <= 2 * a, (which, name, net, k, e, w[name][net][k])
 
 
-if __name__ == '__main__':  # writes the measuring stick
+if __name__ == '__main__':  # writes the measuring stick (`--forms`: keeps case_table()'s entries as recorded, adds form_table()'s)
     torch.set_num_threads(1)
-    blob = T.pack_f32_error({nm: T.f32_error(T.make_case(**kw)) for nm, kw in TABLE.items()})
+    if '--forms' in sys.argv:
+        old = T.load_f32_error(ERR_FILE)
+        table = {nm: (old[0][nm], old[1][nm]) for nm in TABLE}
+        table.update((nm, T.f32_error(T.make_case(**e['kw']))) for nm, e in FORM_TABLE.items())
+        blob = T.pack_f32_error(table)
+    else:
+        blob = T.pack_f32_error({nm: T.f32_error(T.make_case(**kw)) for nm, kw in CASES.items()})
     with open(ERR_FILE, 'w') as fh:
         fh.write('{"keys": ' + json.dumps(blob['keys']) + ',\n"blocks": [\n'
                  + ',\n'.join(json.dumps(b) for b in blob['blocks']) + '],\n"cases": {\n'

@@ -1,7 +1,14 @@
-"""profiles/step_twin_error.md from the figures tests/test_step_oracle_gpu.py records on the GPU:
+"""profiles/step_twin_error.md from the figures tests/test_step_oracle_gpu.py records on the GPU, and
+profiles/step_forms_error.md from those of tests/test_step_forms_gpu.py (one file per run):
 
     OSA_STEP_TWIN_FIGURES=figures.json python -m pytest -m gpu tests/test_step_oracle_gpu.py
     python tools/step_twin_report.py figures.json > profiles/step_twin_error.md
+    OSA_STEP_TWIN_FIGURES=forms.json python -m pytest -m gpu tests/test_step_forms_gpu.py
+    python tools/step_twin_report.py forms.json > profiles/step_forms_error.md
+
+The columns of the tables are the paths found in the figures, in their order of appearance (`per-step / persistent`
+for the 64-row table; per-step, chunked, wide, split, split-spread, balanced, strided for the forms, where a case runs
+on the forms of its family only and the other cells stay `-`).
 
 A figure is (case, path, kind, network, what, measured, bound, single); kinds `<step>/grad` and `<step>/scalar` are ratios
 error / max(e32, 2^-22), `<step>/adam` the parameter residual over its derived bound, `<step>/moments` ulps,
@@ -15,6 +22,12 @@ import sys
 
 def main(path: str) -> None:
     fig = json.load(open(path))
+    paths = []
+    for f in fig:
+        if f[1] not in paths:
+            paths.append(f[1])
+    narrow = paths == ['per-step', 'persistent']
+    per_path = collections.defaultdict(lambda: (0.0, None))  # (class, path) -> worst
     by = collections.defaultdict(float)   # (class, case, net, what, path) -> worst over the steps
     worst = collections.defaultdict(lambda: (0.0, None))
     bound = {}
@@ -29,14 +42,20 @@ def main(path: str) -> None:
         bound[cls] = bnd
         if meas > worst[cls][0]:
             worst[cls] = (meas, (case, p, kind, net, what))
+        if meas > per_path[(cls, p)][0]:
+            per_path[(cls, p)] = (meas, (case, p, kind, net, what))
     out = []
     w = out.append
-    w('# The 64-row optimiser step against its float64 twin: measured error ratios (MI355X)\n')
-    w('Written by `tools/step_twin_report.py` from one run of `tests/test_step_oracle_gpu.py` '
-      f'({len(fig)} figures, {len({f[0] for f in fig})} cases, both paths).  A gradient or scalar entry is '
+    cols_txt = ' / '.join(paths)
+    w('# The 64-row optimiser step against its float64 twin: measured error ratios (MI355X)\n' if narrow else
+      '# The chunked, wide, split and large-batch steps against the float64 twin: measured error ratios (MI355X)\n')
+    w('Written by `tools/step_twin_report.py` from one run of '
+      + ('`tests/test_step_oracle_gpu.py` ' if narrow else '`tests/test_step_forms_gpu.py` ') +
+      f'({len(fig)} figures, {len({f[0] for f in fig})} cases, '
+      + ('both paths' if narrow else f'{len({(f[0], f[1]) for f in fig})} (case, form) pairs') + ').  A gradient or scalar entry is '
       '`error / max(e32, 2^-22)`: the relative L2 error of the kernel against `tests/step_twin.py` in float64, in units of '
       'what the float32 run of the same twin loses (`tests/golden/step_twin_f32_error.json`), worst over the '
-      'minibatches of the case.  Columns `per-step / persistent`.\n')
+      f'minibatches of the case.  Columns `{cols_txt}`' + ('' if narrow else ' (`-`: the case does not run on that form)') + '.\n')
     w('## Summary\n')
     w('| quantity | worst measured | where | bound in the test |')
     w('|---|---|---|---|')
@@ -48,7 +67,23 @@ def main(path: str) -> None:
             m, (case, p, kind, net, what) = worst[cls]
             w(f'| {names[cls]} | {m:.2f} | {case}, {p}, {kind.split("/")[0]}, {net}, {what} | {bound[cls]:g} |')
     w('')
-    w('K = the smallest power of two that is at least twice the worst measured ratio.\n')
+    w('K = the smallest power of two that is at least twice the worst measured ratio.\n' if narrow else
+      'The bounds are those of the 64-row table (`tests/test_step_oracle_gpu.py`); nothing was fitted to these forms.  '
+      + ('Every quantity stayed inside its bound in the units of the float32 twin (the sums over up to 6000 rows and '
+         'the slab sums of the large-batch forms included): no unit was re-derived for these forms.\n'
+         if all(worst[c][0] <= bound[c] for c in worst) else
+         'NOT every quantity stayed inside its bound: see the rows above.\n'))
+    if not narrow:
+        w('## Worst ratio per form\n')
+        w('| form | ' + ' | '.join(names[c] for c in ('grad', 'scalar', 'adam', 'moments', 'state')) + ' |')
+        w('|---|' + '---|' * 5)
+        for p in paths:
+            cells = []
+            for cls in ('grad', 'scalar', 'adam', 'moments', 'state'):
+                m, where = per_path[(cls, p)]
+                cells.append('-' if where is None else f'{m:.2f} ({where[0]}, {where[3]}, {where[4]})')
+            w(f'| {p} | ' + ' | '.join(cells) + ' |')
+        w('')
     w('The unit `e32` of these ratios is the worst of four orders of the minibatch\'s rows (for a critic\'s one-element '
       'output bias: the larger of that and the typical size of the sum of its rows\' forward errors).  Against the '
       'float32 run with the rows as drawn alone -- one draw of the rounding error of every one-element quantity -- the '
@@ -82,18 +117,19 @@ def main(path: str) -> None:
             for case in cases:
                 cells = []
                 for c in cols:
-                    a, b = by.get((cls, case, net, c, 'per-step')), by.get((cls, case, net, c, 'persistent'))
-                    cells.append('' if a is None and b is None else f'{a:.2f} / {b:.2f}')
+                    vals = [by.get((cls, case, net, c, p)) for p in paths]
+                    cells.append('' if all(v is None for v in vals)
+                                 else ' / '.join('-' if v is None else f'{v:.2f}' for v in vals))
                 if any(cells):
                     w(f'| {case} | ' + ' | '.join(cells) + ' |')
             w('')
     w('## Adam, moments and chained state, per case\n')
-    w('| case | network | quantity | per-step | persistent |')
-    w('|---|---|---|---|---|')
-    for key in sorted(k for k in by if k[0] in ('adam', 'moments') and k[4] == 'per-step'):
-        cls, case, net, what, _ = key
-        b = by.get((cls, case, net, what, 'persistent'))
-        w(f'| {case} | {net} | {what} | {by[key]:.2f} | {b:.2f} |')
+    w('| case | network | quantity | ' + ' | '.join(paths) + ' |')
+    w('|---|---|---|' + '---|' * len(paths))
+    for key in sorted({k[:4] for k in by if k[0] in ('adam', 'moments')}):
+        cls, case, net, what = key
+        vals = [by.get(key + (p,)) for p in paths]
+        w(f'| {case} | {net} | {what} | ' + ' | '.join('-' if v is None else f'{v:.2f}' for v in vals) + ' |')
     sys.stdout.write('\n'.join(out) + '\n')
 
 
