@@ -14,12 +14,32 @@ base/trpo.py:56-222 and second_order/cpo.py:57-462 on PADDED flat actor vectors 
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
 from . import _lib
 from . import distributed as dist
 from .models import ConstraintActorCritic, HParams
+
+
+FVP_FAST = 'osa_fvp_kernel + osa_fvp_reduce_kernel'
+FVP_GENERAL = 'osa_mb_grad_kernel<loss_kind 2: Fisher-vector product> + osa_slab_reduce_kernel'
+FVP_LAYERWISE = 'gm_gemm_kernel (layer-wise Fisher-vector product)'
+
+
+def fvp_kernel_name(ac, M: int) -> str:
+    """The kernels one Fisher-vector product over M rows runs on: osa_launch_fvp_fast's conditions
+    (csrc/fvp_kernel.hip), restated on the host -- 64-wide tanh, at most five 16-column blocks of inputs, more than
+    64 rows, and both parameter blocks plus the five tiles inside 160 KB of LDS (act_dim > 16 fits up to 48 inputs)."""
+    if getattr(ac, 'general', False):
+        return FVP_LAYERWISE
+    lay, H = ac.layout, 64
+    padded = H * (lay.INP + 4) + H + H * (H + 4) + H + lay.OUTP * (H + 4) + 2 * lay.OUTP
+    lds = (2 * padded + 4 * H * 68 + lay.OUTP * 68) * 4
+    fast = (ac.hidden == 64 and lay.KB <= 5 and lay.OUTP <= 32 and 64 < M <= 1 << 30 and lds <= 160 * 1024
+            and os.environ.get('OSA_FVP_FAST') != '0')
+    return FVP_FAST if fast else FVP_GENERAL
 
 
 class TrustRegionSolver:  # pylint: disable=too-many-instance-attributes
@@ -126,16 +146,7 @@ class TrustRegionSolver:  # pylint: disable=too-many-instance-attributes
                                              _lib.stream_ptr()), 'osa_actor_fvp_raw')
         if ev is not None:
             ev[1].record()
-            import os
-
-            if getattr(ac, 'general', False):
-                name = 'gm_gemm_kernel (layer-wise Fisher-vector product)'
-            elif ((ac.hidden & 0xFFFF) == 64 and ac.obs_dim <= 80 and ac.act_dim <= 16 and M > 64 and (ac.hidden >> 16) == 0
-                  and os.environ.get('OSA_FVP_FAST', '1') != '0'):  # the shapes of csrc/fvp_kernel.hip
-                name = 'osa_fvp_kernel + osa_fvp_reduce_kernel'
-            else:
-                name = 'osa_mb_grad_kernel<loss_kind 2: Fisher-vector product> + osa_slab_reduce_kernel'
-            self.profile_events.append((name, M, ev))
+            self.profile_events.append((fvp_kernel_name(ac, M), M, ev))
         raw.copy_(ac.grads[0])
         dist.all_reduce_avg_(raw)  # C2: one flat message
         out = out if out is not None else torch.empty_like(v)

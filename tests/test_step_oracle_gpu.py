@@ -421,7 +421,12 @@ def check_chain(name, path, h, ref, failures):
     for k, r in enumerate(chain):  # the statistics row of EVERY step, bias-correction columns included
         check_scalars(name, path, f'chain{k}', r, stats[k], e32, failures)
         check_bias_columns(h, f'chain{k}', stats[k], {net: before['t'][net] + k + 1 for net in h.nets}, failures)
-    for net in h.nets:
+    check_final_state(name, path, h.nets, chain, e32, final, failures)
+
+
+def check_final_state(name, path, nets, chain, e32, final, failures):
+    """The state a chain of float32 steps leaves against the twin's float64 chain of the same steps."""
+    for net in nets:
         # the steps' tolerances add up (a step inherits b1 of the previous first moment's error); a parameter inherits,
         # ELEMENT BY ELEMENT, ss dm / den + |D| dv / (2 v') of its step's moments on top of the Adam bound (dm, dv: the
         # tensor's L2 tolerances, which bound every element's error), so an entry with a tiny second moment loosens
