@@ -1,8 +1,9 @@
-// Per-env transitions of the device-resident vector envs, shared by their per-step kernels
-// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_nav_env_kernel, osa_circle_env_kernel,
-// osa_car_goal_env_kernel, osa_car_circle_env_kernel) and the persistent evaluation kernel (eval_kernels.hip).  Every random number is a Philox4x32-10 draw keyed by (seed, stream
-// position `step`, env index n), so a caller that replays env n at positions 0, 1, 2, ... sees the same episode as the
-// per-step launches.
+// The device-resident vector envs: their arithmetic as free functions, and at the end of the file one description per
+// family (OsaSynthEnv, OsaReachEnv, OsaNavEnv<robot, task>) that binds it together for the per-step kernels
+// (rollout_kernels.hip: osa_synth_env_kernel, osa_reach_env_kernel, osa_goal_env_kernel<robot>,
+// osa_circle_env_kernel<robot, lanes>) and the persistent evaluation kernel (eval_kernels.hip).  Every random number is
+// a Philox4x32-10 draw keyed by (seed, stream position `step`, env index n), so a caller that replays env n at
+// positions 0, 1, 2, ... sees the same episode as the per-step launches.
 #pragma once
 #include "mlp_device.h"
 
@@ -109,7 +110,6 @@ __device__ __forceinline__ void osa_reach_transition(float (&s)[6], float a0_in,
 #define OSA_NAV_DYN 10    // leading floats of the row that a transition changes
 #define OSA_NAV_HAZ 12    // first hazard column of the row
 #define OSA_NAV_VASE 32   // first vase column of the row
-#define OSA_NAV_OBS 60    // observation columns
 
 __device__ __forceinline__ int osa_nav_hazards(int level) { return level == 0 ? 0 : (level == 1 ? 8 : 10); }
 __device__ __forceinline__ int osa_nav_vases(int level) { return level == 0 ? 0 : (level == 1 ? 1 : 10); }
@@ -268,17 +268,6 @@ __device__ __forceinline__ void osa_nav_arrive(float (&d)[OSA_NAV_DYN], const fl
   }
 }
 
-// One transition of env n at position `pos` under the (unclamped) env action (a0, a1), all but its cost (which is a
-// function of the new position: osa_nav_cost, or the caller's own walk over the objects).
-__device__ __forceinline__ void osa_nav_advance(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
-                                                float a0_in, float a1_in, unsigned long long key,
-                                                unsigned long long pos, int n, float& r) {
-  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
-  float mx, my;
-  osa_nav_move(d, a0_in, a1_in, mx, my);
-  osa_nav_arrive(d, row, level, d0, key, pos, n, r);
-}
-
 // An object o seen from the state: body-frame coordinates (bx, by) of r = o - p and |r|.
 __device__ __forceinline__ void osa_nav_see(const float (&d)[OSA_NAV_DYN], float ox, float oy, float& bx, float& by,
                                             float& dist) {
@@ -311,14 +300,6 @@ __device__ __forceinline__ float osa_nav_cost(const float (&d)[OSA_NAV_DYN], con
   return hit ? 1.f : 0.f;
 }
 
-// The whole transition, one lane per env (eval_kernels.hip).
-__device__ __forceinline__ void osa_nav_transition(float (&d)[OSA_NAV_DYN], const float* __restrict__ row, int level,
-                                                   float a0_in, float a1_in, unsigned long long key,
-                                                   unsigned long long pos, int n, float& r, float& c) {
-  osa_nav_advance(d, row, level, a0_in, a1_in, key, pos, n, r);
-  c = osa_nav_cost(d, row, level);
-}
-
 // Columns 0 - 11 of the observation row: 0 f, 1 f - f_prev, 2 t, 3 u_x, 4 u_y, 5 - 11 zero.
 __device__ __forceinline__ float osa_nav_sensor_col(const float (&d)[OSA_NAV_DYN], int col) {
   float v = 0.f;
@@ -330,22 +311,11 @@ __device__ __forceinline__ float osa_nav_sensor_col(const float (&d)[OSA_NAV_DYN
   return v;
 }
 
-// Column `col` of the current state row.
-__device__ __forceinline__ float osa_nav_state_col(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
-                                                   int col) {
-  float v = col >= OSA_NAV_DYN ? row[col] : 0.f;
-#pragma unroll
-  for (int k = 0; k < OSA_NAV_DYN; ++k)
-    if (col == k) v = d[k];
-  return v;
-}
-
-// Column `col` of the observation row: 0 - 11 osa_nav_sensor_col, 12 - 27 goal lidar, 28 - 43 hazard lidar, 44 - 59
+// Lidar column b of the observation row, one lane for the whole walk: 0 - 15 goal lidar, 16 - 31 hazard lidar, 32 - 47
 // vase lidar.  An object in bin k reads max(0, 1 - |r| / LIDAR_MAX) there; a bin reads the maximum over its class.
-__device__ __forceinline__ float osa_nav_obs_col(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
-                                                 int level, int col) {
-  if (col < 12 || col >= OSA_NAV_OBS) return osa_nav_sensor_col(d, col);
-  const int cls = (col - 12) >> 4, k = (col - 12) & 15;
+__device__ __forceinline__ float osa_nav_lidar_col(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
+                                                   int level, int b) {
+  const int cls = b >> 4, k = b & 15;
   const int cnt = cls == 0 ? 1 : (cls == 1 ? osa_nav_hazards(level) : osa_nav_vases(level));
   const float* __restrict__ objs = row + (cls == 0 ? 8 : (cls == 1 ? OSA_NAV_HAZ : OSA_NAV_VASE));
   float out = 0.f;
@@ -367,8 +337,6 @@ __device__ __forceinline__ float osa_nav_obs_col(const float (&d)[OSA_NAV_DYN], 
 // reset.  The numpy twin is tests/circle_twin.py.
 // ------------------------------------------------------------------------------------------------
 #define OSA_CIRCLE_KEY 0xE7037ED1A0B428DBull
-#define OSA_CIRCLE_STATE 8  // floats per state row
-#define OSA_CIRCLE_OBS 28   // observation columns
 
 // The fresh state of a reset: p = 0.4 (u0, u1) (inside every wall), heading (u2, u3) normalised, the rest 0; u0 .. u3
 // reset uniforms 0 .. 3 (Philox block 1).
@@ -401,21 +369,12 @@ __device__ __forceinline__ void osa_circle_pay(const float (&d)[OSA_NAV_DYN], in
   c = out ? 1.f : 0.f;
 }
 
-// One transition under the (unclamped) env action (a0, a1).
-__device__ __forceinline__ void osa_circle_transition(float (&d)[OSA_NAV_DYN], int level, float a0_in, float a1_in,
-                                                      float& r, float& c) {
-  float mx, my;
-  osa_nav_move(d, a0_in, a1_in, mx, my);
-  osa_circle_pay(d, level, mx, my, r, c);
-}
-
-// Column `col` of the observation row: 0 - 11 osa_nav_sensor_col, 12 - 27 the lidar of the origin (bin k reads
-// max(0, 1 - |p| / 3) when the origin lies in sector k; at p = (0, 0) no bin does), 0 past them.
-__device__ __forceinline__ float osa_circle_obs_col(const float (&d)[OSA_NAV_DYN], int col) {
-  if (col < 12 || col >= OSA_CIRCLE_OBS) return osa_nav_sensor_col(d, col);
+// Lidar column k of the observation row, the lidar of the origin: bin k reads max(0, 1 - |p| / 3) when the origin lies
+// in sector k; at p = (0, 0) no bin does.
+__device__ __forceinline__ float osa_circle_lidar_col(const float (&d)[OSA_NAV_DYN], int k) {
   float bx, by, dist;
   osa_nav_see(d, 0.f, 0.f, bx, by, dist);
-  return osa_nav_in_bin(col - 12, bx, by) ? osa_nav_reading(dist) : 0.f;
+  return osa_nav_in_bin(k, bx, by) ? osa_nav_reading(dist) : 0.f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -430,11 +389,8 @@ __device__ __forceinline__ float osa_circle_obs_col(const float (&d)[OSA_NAV_DYN
 // arena of SynthNavGoal<l> with seed s (robots compared on identical layouts, one reset in the numpy twins).
 // Observation: 24 sensor columns (osa_car_sensor_col), then the task's lidars.  The numpy twin is tests/car_twin.py.
 // ------------------------------------------------------------------------------------------------
-#define OSA_CAR_SENSORS 24       // sensor columns of the Car
-#define OSA_CAR_GOAL_OBS 72      // observation columns of SynthNavCarGoal
-#define OSA_CAR_CIRCLE_OBS 40    // observation columns of SynthNavCarCircle
-#define OSA_CAR_CIRCLE_STATE 12  // floats per state row of SynthNavCarCircle
-#define OSA_CAR_WHEELS 10        // column of w_l in either state row
+#define OSA_CAR_SENSORS 24  // sensor columns of the Car
+#define OSA_CAR_WHEELS 10   // column of w_l in either state row
 
 // Sensor columns: 0 f, 1 f - f_prev, 2 t, 3 u_x, 4 u_y, 5 w_l, 6 w_r, 7 t - t_prev, 0 past them.
 __device__ __forceinline__ float osa_car_sensor_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2], int col) {
@@ -445,46 +401,223 @@ __device__ __forceinline__ float osa_car_sensor_col(const float (&d)[OSA_NAV_DYN
   return v;
 }
 
-// One SynthNavCarGoal transition of env n at position `pos`, all but its cost (as osa_nav_advance).
-__device__ __forceinline__ void osa_car_goal_advance(float (&d)[OSA_NAV_DYN], float (&w)[2],
-                                                     const float* __restrict__ row, int level, float a0_in,
-                                                     float a1_in, unsigned long long key, unsigned long long pos,
-                                                     int n, float& r) {
-  const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
-  float mx, my;
-  osa_car_move(d, w, a0_in, a1_in, mx, my);
-  osa_nav_arrive(d, row, level, d0, key, pos, n, r);
-}
+// ------------------------------------------------------------------------------------------------
+// What a family IS: one description each, the only thing the per-step kernels and the evaluation kernel know of an env.
+//   STATE   floats per state row                     OBS    native observation columns
+//   DYN     leading state floats a transition changes ACT    least action columns
+//   TRACE   state floats of an evaluator trace record LDS_ROW  whether the row's objects live in LDS (`row` below)
+//   Regs    what the registers hold of a row; load / store move it from and to the row
+//   fresh   the state after a reset                  advance   one transition (a Goal task leaves its cost to the
+//   obs_col / state_col   one column of either row              caller's walk over the objects), transition: with it
+// Everything works on env `n` at position `pos` of the Philox stream `seed` (OsaEnvAt).  The SynthNav families are a
+// robot {OsaPoint, OsaCar} x a task {OsaGoal, OsaCircle}; the structs only bind the arithmetic above together.
+// A new family is modelled on OsaNavEnv (or, with its state in registers and no robot, on OsaReachEnv), which have every
+// member; OsaSynthEnv is the exception and no template.
+// ------------------------------------------------------------------------------------------------
+struct OsaEnvAt {
+  unsigned long long seed, pos;
+  int n, level;  // (level: the SynthNav families'; the others pass 0)
+  float cost_p;  // the noise env's cost probability, its one parameter; the other families pass 0 and never read it
+};
 
-// One SynthNavCarCircle transition.
-__device__ __forceinline__ void osa_car_circle_transition(float (&d)[OSA_NAV_DYN], float (&w)[2], int level,
-                                                          float a0_in, float a1_in, float& r, float& c) {
-  float mx, my;
-  osa_car_move(d, w, a0_in, a1_in, mx, my);
-  osa_circle_pay(d, level, mx, my, r, c);
-}
+// Synth*-v0: noise, so only half a description.  It has no state (no load / store, an empty Regs and fresh), its
+// observation is drawn pair-wise by the callers (osa_synth_obs_pair; no obs_col), it takes no action (transition ignores
+// it) and any width will do: OBS and ACT are the least widths the entry points accept, not native ones.
+struct OsaSynthEnv {
+  static constexpr int STATE = 0, OBS = 1, DYN = 0, ACT = 1, TRACE = 0;
+  static constexpr bool LDS_ROW = false;
+  struct Regs {};
+  static __device__ __forceinline__ void fresh(Regs&, const OsaEnvAt&, const float*) {}
+  static __device__ __forceinline__ void transition(Regs&, const float*, const OsaEnvAt& at, float, float, float& r,
+                                                    float& c) {
+    uint32_t w[4];
+    osa_philox(at.seed ^ OSA_SYNTH_RC_KEY, at.pos, (unsigned long long)at.n, w);
+    r = osa_synth_reward(w);
+    c = osa_synth_cost(w, at.cost_p);
+  }
+  static __device__ __forceinline__ float state_col(const Regs&, const float*, int) { return 0.f; }
+};
 
-// Column `col` of the SynthNavCarGoal observation row, one lane for the whole row (eval_kernels.hip): 0 - 23
-// osa_car_sensor_col, 24 - 71 the three lidars (columns 12 - 59 of osa_nav_obs_col), 0 past them.
-__device__ __forceinline__ float osa_car_goal_obs_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
-                                                      const float* __restrict__ row, int level, int col) {
-  if (col < OSA_CAR_SENSORS || col >= OSA_CAR_GOAL_OBS) return osa_car_sensor_col(d, w, col);
-  return osa_nav_obs_col(d, row, level, col - (OSA_CAR_SENSORS - 12));
-}
+// SynthReach-v0: the six state floats in registers (the row pads them to eight).
+struct OsaReachEnv {
+  static constexpr int STATE = 8, OBS = 6, DYN = 6, ACT = 2, TRACE = 6;
+  static constexpr bool LDS_ROW = false;
+  struct Regs {
+    float s[6];
+  };
+  static __device__ __forceinline__ void load(Regs& s, const float* __restrict__ srow) {
+#pragma unroll
+    for (int k = 0; k < DYN; ++k) s.s[k] = srow[k];
+  }
+  static __device__ __forceinline__ void store(const Regs& s, float* __restrict__ srow) {
+#pragma unroll
+    for (int k = 0; k < DYN; ++k) srow[k] = s.s[k];
+  }
+  static __device__ __forceinline__ void fresh(Regs& s, const OsaEnvAt& at, const float*) {
+    uint32_t w0[4], w1[4];
+    osa_philox(at.seed ^ OSA_REACH_KEY, at.pos, ((unsigned long long)at.n << 20) + 1, w0);
+    osa_philox(at.seed ^ OSA_REACH_KEY, at.pos, ((unsigned long long)at.n << 20) + 2, w1);
+    osa_reach_fresh(w0, w1, s.s);
+  }
+  static __device__ __forceinline__ void transition(Regs& s, const float*, const OsaEnvAt& at, float a0, float a1,
+                                                    float& r, float& c) {
+    uint32_t w1[4];
+    osa_philox(at.seed ^ OSA_REACH_KEY, at.pos, ((unsigned long long)at.n << 20) + 2, w1);
+    osa_reach_transition(s.s, a0, a1, w1, r, c);
+  }
+  static __device__ __forceinline__ float obs_col(const Regs& s, const float*, int, int col) {
+    return osa_reach_obs_col(s.s, col);
+  }
+  static __device__ __forceinline__ float state_col(const Regs& s, const float*, int col) {
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < DYN; ++k)
+      if (col == k) v = s.s[k];
+    return v;
+  }
+};
 
-// Column `col` of the SynthNavCarCircle observation row: 0 - 23 osa_car_sensor_col, 24 - 39 the lidar of the origin
-// (osa_circle_obs_col's), 0 past them.
-__device__ __forceinline__ float osa_car_circle_obs_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2], int col) {
-  if (col < OSA_CAR_SENSORS || col >= OSA_CAR_CIRCLE_OBS) return osa_car_sensor_col(d, w, col);
-  return osa_circle_obs_col(d, col - (OSA_CAR_SENSORS - 12));
-}
+// The robots.  A robot is the registers it adds to the task's `d`: the Point none, the Car its wheel speeds.
+struct OsaPoint {
+  static constexpr int SENSORS = 12;  // sensor columns in front of the lidars
+  static constexpr int ROW = 8;       // leading floats of the state row that are the robot's
+  __device__ __forceinline__ void load(const float*) {}
+  __device__ __forceinline__ void store(float*) const {}
+  __device__ __forceinline__ void rest() {}
+  __device__ __forceinline__ void move(float (&d)[OSA_NAV_DYN], float a0, float a1, float& mx, float& my) {
+    osa_nav_move(d, a0, a1, mx, my);
+  }
+  __device__ __forceinline__ float sensor_col(const float (&d)[OSA_NAV_DYN], int col) const {
+    return osa_nav_sensor_col(d, col);
+  }
+  __device__ __forceinline__ float state_col(float v, int) const { return v; }
+};
+struct OsaCar {
+  static constexpr int SENSORS = OSA_CAR_SENSORS, ROW = OSA_CAR_WHEELS + 2;
+  float w[2];  // (w_l, w_r)
+  __device__ __forceinline__ void load(const float* __restrict__ row) {
+    w[0] = row[OSA_CAR_WHEELS];
+    w[1] = row[OSA_CAR_WHEELS + 1];
+  }
+  __device__ __forceinline__ void store(float* __restrict__ row) const {
+    row[OSA_CAR_WHEELS] = w[0];
+    row[OSA_CAR_WHEELS + 1] = w[1];
+  }
+  __device__ __forceinline__ void rest() { w[0] = w[1] = 0.f; }
+  __device__ __forceinline__ void move(float (&d)[OSA_NAV_DYN], float a0, float a1, float& mx, float& my) {
+    osa_car_move(d, w, a0, a1, mx, my);
+  }
+  __device__ __forceinline__ float sensor_col(const float (&d)[OSA_NAV_DYN], int col) const {
+    return osa_car_sensor_col(d, w, col);
+  }
+  __device__ __forceinline__ float state_col(float v, int col) const {
+    if (col == OSA_CAR_WHEELS) v = w[0];
+    if (col == OSA_CAR_WHEELS + 1) v = w[1];
+    return v;
+  }
+};
 
-// Column `col` of the current SynthNavCarGoal state row (`row`: the objects, as osa_nav_state_col).
-__device__ __forceinline__ float osa_car_state_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
-                                                   const float* __restrict__ row, int col) {
-  float v = osa_nav_state_col(d, row, col);
-  if (col == OSA_CAR_WHEELS) v = w[0];
-  if (col == OSA_CAR_WHEELS + 1) v = w[1];
-  return v;
-}
+// The tasks.  ROW: the leading floats of the state row that the task reads into `d` (the Circle's goal stays pinned at
+// the origin); LIDARS: 16-bin lidars behind the robot's sensor columns.
+struct OsaGoal {
+  static constexpr unsigned long long KEY = OSA_NAV_KEY;
+  static constexpr int ROW = OSA_NAV_DYN, LIDARS = 3;
+  static constexpr bool OBJECTS = true;  // hazards and vases in the row: 64 floats, kept in LDS
+  static __device__ __forceinline__ void fresh(float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
+                                               const OsaEnvAt& at) {
+    osa_nav_fresh(at.seed ^ KEY, at.pos, at.n, at.level, row, d);
+  }
+  template <class Robot>
+  static __device__ __forceinline__ void advance(float (&d)[OSA_NAV_DYN], Robot& bot, const float* __restrict__ row,
+                                                 const OsaEnvAt& at, float a0, float a1, float& r, float&) {
+    const float d0 = osa_reach_dist(d[0], d[1], d[8], d[9]);
+    float mx, my;
+    bot.move(d, a0, a1, mx, my);
+    osa_nav_arrive(d, row, at.level, d0, at.seed ^ KEY, at.pos, at.n, r);
+  }
+  static __device__ __forceinline__ float lidar_col(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
+                                                    int level, int b) {
+    return osa_nav_lidar_col(d, row, level, b);
+  }
+};
+struct OsaCircle {
+  static constexpr unsigned long long KEY = OSA_CIRCLE_KEY;
+  static constexpr int ROW = 8, LIDARS = 1;
+  static constexpr bool OBJECTS = false;
+  static __device__ __forceinline__ void fresh(float (&d)[OSA_NAV_DYN], const float*, const OsaEnvAt& at) {
+    osa_circle_fresh(at.seed ^ KEY, at.pos, at.n, d);
+  }
+  template <class Robot>
+  static __device__ __forceinline__ void advance(float (&d)[OSA_NAV_DYN], Robot& bot, const float*,
+                                                 const OsaEnvAt& at, float a0, float a1, float& r, float& c) {
+    float mx, my;
+    bot.move(d, a0, a1, mx, my);
+    osa_circle_pay(d, at.level, mx, my, r, c);
+  }
+  static __device__ __forceinline__ float lidar_col(const float (&d)[OSA_NAV_DYN], const float*, int, int b) {
+    return osa_circle_lidar_col(d, b);
+  }
+};
+
+// SynthNav{,Car}{Goal,Circle}{0,1,2}-v0.  The Car takes the POINT task's key and reset (Task::KEY, Task::fresh) and
+// starts its wheels at rest.
+template <class Robot, class Task>
+struct OsaNavEnv {
+  static constexpr int DYN = Robot::ROW > Task::ROW ? Robot::ROW : Task::ROW;
+  static constexpr int STATE = Task::OBJECTS ? OSA_NAV_STATE : DYN, TRACE = STATE;
+  static constexpr int SENSORS = Robot::SENSORS, OBS = SENSORS + 16 * Task::LIDARS, ACT = 2;
+  static constexpr bool LDS_ROW = Task::OBJECTS;
+  struct Regs {
+    float d[OSA_NAV_DYN];  // a SynthNavGoal `d`, the same in every lane that works on the env
+    Robot bot;
+  };
+  static __device__ __forceinline__ void load(Regs& s, const float* __restrict__ row) {
+#pragma unroll
+    for (int k = 0; k < OSA_NAV_DYN; ++k) s.d[k] = k < Task::ROW ? row[k] : 0.f;
+    s.bot.load(row);
+  }
+  static __device__ __forceinline__ void store(const Regs& s, float* __restrict__ srow) {
+#pragma unroll
+    for (int k = 0; k < OSA_NAV_DYN && k < STATE; ++k) srow[k] = s.d[k];
+    s.bot.store(srow);
+  }
+  // Column `col` (>= DYN) of a fresh row with objects; fresh() wants the fresh hazards in `row`.
+  static __device__ __forceinline__ float fresh_obj(const OsaEnvAt& at, int col) {
+    return osa_nav_fresh_obj(at.seed ^ Task::KEY, at.pos, at.n, at.level, col);
+  }
+  static __device__ __forceinline__ void fresh(Regs& s, const OsaEnvAt& at, const float* __restrict__ row) {
+    Task::fresh(s.d, row, at);
+    s.bot.rest();
+  }
+  static __device__ __forceinline__ void advance(Regs& s, const float* __restrict__ row, const OsaEnvAt& at, float a0,
+                                                 float a1, float& r, float& c) {
+    Task::advance(s.d, s.bot, row, at, a0, a1, r, c);
+  }
+  static __device__ __forceinline__ void transition(Regs& s, const float* __restrict__ row, const OsaEnvAt& at,
+                                                    float a0, float a1, float& r, float& c) {
+    advance(s, row, at, a0, a1, r, c);
+    if (Task::OBJECTS) c = osa_nav_cost(s.d, row, at.level);
+  }
+  // One lane for the whole column: the robot's sensors, then the task's lidars, 0 past them.
+  static __device__ __forceinline__ float obs_col(const Regs& s, const float* __restrict__ row, int level, int col) {
+    if (col < SENSORS || col >= OBS) return s.bot.sensor_col(s.d, col);
+    return Task::lidar_col(s.d, row, level, col - SENSORS);
+  }
+  static __device__ __forceinline__ float state_col(const Regs& s, const float* __restrict__ row, int col) {
+    float v = 0.f;
+    if (Task::OBJECTS && col >= OSA_NAV_DYN) v = row[col];
+#pragma unroll
+    for (int k = 0; k < OSA_NAV_DYN; ++k)
+      if (col == k) v = s.d[k];
+    return s.bot.state_col(v, col);
+  }
+};
+using OsaPointGoal = OsaNavEnv<OsaPoint, OsaGoal>;
+using OsaPointCircle = OsaNavEnv<OsaPoint, OsaCircle>;
+using OsaCarGoal = OsaNavEnv<OsaCar, OsaGoal>;
+using OsaCarCircle = OsaNavEnv<OsaCar, OsaCircle>;
+static_assert(OsaPointGoal::STATE == 64 && OsaPointGoal::OBS == 60 && OsaPointGoal::DYN == 10, "SynthNavGoal");
+static_assert(OsaPointCircle::STATE == 8 && OsaPointCircle::OBS == 28 && OsaPointCircle::DYN == 8, "SynthNavCircle");
+static_assert(OsaCarGoal::STATE == 64 && OsaCarGoal::OBS == 72 && OsaCarGoal::DYN == 12, "SynthNavCarGoal");
+static_assert(OsaCarCircle::STATE == 12 && OsaCarCircle::OBS == 40 && OsaCarCircle::DYN == 12, "SynthNavCarCircle");
 #pragma clang fp contract(fast)

@@ -29,7 +29,7 @@ struct OsaEvalArgs {
   int* ep_len;
   float* trace;
   int rec;  // floats per trace record
-  int level;  // level of a SynthNav* env (env kinds OSA_EVAL_ENV_NAV0 / _CIRCLE0 / _CARGOAL0 / _CARCIRCLE0 + level)
+  int level;  // level of a SynthNav* env (env_kind - its family's OSA_EVAL_ENV_* constant)
 };
 
 #define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
@@ -45,52 +45,29 @@ __device__ __forceinline__ float osa_eval_norm(const OsaEvalArgs& a, bool on, fl
   return v;
 }
 
-// The env observation of row k at stream position `pos` into its LDS input row (lane group g takes a quarter of the
-// columns).  Reach: from the state s (SynthNavGoal: osa_eval_obs_nav below).  Synth: the non-truncating draw (a, b)
-// of every feature pair.
-template <int ENV>
+// The env observation of episode k (at) into its LDS input row, lane group g taking a quarter of the columns.
+template <class E>
 __device__ __forceinline__ void osa_eval_obs(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
-                                             int k, unsigned long long pos, const float (&s)[6]) {
+                                             const typename E::Regs& s, const float* __restrict__ srow,
+                                             const OsaEnvAt&) {
+  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, E::obs_col(s, srow, a.level, c), c);
+}
+// The noise env draws its observation pair-wise: the non-truncating draw (v0, v1) of every feature pair.
+template <>
+__device__ __forceinline__ void osa_eval_obs<OsaSynthEnv>(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow,
+                                                          int g, const OsaSynthEnv::Regs&, const float* __restrict__,
+                                                          const OsaEnvAt& at) {
   const int D = a.obs_dim;
-  if (ENV == OSA_EVAL_ENV_REACH) {
-    for (int c = g; c < D; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_reach_obs_col(s, c), c);
-  } else {
-    for (int pair = g; 2 * pair < D; pair += 4) {
-      float v0, v1, c2, d2;
-      osa_synth_obs_pair(a.seed, pos, k, pair, v0, v1, c2, d2);
-      xrow[2 * pair] = osa_eval_norm(a, norm_on, v0, 2 * pair);
-      if (2 * pair + 1 < D) xrow[2 * pair + 1] = osa_eval_norm(a, norm_on, v1, 2 * pair + 1);
-    }
+  for (int pair = g; 2 * pair < D; pair += 4) {
+    float v0, v1, c2, d2;
+    osa_synth_obs_pair(at.seed, at.pos, at.n, pair, v0, v1, c2, d2);
+    xrow[2 * pair] = osa_eval_norm(a, norm_on, v0, 2 * pair);
+    if (2 * pair + 1 < D) xrow[2 * pair + 1] = osa_eval_norm(a, norm_on, v1, 2 * pair + 1);
   }
 }
 
-// SynthNavGoal: from the row's state (d: its first ten floats, srow: the row in LDS with the objects).
-__device__ __forceinline__ void osa_eval_obs_nav(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
-                                                 const float (&d)[OSA_NAV_DYN], const float* __restrict__ srow) {
-  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_nav_obs_col(d, srow, a.level, c), c);
-}
-
-// SynthNavCircle: from the row's state in registers (d: the eight state floats and the pinned centre).
-__device__ __forceinline__ void osa_eval_obs_circle(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
-                                                    const float (&d)[OSA_NAV_DYN]) {
-  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_circle_obs_col(d, c), c);
-}
-
-// SynthNavCarGoal: as osa_eval_obs_nav, with the wheel speeds w.
-__device__ __forceinline__ void osa_eval_obs_car_goal(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow,
-                                                      int g, const float (&d)[OSA_NAV_DYN], const float (&w)[2],
-                                                      const float* __restrict__ srow) {
-  for (int c = g; c < a.obs_dim; c += 4)
-    xrow[c] = osa_eval_norm(a, norm_on, osa_car_goal_obs_col(d, w, srow, a.level, c), c);
-}
-
-// SynthNavCarCircle: as osa_eval_obs_circle, with the wheel speeds w.
-__device__ __forceinline__ void osa_eval_obs_car_circle(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow,
-                                                        int g, const float (&d)[OSA_NAV_DYN], const float (&w)[2]) {
-  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, osa_car_circle_obs_col(d, w, c), c);
-}
-
-template <int HT, int OT, int ENV>
+// E: the family's description (env_device.h).
+template <int HT, int OT, class E>
 __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
   extern __shared__ f32x4 osa_eval_lds[];
   const OsaNet& nd = a.nd;
@@ -101,42 +78,17 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
   float* __restrict__ xrow = reinterpret_cast<float*>(osa_eval_lds) + j * INP;
   float* __restrict__ arow = reinterpret_cast<float*>(osa_eval_lds) + 16 * INP + j * OSA_EVAL_ACT_LD;
   const bool norm_on = a.mean != nullptr && *a.count > 1;
-  // reset (stream position 0)
-  float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (ENV == OSA_EVAL_ENV_REACH) {
-    uint32_t w0[4], w1[4];
-    osa_philox(a.seed ^ OSA_REACH_KEY, 0, ((unsigned long long)k << 20) + 1, w0);
-    osa_philox(a.seed ^ OSA_REACH_KEY, 0, ((unsigned long long)k << 20) + 2, w1);
-    osa_reach_fresh(w0, w1, s);
+  // reset (stream position 0).  A family with objects keeps the state row of episode k in LDS behind the action rows;
+  // what a transition changes is in registers either way.
+  OsaEnvAt at = {a.seed, 0, k, a.level, a.cost_p};
+  float* __restrict__ srow = reinterpret_cast<float*>(osa_eval_lds) + 16 * (INP + OSA_EVAL_ACT_LD) + j * E::STATE;
+  typename E::Regs s = {};
+  if constexpr (E::LDS_ROW) {
+    for (int c = OSA_NAV_DYN + g; c < E::STATE; c += 4) srow[c] = valid ? E::fresh_obj(at, c) : 0.f;
+    __syncthreads();  // the row's hazards are in LDS (the reset places the goal away from them)
   }
-  // SynthNavGoal, SynthNavCarGoal: the state row of episode k in LDS behind the action rows, its first ten floats (and
-  // the Car's wheel speeds cw) in registers
-  float* __restrict__ srow =
-      reinterpret_cast<float*>(osa_eval_lds) + 16 * (INP + OSA_EVAL_ACT_LD) + j * OSA_NAV_STATE;
-  float d[OSA_NAV_DYN] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float cw[2] = {0.f, 0.f};  // a reset leaves the Car's wheels at rest
-  if (ENV == OSA_EVAL_ENV_NAV0 || ENV == OSA_EVAL_ENV_CARGOAL0) {
-    for (int c = OSA_NAV_DYN + g; c < OSA_NAV_STATE; c += 4)
-      srow[c] = valid ? osa_nav_fresh_obj(a.seed ^ OSA_NAV_KEY, 0, k, a.level, c) : 0.f;
-    __syncthreads();  // the row's hazards are in LDS (osa_nav_fresh places the goal away from them)
-    osa_nav_fresh(a.seed ^ OSA_NAV_KEY, 0, k, a.level, srow, d);
-    if (valid) {
-      if (ENV == OSA_EVAL_ENV_NAV0)
-        osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
-      else
-        osa_eval_obs_car_goal(a, norm_on, xrow, g, d, cw, srow);
-    }
-  } else if (ENV == OSA_EVAL_ENV_CIRCLE0 || ENV == OSA_EVAL_ENV_CARCIRCLE0) {  // the whole state in registers
-    osa_circle_fresh(a.seed ^ OSA_CIRCLE_KEY, 0, k, d);
-    if (valid) {
-      if (ENV == OSA_EVAL_ENV_CIRCLE0)
-        osa_eval_obs_circle(a, norm_on, xrow, g, d);
-      else
-        osa_eval_obs_car_circle(a, norm_on, xrow, g, d, cw);
-    }
-  } else if (valid) {
-    osa_eval_obs<ENV>(a, norm_on, xrow, g, k, 0, s);
-  }
+  E::fresh(s, at, srow);
+  if (valid) osa_eval_obs<E>(a, norm_on, xrow, g, s, srow, at);
   float z = 1.f;  // Saute / Simmer safety budget left (evaluator.py:415)
   if (a.saute && g == 0) xrow[a.obs_dim] = z;
   double ret = 0.0, cost = 0.0;
@@ -163,45 +115,16 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
       }
     }
     __syncthreads();  // the row's env action is in LDS; the forward's reads of the input row are done
-    const unsigned long long pos = (unsigned long long)t + 1;
+    at.pos = (unsigned long long)t + 1;
     const bool trunc = t + 1 >= a.horizon;
     float rw, cs;
-    if (ENV == OSA_EVAL_ENV_NAV0) {
-      if (rec)
-        for (int q = g; q < OSA_NAV_STATE; q += 4) rec[in_w + nd.act_dim + 3 + q] = osa_nav_state_col(d, srow, q);
-      osa_nav_transition(d, srow, a.level, arow[0], arow[1], a.seed ^ OSA_NAV_KEY, pos, k, rw, cs);
-    } else if (ENV == OSA_EVAL_ENV_CIRCLE0) {
-      if (rec && g == 0) {
+    if (rec && E::LDS_ROW)  // the lane groups share the columns of a row in LDS; lane group 0 writes out registers
+      for (int q = g; q < E::TRACE; q += 4) rec[in_w + nd.act_dim + 3 + q] = E::state_col(s, srow, q);
+    if (rec && !E::LDS_ROW && g == 0) {
 #pragma unroll
-        for (int q = 0; q < OSA_CIRCLE_STATE; ++q) rec[in_w + nd.act_dim + 3 + q] = d[q];
-      }
-      osa_circle_transition(d, a.level, arow[0], arow[1], rw, cs);
-    } else if (ENV == OSA_EVAL_ENV_CARGOAL0) {
-      if (rec)
-        for (int q = g; q < OSA_NAV_STATE; q += 4)
-          rec[in_w + nd.act_dim + 3 + q] = osa_car_state_col(d, cw, srow, q);
-      osa_car_goal_advance(d, cw, srow, a.level, arow[0], arow[1], a.seed ^ OSA_NAV_KEY, pos, k, rw);
-      cs = osa_nav_cost(d, srow, a.level);
-    } else if (ENV == OSA_EVAL_ENV_CARCIRCLE0) {
-      if (rec && g == 0) {
-#pragma unroll
-        for (int q = 0; q < OSA_NAV_DYN; ++q) rec[in_w + nd.act_dim + 3 + q] = d[q];
-        rec[in_w + nd.act_dim + 3 + OSA_CAR_WHEELS] = cw[0];
-        rec[in_w + nd.act_dim + 3 + OSA_CAR_WHEELS + 1] = cw[1];
-      }
-      osa_car_circle_transition(d, cw, a.level, arow[0], arow[1], rw, cs);
-    } else if (ENV == OSA_EVAL_ENV_REACH) {
-      if (rec && g == 0)
-        for (int q = 0; q < 6; ++q) rec[in_w + nd.act_dim + 3 + q] = s[q];
-      uint32_t w1[4];
-      osa_philox(a.seed ^ OSA_REACH_KEY, pos, ((unsigned long long)k << 20) + 2, w1);
-      osa_reach_transition(s, arow[0], arow[1], w1, rw, cs);
-    } else {
-      uint32_t w[4];
-      osa_philox(a.seed ^ OSA_SYNTH_RC_KEY, pos, (unsigned long long)k, w);
-      rw = osa_synth_reward(w);
-      cs = osa_synth_cost(w, a.cost_p);
+      for (int q = 0; q < E::TRACE; ++q) rec[in_w + nd.act_dim + 3 + q] = E::state_col(s, srow, q);
     }
+    E::transition(s, srow, at, arow[0], arow[1], rw, cs);
     if (rec && g == 0) {
       rec[in_w + nd.act_dim + 0] = rw;
       rec[in_w + nd.act_dim + 1] = cs;
@@ -224,16 +147,7 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
           a.ep_len[k] = len;
         }
       } else {
-        if (ENV == OSA_EVAL_ENV_NAV0)
-          osa_eval_obs_nav(a, norm_on, xrow, g, d, srow);
-        else if (ENV == OSA_EVAL_ENV_CIRCLE0)
-          osa_eval_obs_circle(a, norm_on, xrow, g, d);
-        else if (ENV == OSA_EVAL_ENV_CARGOAL0)
-          osa_eval_obs_car_goal(a, norm_on, xrow, g, d, cw, srow);
-        else if (ENV == OSA_EVAL_ENV_CARCIRCLE0)
-          osa_eval_obs_car_circle(a, norm_on, xrow, g, d, cw);
-        else
-          osa_eval_obs<ENV>(a, norm_on, xrow, g, k, pos, s);
+        osa_eval_obs<E>(a, norm_on, xrow, g, s, srow, at);
         if (a.saute && g == 0) xrow[a.obs_dim] = z;
       }
     }
@@ -246,27 +160,32 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
 }
 #pragma clang fp contract(fast)
 
+// The families: the OSA_EVAL_ENV_* constant of level 0, the highest level, the description.
+#define OSA_EVAL_FAMILIES(X)                 \
+  X(OSA_EVAL_ENV_SYNTH, 0, OsaSynthEnv)      \
+  X(OSA_EVAL_ENV_REACH, 0, OsaReachEnv)      \
+  X(OSA_EVAL_ENV_NAV0, 2, OsaPointGoal)      \
+  X(OSA_EVAL_ENV_CIRCLE0, 2, OsaPointCircle) \
+  X(OSA_EVAL_ENV_CARGOAL0, 2, OsaCarGoal)    \
+  X(OSA_EVAL_ENV_CARCIRCLE0, 2, OsaCarCircle)
+
 // What the host needs to know of an env_kind: one row per family, matched by family <= env_kind <= family + level.
 struct OsaEvalKind {
-  int family;            // the OSA_EVAL_ENV_* constant the kernel is instantiated with; -1: unknown kind
+  int family;            // the OSA_EVAL_ENV_* constant of the family; -1: unknown kind
   int level;             // in the table: the highest level; as returned: env_kind - family
   int min_obs, min_act;  // least obs_dim and act_dim
   int state_floats;      // state floats of a trace record
-  bool lds_state;        // the kernel keeps a row of OSA_NAV_STATE floats per episode in LDS
+  int lds_state;         // floats of the state row that the kernel keeps per episode in LDS
 };
 
 static OsaEvalKind osa_eval_kind(int env_kind) {
-  static const OsaEvalKind kinds[] = {
-      {OSA_EVAL_ENV_SYNTH, 0, 1, 1, 0, false},
-      {OSA_EVAL_ENV_REACH, 0, 6, 2, 6, false},
-      {OSA_EVAL_ENV_NAV0, 2, OSA_NAV_OBS, 2, OSA_NAV_STATE, true},
-      {OSA_EVAL_ENV_CIRCLE0, 2, OSA_CIRCLE_OBS, 2, OSA_CIRCLE_STATE, false},
-      {OSA_EVAL_ENV_CARGOAL0, 2, OSA_CAR_GOAL_OBS, 2, OSA_NAV_STATE, true},
-      {OSA_EVAL_ENV_CARCIRCLE0, 2, OSA_CAR_CIRCLE_OBS, 2, OSA_CAR_CIRCLE_STATE, false}};
+#define OSA_KIND(FAMILY, LEVELS, E) {FAMILY, LEVELS, E::OBS, E::ACT, E::TRACE, E::LDS_ROW ? E::STATE : 0},
+  static const OsaEvalKind kinds[] = {OSA_EVAL_FAMILIES(OSA_KIND)};
+#undef OSA_KIND
   for (const OsaEvalKind& k : kinds)
     if (env_kind >= k.family && env_kind <= k.family + k.level)
       return {k.family, env_kind - k.family, k.min_obs, k.min_act, k.state_floats, k.lds_state};
-  return {-1, 0, 0, 0, 0, false};
+  return {-1, 0, 0, 0, 0, 0};
 }
 
 extern "C" {
@@ -290,7 +209,7 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   if (rc != OSA_OK) return rc;
   OsaEvalArgs a;
   a.nd = osa_make_net(in_w, act_dim, hidden);
-  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (kind.lds_state ? OSA_NAV_STATE : 0)) * sizeof(float);
+  const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + kind.lds_state) * sizeof(float);
   if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns (928 with a 64-float state row)
   a.params = params;
   a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
@@ -303,18 +222,16 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
   a.rec = osa_eval_trace_floats(env_kind, obs_dim, act_dim, saute);
   a.level = kind.level;
   const dim3 grid((unsigned)((K + 15) / 16));
-#define OSA_LAUNCH(HT, OT, ENV)                                                                               \
-  case ENV:                                                                                                   \
-    hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, ENV>), grid, dim3(64), lds, osa_stream(stream), a); \
-    break
-#define OSA_CALL(HT, OT, NSB)                     \
-  switch (kind.family) {                          \
-    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_NAV0);        \
-    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_CIRCLE0);     \
-    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_CARGOAL0);    \
-    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_CARCIRCLE0);  \
-    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_REACH);       \
-    OSA_LAUNCH(HT, OT, OSA_EVAL_ENV_SYNTH);       \
+#define OSA_LAUNCH(FAMILY, LEVELS, E)                                                                       \
+  case FAMILY:                                                                                              \
+    hipLaunchKernelGGL((osa_eval_episodes_kernel<HT_, OT_, E>), grid, dim3(64), lds, osa_stream(stream), a); \
+    break;
+#define OSA_CALL(HT, OT, NSB)             \
+  {                                       \
+    constexpr int HT_ = HT, OT_ = OT;     \
+    switch (kind.family) {                \
+      OSA_EVAL_FAMILIES(OSA_LAUNCH)       \
+    }                                     \
   }
   OSA_DISPATCH_OT(a.nd, OSA_CALL);
 #undef OSA_CALL

@@ -280,47 +280,75 @@ __global__ __launch_bounds__(256) void osa_saute_step_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// Synthetic fixed-shape vector environment (benchmark stand-in for Safety-Gymnasium, whose MuJoCo
-// physics is third-party CPU code outside the reference repository): obs ~ N(0,1)^D_o,
-// reward ~ N(0,1), cost ~ Bernoulli(p), never terminates, truncates every `horizon` steps with the
-// gymnasium vector auto-reset convention (returned obs is the post-reset obs, the pre-reset obs is
-// handed back as final_observation).
+// The per-step kernels of the device envs (env_device.h).  Their frame is the same for every family and written once:
+// the arguments, the device-resident part of the Philox stream position, the truncation every `horizon` steps with the
+// gymnasium vector auto-reset convention (the returned obs is the post-reset obs, the pre-reset obs is handed back as
+// final_observation where the caller asks for it) and what an env's first lane writes at the end.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void osa_synth_env_kernel(
-    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
-    int D, int horizon, float cost_p, int* __restrict__ steps, float* __restrict__ obs, int ld,
-    float* __restrict__ reward, float* __restrict__ cost, uint8_t* __restrict__ terminated,
-    uint8_t* __restrict__ truncated, float* __restrict__ final_obs, int ld_f, int reset_only) {
-  if (step_base) step += *step_base;  // device-resident part of the Philox stream position
-  const int n = blockIdx.x;  // one workgroup per env row; threads over feature pairs
-  uint8_t trunc = 0;
-  if (!reset_only) trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
+struct OsaStepArgs {
+  unsigned long long seed, step;
+  const unsigned long long* step_base;
+  int N, D, horizon, level;
+  float cost_p;
+  float* state;
+  int* steps;
+  const float* action;
+  int ld_a;
+  float* obs;
+  int ld;
+  float *reward, *cost;
+  uint8_t *terminated, *truncated;
+  float* final_obs;
+  int ld_f, reset_only;
+};
+
+// The stream position of the launch: the host's part and the device-resident one.
+__device__ __forceinline__ unsigned long long osa_step_pos(const OsaStepArgs& a) {
+  return a.step_base ? a.step + *a.step_base : a.step;
+}
+// Whether this step of env n truncates (the final observation, then a reset); `count`: the steps of its episode, this
+// one included.  (Asked after the transition, whose arithmetic hides the load; asked first, the scalar unit waits for
+// it before anything else: profiles/env_frame_timing.json, first_form.)
+__device__ __forceinline__ uint8_t osa_step_trunc(const OsaStepArgs& a, int n, int& count) {
+  count = a.steps[n] + 1;
+  return (count >= a.horizon) ? 1 : 0;
+}
+// What the first lane of env n writes at the end, besides the state (count, trunc: 0 after a reset alone).
+__device__ __forceinline__ void osa_step_end(const OsaStepArgs& a, int n, float r, float c, uint8_t trunc, int count) {
+  if (!a.reset_only) {
+    a.reward[n] = r;
+    a.cost[n] = c;
+    a.terminated[n] = 0;
+    a.truncated[n] = trunc;
+  }
+  a.steps[n] = trunc ? 0 : count;
+}
+
+// Synth*-v0, the benchmark's stand-in for Safety-Gymnasium (whose MuJoCo physics is third-party CPU code outside the
+// reference repository): one workgroup per env row, threads over feature pairs.
+__global__ __launch_bounds__(256) void osa_synth_env_kernel(OsaStepArgs a) {
+  const int n = blockIdx.x, D = a.D;
+  const OsaEnvAt at = {a.seed, osa_step_pos(a), n, 0, a.cost_p};
+  int count = 0;
+  const uint8_t trunc = a.reset_only ? 0 : osa_step_trunc(a, n, count);
+  float* __restrict__ obs = a.obs + (long)n * a.ld;
   for (int pair = threadIdx.x; 2 * pair < D; pair += blockDim.x) {
-    float a, b, c2, d2;
-    osa_synth_obs_pair(seed, step, n, pair, a, b, c2, d2);  // (env_device.h)
+    float x, y, x2, y2;
+    osa_synth_obs_pair(a.seed, at.pos, n, pair, x, y, x2, y2);
     const int i0 = 2 * pair, i1 = 2 * pair + 1;
-    if (trunc) {
-      if (final_obs) {
-        final_obs[(long)n * ld_f + i0] = a;
-        if (i1 < D) final_obs[(long)n * ld_f + i1] = b;
-      }
-      obs[(long)n * ld + i0] = c2;
-      if (i1 < D) obs[(long)n * ld + i1] = d2;
-    } else {
-      obs[(long)n * ld + i0] = a;
-      if (i1 < D) obs[(long)n * ld + i1] = b;
+    if (trunc && a.final_obs) {
+      a.final_obs[(long)n * a.ld_f + i0] = x;
+      if (i1 < D) a.final_obs[(long)n * a.ld_f + i1] = y;
     }
+    obs[i0] = trunc ? x2 : x;
+    if (i1 < D) obs[i1] = trunc ? y2 : y;
   }
-  if (threadIdx.x == 0 && !reset_only) {
-    uint32_t w[4];
-    osa_philox(seed ^ OSA_SYNTH_RC_KEY, step, (unsigned long long)n, w);
-    reward[n] = osa_synth_reward(w);  // (env_device.h)
-    cost[n] = osa_synth_cost(w, cost_p);
-    terminated[n] = 0;
-    truncated[n] = trunc;
-    steps[n] = trunc ? 0 : steps[n] + 1;
+  if (threadIdx.x == 0) {
+    OsaSynthEnv::Regs none;
+    float r = 0.f, c = 0.f;
+    if (!a.reset_only) OsaSynthEnv::transition(none, nullptr, at, 0.f, 0.f, r, c);
+    osa_step_end(a, n, r, c, trunc, count);
   }
-  if (threadIdx.x == 0 && reset_only) steps[n] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -331,69 +359,72 @@ __global__ __launch_bounds__(256) void osa_synth_env_kernel(
 // transition, lane k writes column k of the observation row (coalesced 240-byte row stores).
 // ------------------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
-__global__ __launch_bounds__(64) void osa_reach_env_kernel(
-    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
-    int D, int horizon, float* __restrict__ state, int* __restrict__ steps,
-    const float* __restrict__ action, int ld_a,
-    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
-    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
-    int ld_f, int reset_only) {
-  if (step_base) step += *step_base;
+__global__ __launch_bounds__(64) void osa_reach_env_kernel(OsaStepArgs a) {
+  using E = OsaReachEnv;
   const int n = blockIdx.x, lane = threadIdx.x;
-  float s[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) s[k] = state[(long)n * 8 + k];
-  uint32_t w0[4], w1[4];  // fresh positions for a reset: 6 uniforms
-  osa_philox(seed ^ 0xD1B54A32D192ED03ull, step, ((unsigned long long)n << 20) + 1, w0);
-  osa_philox(seed ^ 0xD1B54A32D192ED03ull, step, ((unsigned long long)n << 20) + 2, w1);  // (env_device.h)
-  const float fresh[6] = {osa_reach_uniform(w0[0]), osa_reach_uniform(w0[1]), osa_reach_uniform(w0[2]),
-                          osa_reach_uniform(w0[3]), osa_reach_uniform(w1[0]), osa_reach_uniform(w1[1])};
+  const unsigned long long pos = osa_step_pos(a);
+  float* __restrict__ srow = a.state + (long)n * E::STATE;
+  E::Regs s, fresh;
+  E::load(s, srow);
+  uint32_t w0[4], w1[4];  // both blocks of the position once: the reset's six uniforms and the transition's new goal
+  osa_philox(a.seed ^ OSA_REACH_KEY, pos, ((unsigned long long)n << 20) + 1, w0);
+  osa_philox(a.seed ^ OSA_REACH_KEY, pos, ((unsigned long long)n << 20) + 2, w1);
+  osa_reach_fresh(w0, w1, fresh.s);
   uint8_t trunc = 0;
+  int count = 0;
   float r = 0.f, c = 0.f;
-  if (reset_only) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) s[k] = fresh[k];
-  } else {
-    osa_reach_transition(s, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], w1, r, c);
-    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
-    if (trunc) {
-      if (final_obs)
-        for (int k = lane; k < D; k += 64) final_obs[(long)n * ld_f + k] = osa_reach_obs_col(s, k);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) s[k] = fresh[k];
-    }
+  if (!a.reset_only) {
+    osa_reach_transition(s.s, a.action[(long)n * a.ld_a + 0], a.action[(long)n * a.ld_a + 1], w1, r, c);
+    trunc = osa_step_trunc(a, n, count);
+    if (trunc && a.final_obs)
+      for (int k = lane; k < a.D; k += 64) a.final_obs[(long)n * a.ld_f + k] = E::obs_col(s, nullptr, 0, k);
   }
-  for (int k = lane; k < D; k += 64) obs[(long)n * ld + k] = osa_reach_obs_col(s, k);
+  if (a.reset_only || trunc) s = fresh;
+  for (int k = lane; k < a.D; k += 64) a.obs[(long)n * a.ld + k] = E::obs_col(s, nullptr, 0, k);
   if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) state[(long)n * 8 + k] = s[k];
-    if (reset_only) {
-      steps[n] = 0;
-    } else {
-      reward[n] = r;
-      cost[n] = c;
-      terminated[n] = 0;
-      truncated[n] = trunc;
-      steps[n] = trunc ? 0 : steps[n] + 1;
-    }
+    E::store(s, srow);
+    osa_step_end(a, n, r, c, trunc, count);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// "SynthNavGoal{0,1,2}" (env_device.h): state[n][64].  One wave per env: the 256-byte state row is one coalesced
-// load into LDS and every lane computes the transition from the row's first ten floats (wave-uniform work).  Then
-// one lane per OBJECT (lanes 0 - 9 hazards, 16 - 25 vases, 32 the goal) takes its distance and body-frame direction
-// -- the square root and the division of every object in one pass; a ballot over the lanes' contact tests is the
-// cost -- and lane c writes column c of the observation row: the 48 lidar lanes walk the <= 10 directions of their
-// class in LDS with two cross products and a compare each.  A reset draws one Philox block per lane for the object
-// columns.  (The one-lane form of the same arithmetic, osa_nav_cost / osa_nav_obs_col with a square root per object
-// and lane, cost 8.3 / 10.7 us per launch at N = 4096 on levels 1 / 2 against SynthReach's 4.6.)
+// The Goal task of either robot, "SynthNavGoal{0,1,2}" and "SynthNavCarGoal{0,1,2}": state[n][64].  One wave per env:
+// the 256-byte state row is one coalesced load into LDS and every lane computes the transition from the row's leading
+// floats (wave-uniform work).  Then one lane per OBJECT (lanes 0 - 9 hazards, 16 - 25 vases, 32 the goal) takes its
+// distance and body-frame direction -- the square root and the division of every object in one pass; a ballot over
+// the lanes' contact tests is the cost -- and lane c writes column c of the observation row: the 48 lidar lanes walk
+// the <= 10 directions of their class in LDS with two cross products and a compare each.  The Car's row (72 columns)
+// is wider than the wave, so there a lane is no longer "its column": lanes 0 - 7 also compute column 64 + l, the last
+// eight vase bins, in a second walk over the vases for the whole wave (eight lanes active), which is what its level 2
+// pays above the ratio of the row bytes (7.66 us against the Point's 6.16 at N = 4096, 1.24 x for 1.2 x the bytes;
+// levels 0 / 1, with 0 / 1 vases: 1.10 / 1.09 x).  Columns past the native width of a wider row are zeros.  A reset
+// draws one Philox block per lane for the object columns.  (The one-lane form of the same arithmetic, osa_nav_cost /
+// osa_nav_lidar_col with a square root per object and lane, cost 8.3 / 10.7 us per launch at N = 4096 on levels 1 / 2
+// against SynthReach's 4.6.)
 // ------------------------------------------------------------------------------------------------
 #define OSA_NAV_SEEN 33  // object slots of a wave: hazard i -> i, vase i -> 16 + i, goal -> 32
 
-// Column `lane` of the observation row of state (d, row) and, wave-uniform, whether the position costs.
-__device__ __forceinline__ float osa_nav_wave_obs(const float (&d)[OSA_NAV_DYN], const float* __restrict__ row,
-                                                  float (&seen)[3][OSA_NAV_SEEN], int level, int lane, bool& hit) {
+// Column `col` of the observation row from the staged objects.
+template <class F>
+__device__ __forceinline__ float osa_goal_seen_col(const typename F::Regs& s, const float (&seen)[3][OSA_NAV_SEEN],
+                                                   int level, int col) {
+  float v = s.bot.sensor_col(s.d, col);
+  if (col >= F::SENSORS && col < F::OBS) {
+    const int cls = (col - F::SENSORS) >> 4, k = (col - F::SENSORS) & 15;
+    const int cnt = cls == 0 ? 1 : (cls == 1 ? osa_nav_hazards(level) : osa_nav_vases(level));
+    const int first = cls == 0 ? 32 : (cls == 1 ? 0 : 16);
+    for (int i = first; i < first + cnt; ++i)
+      if (osa_nav_in_bin(k, seen[0][i], seen[1][i])) v = fmaxf(v, seen[2][i]);
+  }
+  return v;
+}
+
+// Columns lane, 64 + lane, ... (v[0], v[1], ...; 0 past the row) of the observation row of state (s, row); returns,
+// wave-uniform, whether the position costs.
+template <class F, int COLS>
+__device__ __forceinline__ bool osa_goal_wave_obs(const typename F::Regs& s, const float* __restrict__ row,
+                                                  float (&seen)[3][OSA_NAV_SEEN], int level, int lane,
+                                                  float (&v)[COLS]) {
   const int cls_o = lane == 32 ? 0 : (lane < 16 ? 1 : 2), i_o = lane & 15;
   const bool object = lane == 32 || (lane < 16 && i_o < osa_nav_hazards(level)) ||
                       (lane >= 16 && lane < 32 && i_o < osa_nav_vases(level));
@@ -401,299 +432,108 @@ __device__ __forceinline__ float osa_nav_wave_obs(const float (&d)[OSA_NAV_DYN],
   if (object) {
     const float* __restrict__ o = row + (cls_o == 1 ? OSA_NAV_HAZ : OSA_NAV_VASE) + 2 * i_o;
     float bx, by, dist;
-    osa_nav_see(d, cls_o == 0 ? d[8] : o[0], cls_o == 0 ? d[9] : o[1], bx, by, dist);
+    osa_nav_see(s.d, cls_o == 0 ? s.d[8] : o[0], cls_o == 0 ? s.d[9] : o[1], bx, by, dist);
     mine = osa_nav_hit(level, cls_o, dist);
     seen[0][lane] = bx;
     seen[1][lane] = by;
     seen[2][lane] = osa_nav_reading(dist);
   }
-  hit = __ballot(mine) != 0;
+  const bool hit = __ballot(mine) != 0;
   __syncthreads();
-  float v = osa_nav_sensor_col(d, lane);
-  if (lane >= 12 && lane < OSA_NAV_OBS) {
-    const int cls = (lane - 12) >> 4, k = (lane - 12) & 15;
-    const int cnt = cls == 0 ? 1 : (cls == 1 ? osa_nav_hazards(level) : osa_nav_vases(level));
-    const int first = cls == 0 ? 32 : (cls == 1 ? 0 : 16);
-    for (int i = first; i < first + cnt; ++i)
-      if (osa_nav_in_bin(k, seen[0][i], seen[1][i])) v = fmaxf(v, seen[2][i]);
-  }
+#pragma unroll
+  for (int i = 0; i < COLS; ++i)
+    v[i] = (i == 0 || 64 * i + lane < F::OBS) ? osa_goal_seen_col<F>(s, seen, level, 64 * i + lane) : 0.f;
   __syncthreads();  // (the slots are written again on a truncating step)
-  return v;
+  return hit;
 }
 
-__global__ __launch_bounds__(64) void osa_nav_env_kernel(
-    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
-    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
-    const float* __restrict__ action, int ld_a,
-    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
-    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
-    int ld_f, int reset_only) {
-  __shared__ float row[OSA_NAV_STATE];
+// The row v of osa_goal_wave_obs into D columns at dst.
+template <class F, int COLS>
+__device__ __forceinline__ void osa_goal_put_row(float* __restrict__ dst, int D, int lane, const float (&v)[COLS]) {
+  for (int k = lane; k < D; k += 64) dst[k] = k < 64 ? v[0] : (COLS > 1 && k < F::OBS ? v[COLS - 1] : 0.f);
+}
+
+template <class Robot>
+__global__ __launch_bounds__(64) void osa_goal_env_kernel(OsaStepArgs a) {
+  using F = OsaNavEnv<Robot, OsaGoal>;
+  constexpr int COLS = (F::OBS + 63) / 64;
+  static_assert(F::STATE == 64 && COLS <= 2, "one lane per state float, at most two columns per lane");
+  __shared__ float row[F::STATE];
   __shared__ float seen[3][OSA_NAV_SEEN];
-  if (step_base) step += *step_base;
   const int n = blockIdx.x, lane = threadIdx.x;
-  const unsigned long long key = seed ^ OSA_NAV_KEY;
-  float* __restrict__ srow = state + (long)n * OSA_NAV_STATE;
+  const OsaEnvAt at = {a.seed, osa_step_pos(a), n, a.level, 0.f};
+  float* __restrict__ srow = a.state + (long)n * F::STATE;
   row[lane] = srow[lane];
   __syncthreads();
-  float d[OSA_NAV_DYN];
-#pragma unroll
-  for (int k = 0; k < OSA_NAV_DYN; ++k) d[k] = row[k];
+  typename F::Regs s;
+  F::load(s, row);
   uint8_t trunc = 0;
-  float r = 0.f, v = 0.f;
+  int count = 0;
+  float r = 0.f, c = 0.f, v[COLS] = {};
   bool hit = false;
-  if (!reset_only) {
-    osa_nav_advance(d, row, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], key, step, n, r);
-    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
-    v = osa_nav_wave_obs(d, row, seen, level, lane, hit);
-    if (trunc && final_obs)
-      for (int k = lane; k < D; k += 64) final_obs[(long)n * ld_f + k] = k < 64 ? v : 0.f;
+  if (!a.reset_only) {
+    F::advance(s, row, at, a.action[(long)n * a.ld_a + 0], a.action[(long)n * a.ld_a + 1], r, c);
+    trunc = osa_step_trunc(a, n, count);
+    hit = osa_goal_wave_obs<F>(s, row, seen, a.level, lane, v);
+    if (trunc && a.final_obs) osa_goal_put_row<F>(a.final_obs + (long)n * a.ld_f, a.D, lane, v);
   }
-  if (reset_only || trunc) {  // (uniform over the workgroup)
-    if (lane >= OSA_NAV_DYN) {
-      const float o = osa_nav_fresh_obj(key, step, n, level, lane);
+  if (a.reset_only || trunc) {  // (uniform over the workgroup)
+    if (lane >= F::DYN) {
+      const float o = F::fresh_obj(at, lane);
       row[lane] = o;
       srow[lane] = o;
     }
     __syncthreads();
-    osa_nav_fresh(key, step, n, level, row, d);
-    bool unused;
-    v = osa_nav_wave_obs(d, row, seen, level, lane, unused);
+    F::fresh(s, at, row);
+    osa_goal_wave_obs<F>(s, row, seen, a.level, lane, v);
   }
-  for (int k = lane; k < D; k += 64) obs[(long)n * ld + k] = k < 64 ? v : 0.f;
+  osa_goal_put_row<F>(a.obs + (long)n * a.ld, a.D, lane, v);
   if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < OSA_NAV_DYN; ++k) srow[k] = d[k];
-    if (reset_only) {
-      steps[n] = 0;
-    } else {
-      reward[n] = r;
-      cost[n] = hit ? 1.f : 0.f;
-      terminated[n] = 0;
-      truncated[n] = trunc;
-      steps[n] = trunc ? 0 : steps[n] + 1;
-    }
+    F::store(s, srow);
+    osa_step_end(a, n, r, hit ? 1.f : 0.f, trunc, count);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// "SynthNavCircle{0,1,2}" (env_device.h): state[n][8], 28 observation columns, no objects.  The env is too small for a
-// wave: HALF a wave per env, two envs per 64-lane workgroup.  Lane l of a half computes the whole (tiny) transition
-// from the 32-byte state row and writes column l of the observation row (one 112-byte row store per half); columns
-// past 31 of a wider row are zeros in the same strided loop.  Lane 0 of a half writes the state, reward, cost, flags
+// The Circle task of either robot, "SynthNavCircle{0,1,2}" (state[n][8], 28 observation columns) and
+// "SynthNavCarCircle{0,1,2}" (state[n][12], 40 columns): no objects.  The env is too small for a wave: HALF a wave per
+// env, two envs per 64-lane workgroup.  Every lane of a half computes the whole (tiny) transition from the 32- or
+// 48-byte state row and the strided column loop writes the observation row (the Point's 112 bytes in one store per
+// half, the Car's 40 columns in two rounds: lane l writes column l and, for l < 8, column 32 + l); columns past the
+// native width of a wider row are zeros in the same loop.  Lane 0 of a half writes the state, reward, cost, flags
 // and the step counter.  No LDS, no barrier, no cross-lane operation: the half-wave of a missing last env (odd N)
-// leaves at once.  (OSA_CIRCLE_LANES = 64 builds the one-wave-per-env mapping of the sibling kernels for comparison:
-// tools/circle_env_timing.py.)
+// leaves at once.  (OSA_CIRCLE_LANES = 64 / OSA_CAR_CIRCLE_LANES = 64 build the one-wave-per-env mapping of the sibling
+// kernels for comparison: tools/circle_env_timing.py, tools/car_env_timing.py.)
 // ------------------------------------------------------------------------------------------------
 #ifndef OSA_CIRCLE_LANES
-#define OSA_CIRCLE_LANES 32  // lanes per env
+#define OSA_CIRCLE_LANES 32  // lanes per SynthNavCircle env
 #endif
-#define OSA_CIRCLE_PER_WG (64 / OSA_CIRCLE_LANES)  // envs per workgroup
-__global__ __launch_bounds__(64) void osa_circle_env_kernel(
-    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
-    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
-    const float* __restrict__ action, int ld_a,
-    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
-    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
-    int ld_f, int reset_only) {
-  if (step_base) step += *step_base;
-  const int n = OSA_CIRCLE_PER_WG * blockIdx.x + threadIdx.x / OSA_CIRCLE_LANES, lane = threadIdx.x % OSA_CIRCLE_LANES;
-  if (n >= N) return;
-  const unsigned long long key = seed ^ OSA_CIRCLE_KEY;
-  float* __restrict__ srow = state + (long)n * OSA_CIRCLE_STATE;
-  float d[OSA_NAV_DYN];
-#pragma unroll
-  for (int k = 0; k < OSA_CIRCLE_STATE; ++k) d[k] = srow[k];
-  d[8] = d[9] = 0.f;  // the lidar's object: the circle's centre
-  uint8_t trunc = 0;
-  float r = 0.f, c = 0.f;
-  if (!reset_only) {
-    osa_circle_transition(d, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], r, c);
-    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
-    if (trunc && final_obs)
-      for (int k = lane; k < D; k += OSA_CIRCLE_LANES) final_obs[(long)n * ld_f + k] = osa_circle_obs_col(d, k);
-  }
-  if (reset_only || trunc) osa_circle_fresh(key, step, n, d);
-  for (int k = lane; k < D; k += OSA_CIRCLE_LANES) obs[(long)n * ld + k] = osa_circle_obs_col(d, k);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < OSA_CIRCLE_STATE; ++k) srow[k] = d[k];
-    if (reset_only) {
-      steps[n] = 0;
-    } else {
-      reward[n] = r;
-      cost[n] = c;
-      terminated[n] = 0;
-      truncated[n] = trunc;
-      steps[n] = trunc ? 0 : steps[n] + 1;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// "SynthNavCarGoal{0,1,2}" (env_device.h): state[n][64], 72 observation columns.  One wave per env and the object
-// staging of osa_nav_env_kernel (one lane per object into seen[3][33], a ballot for the cost).  The row is wider than
-// the wave, so a lane is no longer "its column": lane l computes column l and lanes 0 - 7 also column 64 + l, the last
-// eight vase bins.  The second column is a second walk over the vases for the whole wave (eight lanes active), which is
-// what level 2 pays above the ratio of the row bytes (7.66 us against SynthNavGoal2's 6.16 at N = 4096, 1.24 x for
-// 1.2 x the bytes; levels 0 / 1, with 0 / 1 vases: 1.10 / 1.09 x).  Columns 72 .. D - 1 of a wider row are zeros.
-// ------------------------------------------------------------------------------------------------
-// Column `col` of the observation row from the staged objects.
-__device__ __forceinline__ float osa_car_seen_col(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
-                                                  const float (&seen)[3][OSA_NAV_SEEN], int level, int col) {
-  float v = osa_car_sensor_col(d, w, col);
-  if (col >= OSA_CAR_SENSORS && col < OSA_CAR_GOAL_OBS) {
-    const int cls = (col - OSA_CAR_SENSORS) >> 4, k = (col - OSA_CAR_SENSORS) & 15;
-    const int cnt = cls == 0 ? 1 : (cls == 1 ? osa_nav_hazards(level) : osa_nav_vases(level));
-    const int first = cls == 0 ? 32 : (cls == 1 ? 0 : 16);
-    for (int i = first; i < first + cnt; ++i)
-      if (osa_nav_in_bin(k, seen[0][i], seen[1][i])) v = fmaxf(v, seen[2][i]);
-  }
-  return v;
-}
-
-// Columns `lane` (v0) and, in lanes 0 - 7, 64 + lane (v1; 0 in the other lanes) of the observation row of state
-// (d, w, row) and, wave-uniform, whether the position costs.
-__device__ __forceinline__ void osa_car_wave_obs(const float (&d)[OSA_NAV_DYN], const float (&w)[2],
-                                                 const float* __restrict__ row, float (&seen)[3][OSA_NAV_SEEN],
-                                                 int level, int lane, bool& hit, float& v0, float& v1) {
-  const int cls_o = lane == 32 ? 0 : (lane < 16 ? 1 : 2), i_o = lane & 15;
-  const bool object = lane == 32 || (lane < 16 && i_o < osa_nav_hazards(level)) ||
-                      (lane >= 16 && lane < 32 && i_o < osa_nav_vases(level));
-  bool mine = false;
-  if (object) {
-    const float* __restrict__ o = row + (cls_o == 1 ? OSA_NAV_HAZ : OSA_NAV_VASE) + 2 * i_o;
-    float bx, by, dist;
-    osa_nav_see(d, cls_o == 0 ? d[8] : o[0], cls_o == 0 ? d[9] : o[1], bx, by, dist);
-    mine = osa_nav_hit(level, cls_o, dist);
-    seen[0][lane] = bx;
-    seen[1][lane] = by;
-    seen[2][lane] = osa_nav_reading(dist);
-  }
-  hit = __ballot(mine) != 0;
-  __syncthreads();
-  v0 = osa_car_seen_col(d, w, seen, level, lane);
-  v1 = lane < OSA_CAR_GOAL_OBS - 64 ? osa_car_seen_col(d, w, seen, level, 64 + lane) : 0.f;
-  __syncthreads();  // (the slots are written again on a truncating step)
-}
-
-__global__ __launch_bounds__(64) void osa_car_goal_env_kernel(
-    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
-    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
-    const float* __restrict__ action, int ld_a,
-    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
-    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
-    int ld_f, int reset_only) {
-  __shared__ float row[OSA_NAV_STATE];
-  __shared__ float seen[3][OSA_NAV_SEEN];
-  if (step_base) step += *step_base;
-  const int n = blockIdx.x, lane = threadIdx.x;
-  const unsigned long long key = seed ^ OSA_NAV_KEY;  // the point task's key: the same arena (env_device.h)
-  float* __restrict__ srow = state + (long)n * OSA_NAV_STATE;
-  row[lane] = srow[lane];
-  __syncthreads();
-  float d[OSA_NAV_DYN];
-#pragma unroll
-  for (int k = 0; k < OSA_NAV_DYN; ++k) d[k] = row[k];
-  float w[2] = {row[OSA_CAR_WHEELS], row[OSA_CAR_WHEELS + 1]};
-  uint8_t trunc = 0;
-  float r = 0.f, v0 = 0.f, v1 = 0.f;
-  bool hit = false;
-  if (!reset_only) {
-    osa_car_goal_advance(d, w, row, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], key, step, n, r);
-    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
-    osa_car_wave_obs(d, w, row, seen, level, lane, hit, v0, v1);
-    if (trunc && final_obs)
-      for (int k = lane; k < D; k += 64)
-        final_obs[(long)n * ld_f + k] = k < 64 ? v0 : (k < OSA_CAR_GOAL_OBS ? v1 : 0.f);
-  }
-  if (reset_only || trunc) {  // (uniform over the workgroup)
-    if (lane >= OSA_NAV_HAZ) {
-      const float o = osa_nav_fresh_obj(key, step, n, level, lane);
-      row[lane] = o;
-      srow[lane] = o;
-    }
-    __syncthreads();
-    osa_nav_fresh(key, step, n, level, row, d);  // (d[7], the Car's t_prev, starts at 0 with the point robot's pad)
-    w[0] = w[1] = 0.f;
-    bool unused;
-    osa_car_wave_obs(d, w, row, seen, level, lane, unused, v0, v1);
-  }
-  for (int k = lane; k < D; k += 64) obs[(long)n * ld + k] = k < 64 ? v0 : (k < OSA_CAR_GOAL_OBS ? v1 : 0.f);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < OSA_NAV_DYN; ++k) srow[k] = d[k];
-    srow[OSA_CAR_WHEELS] = w[0];
-    srow[OSA_CAR_WHEELS + 1] = w[1];
-    if (reset_only) {
-      steps[n] = 0;
-    } else {
-      reward[n] = r;
-      cost[n] = hit ? 1.f : 0.f;
-      terminated[n] = 0;
-      truncated[n] = trunc;
-      steps[n] = trunc ? 0 : steps[n] + 1;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// "SynthNavCarCircle{0,1,2}" (env_device.h): state[n][12], 40 observation columns, no objects.  The half-wave mapping
-// of osa_circle_env_kernel: two envs per 64-lane workgroup, every lane of a half computes the whole transition from
-// the 48-byte state row, and the strided column loop covers the 40 columns in two rounds (lane l writes column l and,
-// for l < 8, column 32 + l; columns past 39 of a wider row are zeros in the same loop).  No LDS, no barrier, no
-// cross-lane operation.  (OSA_CAR_CIRCLE_LANES = 64 builds one wave per env for comparison: tools/car_env_timing.py.)
-// ------------------------------------------------------------------------------------------------
 #ifndef OSA_CAR_CIRCLE_LANES
-#define OSA_CAR_CIRCLE_LANES 32  // lanes per env
+#define OSA_CAR_CIRCLE_LANES 32  // lanes per SynthNavCarCircle env
 #endif
-#define OSA_CAR_CIRCLE_PER_WG (64 / OSA_CAR_CIRCLE_LANES)  // envs per workgroup
-__global__ __launch_bounds__(64) void osa_car_circle_env_kernel(
-    unsigned long long seed, unsigned long long step, const unsigned long long* __restrict__ step_base, int N,
-    int D, int horizon, int level, float* __restrict__ state, int* __restrict__ steps,
-    const float* __restrict__ action, int ld_a,
-    float* __restrict__ obs, int ld, float* __restrict__ reward, float* __restrict__ cost,
-    uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated, float* __restrict__ final_obs,
-    int ld_f, int reset_only) {
-  if (step_base) step += *step_base;
-  const int n = OSA_CAR_CIRCLE_PER_WG * blockIdx.x + threadIdx.x / OSA_CAR_CIRCLE_LANES;
-  const int lane = threadIdx.x % OSA_CAR_CIRCLE_LANES;
-  if (n >= N) return;
-  const unsigned long long key = seed ^ OSA_CIRCLE_KEY;  // the point task's key: the same start (env_device.h)
-  float* __restrict__ srow = state + (long)n * OSA_CAR_CIRCLE_STATE;
-  float d[OSA_NAV_DYN];
-#pragma unroll
-  for (int k = 0; k < OSA_CIRCLE_STATE; ++k) d[k] = srow[k];
-  d[8] = d[9] = 0.f;  // the lidar's object: the circle's centre
-  float w[2] = {srow[OSA_CAR_WHEELS], srow[OSA_CAR_WHEELS + 1]};
+template <class Robot, int LANES>
+__global__ __launch_bounds__(64) void osa_circle_env_kernel(OsaStepArgs a) {
+  using F = OsaNavEnv<Robot, OsaCircle>;
+  const int n = (64 / LANES) * blockIdx.x + threadIdx.x / LANES, lane = threadIdx.x % LANES;
+  if (n >= a.N) return;
+  const OsaEnvAt at = {a.seed, osa_step_pos(a), n, a.level, 0.f};
+  float* __restrict__ srow = a.state + (long)n * F::STATE;
+  typename F::Regs s;
+  F::load(s, srow);
   uint8_t trunc = 0;
+  int count = 0;
   float r = 0.f, c = 0.f;
-  if (!reset_only) {
-    osa_car_circle_transition(d, w, level, action[(long)n * ld_a + 0], action[(long)n * ld_a + 1], r, c);
-    trunc = (steps[n] + 1 >= horizon) ? 1 : 0;
-    if (trunc && final_obs)
-      for (int k = lane; k < D; k += OSA_CAR_CIRCLE_LANES)
-        final_obs[(long)n * ld_f + k] = osa_car_circle_obs_col(d, w, k);
+  if (!a.reset_only) {
+    F::advance(s, nullptr, at, a.action[(long)n * a.ld_a + 0], a.action[(long)n * a.ld_a + 1], r, c);
+    trunc = osa_step_trunc(a, n, count);
+    if (trunc && a.final_obs)
+      for (int k = lane; k < a.D; k += LANES) a.final_obs[(long)n * a.ld_f + k] = F::obs_col(s, nullptr, a.level, k);
   }
-  if (reset_only || trunc) {
-    osa_circle_fresh(key, step, n, d);  // (d[7], the Car's t_prev, starts at 0 with the point robot's pad)
-    w[0] = w[1] = 0.f;
-  }
-  for (int k = lane; k < D; k += OSA_CAR_CIRCLE_LANES) obs[(long)n * ld + k] = osa_car_circle_obs_col(d, w, k);
+  if (a.reset_only || trunc) F::fresh(s, at, nullptr);
+  for (int k = lane; k < a.D; k += LANES) a.obs[(long)n * a.ld + k] = F::obs_col(s, nullptr, a.level, k);
   if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < OSA_NAV_DYN; ++k) srow[k] = d[k];
-    srow[OSA_CAR_WHEELS] = w[0];
-    srow[OSA_CAR_WHEELS + 1] = w[1];
-    if (reset_only) {
-      steps[n] = 0;
-    } else {
-      reward[n] = r;
-      cost[n] = c;
-      terminated[n] = 0;
-      truncated[n] = trunc;
-      steps[n] = trunc ? 0 : steps[n] + 1;
-    }
+    F::store(s, srow);
+    osa_step_end(a, n, r, c, trunc, count);
   }
 }
 #pragma clang fp contract(fast)
@@ -865,13 +705,20 @@ __global__ __launch_bounds__(1024) void osa_gather_mean_kernel(const float* __re
   if (threadIdx.x == 0) *out = (float)(s / (double)n);
 }
 
-// The argument checks of the env entry points that take a level (min_obs: the env's observation columns).
-static bool osa_level_env_ok(int min_obs, int N, int obs_dim, int horizon, int level, float* state, int* steps,
-                             const float* action, int ld_action, float* obs, int ld_obs, float* reward, float* cost,
-                             uint8_t* terminated, uint8_t* truncated, float* final_obs, int ld_final, int reset_only) {
-  if (!(N > 0 && obs_dim >= min_obs && state && steps && obs && ld_obs >= obs_dim)) return false;
-  if (!(level >= 0 && level <= 2 && (!final_obs || ld_final >= obs_dim))) return false;
-  return reset_only || (action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
+// The argument checks and the launch of every env entry point: `envs` envs per 64-lane workgroup, at least min_obs
+// observation columns; has_state: the env has a state matrix and takes actions; has_level: it takes a level.
+template <class Kernel>
+static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bool has_level, const OsaStepArgs& a,
+                        void* stream) {
+  OSA_REQUIRE(a.N > 0 && a.D >= min_obs && (a.state || !has_state) && a.steps && a.obs && a.ld >= a.D);
+  if (has_level) OSA_REQUIRE(a.level >= 0 && a.level <= 2 && (!a.final_obs || a.ld_f >= a.D));
+  if (!a.reset_only) {
+    OSA_REQUIRE(a.reward && a.cost && a.terminated && a.truncated && a.horizon > 0);
+    OSA_REQUIRE(!has_state || (a.action && a.ld_a >= 2));
+  }
+  hipLaunchKernelGGL(kernel, dim3((a.N + envs - 1) / envs), dim3(64), 0, osa_stream(stream), a);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
 }
 
 extern "C" {
@@ -960,13 +807,10 @@ int osa_synth_env_step(unsigned long long seed, unsigned long long step,
                        int horizon, float cost_p, int* steps, float* obs, int ld_obs, float* reward,
                        float* cost, uint8_t* terminated, uint8_t* truncated, float* final_obs,
                        int ld_final, int reset_only, void* stream) {
-  OSA_REQUIRE(N > 0 && obs_dim > 0 && steps && obs && ld_obs >= obs_dim);
-  if (!reset_only) OSA_REQUIRE(reward && cost && terminated && truncated && horizon > 0);
-  hipLaunchKernelGGL(osa_synth_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
-                     obs_dim, horizon, cost_p, steps, obs, ld_obs, reward, cost, terminated,
-                     truncated, final_obs, ld_final, reset_only);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
+  return osa_env_step(osa_synth_env_kernel, OsaSynthEnv::OBS, 1, false, false,
+                      {seed, step, step_base, N, obs_dim, horizon, 0, cost_p, nullptr, steps, nullptr, 0, obs, ld_obs,
+                       reward, cost, terminated, truncated, final_obs, ld_final, reset_only},
+                      stream);
 }
 
 int osa_reach_env_step(unsigned long long seed, unsigned long long step,
@@ -975,76 +819,30 @@ int osa_reach_env_step(unsigned long long seed, unsigned long long step,
                        float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
                        uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
                        void* stream) {
-  OSA_REQUIRE(N > 0 && obs_dim >= 6 && state && steps && obs && ld_obs >= obs_dim);
-  if (!reset_only)
-    OSA_REQUIRE(action && ld_action >= 2 && reward && cost && terminated && truncated && horizon > 0);
-  hipLaunchKernelGGL(osa_reach_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
-                     obs_dim, horizon, state, steps, action, ld_action, obs, ld_obs, reward, cost,
-                     terminated, truncated, final_obs, ld_final, reset_only);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
+  return osa_env_step(osa_reach_env_kernel, OsaReachEnv::OBS, 1, true, false,
+                      {seed, step, step_base, N, obs_dim, horizon, 0, 0.f, state, steps, action, ld_action, obs, ld_obs,
+                       reward, cost, terminated, truncated, final_obs, ld_final, reset_only},
+                      stream);
 }
 
-int osa_nav_env_step(unsigned long long seed, unsigned long long step,
-                     const unsigned long long* step_base, int N, int obs_dim,
-                     int horizon, int level, float* state, int* steps, const float* action, int ld_action,
-                     float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
-                     uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
-                     void* stream) {
-  OSA_REQUIRE(osa_level_env_ok(OSA_NAV_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
-                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
-  hipLaunchKernelGGL(osa_nav_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
-                     obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs, reward, cost,
-                     terminated, truncated, final_obs, ld_final, reset_only);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
-}
-
-int osa_circle_env_step(unsigned long long seed, unsigned long long step,
-                        const unsigned long long* step_base, int N, int obs_dim,
-                        int horizon, int level, float* state, int* steps, const float* action, int ld_action,
-                        float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
-                        uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
-                        void* stream) {
-  OSA_REQUIRE(osa_level_env_ok(OSA_CIRCLE_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
-                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
-  hipLaunchKernelGGL(osa_circle_env_kernel, dim3((N + OSA_CIRCLE_PER_WG - 1) / OSA_CIRCLE_PER_WG), dim3(64), 0,
-                     osa_stream(stream), seed, step, step_base, N, obs_dim, horizon, level, state, steps, action,
-                     ld_action, obs, ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
-}
-
-int osa_car_goal_env_step(unsigned long long seed, unsigned long long step,
-                          const unsigned long long* step_base, int N, int obs_dim,
-                          int horizon, int level, float* state, int* steps, const float* action, int ld_action,
-                          float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
-                          uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
-                          void* stream) {
-  OSA_REQUIRE(osa_level_env_ok(OSA_CAR_GOAL_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
-                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
-  hipLaunchKernelGGL(osa_car_goal_env_kernel, dim3(N), dim3(64), 0, osa_stream(stream), seed, step, step_base, N,
-                     obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs, reward, cost,
-                     terminated, truncated, final_obs, ld_final, reset_only);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
-}
-
-int osa_car_circle_env_step(unsigned long long seed, unsigned long long step,
-                            const unsigned long long* step_base, int N, int obs_dim,
-                            int horizon, int level, float* state, int* steps, const float* action, int ld_action,
-                            float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
-                            uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
-                            void* stream) {
-  OSA_REQUIRE(osa_level_env_ok(OSA_CAR_CIRCLE_OBS, N, obs_dim, horizon, level, state, steps, action, ld_action, obs,
-                               ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only));
-  hipLaunchKernelGGL(osa_car_circle_env_kernel,
-                     dim3((N + OSA_CAR_CIRCLE_PER_WG - 1) / OSA_CAR_CIRCLE_PER_WG), dim3(64), 0, osa_stream(stream),
-                     seed, step, step_base, N, obs_dim, horizon, level, state, steps, action, ld_action, obs, ld_obs,
-                     reward, cost, terminated, truncated, final_obs, ld_final, reset_only);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
-}
+// The four SynthNav entry points share one argument list.
+#define OSA_NAV_ENV_STEP(NAME, KERNEL, FAMILY, LANES)                                                                \
+  int NAME(unsigned long long seed, unsigned long long step, const unsigned long long* step_base, int N,            \
+           int obs_dim, int horizon, int level, float* state, int* steps, const float* action, int ld_action,       \
+           float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated, uint8_t* truncated,             \
+           float* final_obs, int ld_final, int reset_only, void* stream) {                                          \
+    return osa_env_step(KERNEL, FAMILY::OBS, 64 / (LANES), true, true,                                              \
+                        {seed, step, step_base, N, obs_dim, horizon, level, 0.f, state, steps, action, ld_action,   \
+                         obs, ld_obs, reward, cost, terminated, truncated, final_obs, ld_final, reset_only},        \
+                        stream);                                                                                    \
+  }
+OSA_NAV_ENV_STEP(osa_nav_env_step, osa_goal_env_kernel<OsaPoint>, OsaPointGoal, 64)
+OSA_NAV_ENV_STEP(osa_circle_env_step, (osa_circle_env_kernel<OsaPoint, OSA_CIRCLE_LANES>), OsaPointCircle,
+                 OSA_CIRCLE_LANES)
+OSA_NAV_ENV_STEP(osa_car_goal_env_step, osa_goal_env_kernel<OsaCar>, OsaCarGoal, 64)
+OSA_NAV_ENV_STEP(osa_car_circle_env_step, (osa_circle_env_kernel<OsaCar, OSA_CAR_CIRCLE_LANES>), OsaCarCircle,
+                 OSA_CAR_CIRCLE_LANES)
+#undef OSA_NAV_ENV_STEP
 
 size_t osa_episode_flush_ws_doubles(long M) {
   (void)M;

@@ -93,3 +93,50 @@ def test_env_object_equals_direct_calls_of_its_entry_point(env_id):
             env.commit()
             assert (env._t, int(env._t_base)) == (0, 6)
     assert (env._t, int(env._t_base)) == (4, 6) and len(set(ptrs)) == 2
+
+
+@pytest.mark.parametrize('env_id', list(CASES))
+def test_final_obs_null_on_a_truncating_step(env_id):
+    """A reset and three steps at horizon 2 (the second step truncates) from the device-resident stream base 5, once with
+    a final-observation matrix and once with final_obs = NULL: everything else the launches write is equal bit for bit
+    after every launch, and the matrix that was supplied is written on the truncating step and on no other."""
+    from omnisafe_amd import _lib, envs
+
+    entry, state_w, level = CASES[env_id]
+    space = envs.make(env_id, num_envs=N, device=DEV, horizon=2, seed=SEED)
+    D, A = space.observation_space.shape[0], space.action_space.shape[0]
+    fn, p = getattr(_lib.load(require_gpu=True), entry), _lib.ptr
+    f32 = dict(dtype=torch.float32, device=DEV)
+    base = torch.full((1,), 5, dtype=torch.int64, device=DEV)
+
+    def buffers():
+        return {'state': torch.zeros(N, max(state_w, 1), **f32), 'steps': torch.zeros(N, dtype=torch.int32, device=DEV),
+                'obs': torch.zeros(N, D, **f32), 'reward': torch.zeros(N, **f32), 'cost': torch.zeros(N, **f32),
+                'term': torch.zeros(N, dtype=torch.uint8, device=DEV),
+                'trunc': torch.zeros(N, dtype=torch.uint8, device=DEV)}
+
+    def launch(b, final, pos, action, reset_only):
+        if entry == 'osa_synth_env_step':
+            middle = (0.05, p(b['steps']))
+        else:
+            middle = (p(b['state']), p(b['steps']), p(action), action.stride(0) if action is not None else 0)
+            if level is not None:
+                middle = (level,) + middle
+        assert fn(SEED, pos, p(base), N, D, 2, *middle, p(b['obs']), D, p(b['reward']), p(b['cost']), p(b['term']),
+                  p(b['trunc']), p(final), D, reset_only, _lib.stream_ptr()) == 0
+
+    with_final, without = buffers(), buffers()
+    final = torch.full((N, D), -777.0, **f32)
+    gen = torch.Generator(device='cpu').manual_seed(11)
+    for pos in range(4):
+        action = (1.5 * torch.randn(N, A, generator=gen)).to(DEV) if pos else None
+        launch(with_final, final, pos, action, int(pos == 0))
+        launch(without, None, pos, action, int(pos == 0))
+        for name in with_final:
+            np.testing.assert_array_equal(bits(with_final[name]), bits(without[name]), err_msg=f'{name} at {pos}')
+        assert bool(with_final['trunc'].all()) == (pos == 2)
+        if pos == 2:
+            assert not bool((final == -777.0).any()) and not torch.equal(final, with_final['obs'])
+            final.fill_(-777.0)
+        else:
+            assert bool((final == -777.0).all())

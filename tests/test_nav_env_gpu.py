@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import nav_twin as T
+import raw_env
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -40,6 +41,46 @@ def test_reset_from_the_seed_alone(level, seed):
 
 
 # ------------------------------------------------------------------ 2. trace
+@pytest.mark.parametrize('level', [0, 1, 2])
+@pytest.mark.parametrize('N', [1, 3, 130])
+def test_raw_launches_equal_the_twin(level, N):
+    """Raw launches of osa_nav_env_step on buffers of the test's own (the Point and the Car Goal kernels are one
+    template; test_car_env_gpu.py does the same for the Car): 7 steps at horizon 3 (truncations with same-position
+    resets at steps 3 and 6) from stream base 2 under actions 1.5 randn, at obs_dim = ld_obs = 60 and at obs_dim = 68 in
+    rows of 72: everything the launch writes equals the twin at every step, the pad columns are zero, the final
+    observation is written on the truncating step only, and nothing else is written."""
+    W, H, seed, steps = 60, 3, 11 + level, 7
+    for obs_dim, ld in ((W, W), (W + 8, W + 12)):
+        env = raw_env.RawEnv('osa_nav_env_step', 64, level, N, obs_dim, ld, H, seed)
+        twin = T.NavTwin(level, N, H, seed)
+        env.base.fill_(2)  # the device part of the stream position (graph replay): the episode starts at position 2
+        twin.pos = 2
+        assert env.launch(0, None, 1) == 0
+        np.testing.assert_array_equal(env.obs[:N, :W].cpu().numpy(), twin.reset())
+        assert not env.obs[:N, W:obs_dim].any() and int(env.steps[:N].abs().sum()) == 0
+        assert bool((env.final == raw_env.SENTINEL).all()) and bool((env.reward == raw_env.SENTINEL).all())
+        gen = torch.Generator(device='cpu').manual_seed(100 * level + N)
+        for t in range(steps):
+            act = torch.randn(N, 2, generator=gen) * 1.5
+            assert env.launch(t + 1, act.to(DEV), 0) == 0
+            o_exp, r_exp, c_exp, done, final, _ = twin.step(act.numpy())
+            assert done == ((t + 1) % H == 0)
+            np.testing.assert_array_equal(env.reward[:N].cpu().numpy(), r_exp)
+            np.testing.assert_array_equal(env.cost[:N].cpu().numpy(), c_exp)
+            assert not env.term[:N].any() and bool((env.trunc[:N] == int(done)).all())
+            assert bool((env.steps[:N] == (t + 1) % H).all())
+            if done:
+                np.testing.assert_array_equal(env.final[:N, :W].cpu().numpy(), final)
+                assert not env.final[:N, W:obs_dim].any()
+                env.final.fill_(raw_env.SENTINEL)
+            else:
+                assert bool((env.final == raw_env.SENTINEL).all())  # written on the truncating step only
+            np.testing.assert_array_equal(env.state[:N].cpu().numpy(), twin.state)
+            np.testing.assert_array_equal(env.obs[:N, :W].cpu().numpy(), o_exp)
+            assert not env.obs[:N, W:obs_dim].any()
+            assert env.pads_untouched(), (obs_dim, t)
+
+
 @pytest.mark.parametrize('level', [0, 1, 2])
 def test_trace_equals_the_twin(level):
     """2 H + 3 steps at H = 20 under actions 1.5 randn (about half of the components clamp): everything the env

@@ -10,7 +10,7 @@ process.
     `row_bytes_ratio` (72 / 60 or 40 / 28), the gap the wider observation row alone would explain.
 (2) env-steps/s of whole CPO epochs at the BASELINE config-3 sizes (4096 envs x 16 steps) on SynthNavCarGoal1-v0 and on
     the noise env of the same shape, SynthCarGoal1-v0.
---variant-lib: a build of the library with one wave per env in osa_car_circle_env_kernel
+--variant-lib: a build of the library with one wave per env in osa_circle_env_kernel<OsaCar, LANES>
     (tools/build_variant_lib.sh carwave64 rollout_kernels.hip -DOSA_CAR_CIRCLE_LANES=64); part (1) for the CarCircle ids
     is repeated on it in a child process (OSA_LIB_PATH) and reported as `env_step_variant`.
 --learning: seed-mean EpRet / EpCost per epoch of 4 seeds in one AgentGroup (256 envs, horizon 200, 10 epochs of

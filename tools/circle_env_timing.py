@@ -8,7 +8,7 @@ process.
     Also the same launches issued eagerly back to back (includes what the host adds when it cannot keep ahead).
 (2) env-steps/s of whole PPOLag epochs at the BASELINE config-2 sizes (4096 envs x 16 steps) on SynthNavCircle1-v0 and
     on SynthPointGoal1-v0.
---variant-lib: a build of the library with another lane mapping of osa_circle_env_kernel
+--variant-lib: a build of the library with another lane mapping of osa_circle_env_kernel<OsaPoint, LANES>
     (tools/build_variant_lib.sh wave64 rollout_kernels.hip -DOSA_CIRCLE_LANES=64: one wave per env); part (1) for the
     Circle ids is repeated on it in a child process (OSA_LIB_PATH) and reported as `env_step_variant`.
 Prints one JSON line (profiles/circle_env_timing.json)."""
