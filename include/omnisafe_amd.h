@@ -928,6 +928,54 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
 /* Floats per trace record of osa_eval_episodes (0 for bad dims). */
 int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute);
 
+/* Rasterised replay of one episode of a geometric device env: frames first .. first + count - 1 of a top-down picture
+ * of its state rows, written to rgb as uint8 [count][height][width][3].  The picture is a specification of this
+ * package (the reference renders through MuJoCo, third-party CPU code: omnisafe/evaluator.py:511-629 only collects
+ * env.render() frames); tests/render_twin.py restates it in numpy and reproduces every byte.
+ * env_kind: as osa_eval_episodes -- OSA_EVAL_ENV_REACH, or OSA_EVAL_ENV_NAV0 / CIRCLE0 / CARGOAL0 / CARCIRCLE0 + level
+ * 0 .. 2; OSA_EVAL_ENV_SYNTH (no state to draw) and anything else: OSA_EUNSUPPORTED.
+ * state: the state row of record 0; record f at state + f * stride floats (episode k of a trace [T][K][rec]:
+ * trace + k * rec + (rec - state floats), stride = K * rec).  Row layouts as the env entry points above: SynthReach p,
+ * goal, hazard; SynthNavGoal / SynthNavCarGoal p (0, 1), u (2, 3), goal (8, 9), hazards from 12, vases from 32, their
+ * counts per level those of the env (0 / 8 / 10 hazards, 0 / 1 / 10 vases); SynthNavCircle / SynthNavCarCircle p, u.
+ * Frame f shows record f and the robot's path through records max(0, f - trail) .. f as segments between consecutive
+ * positions; nothing before record 0 is read, and a call for frames first .. gives the bytes that a call from 0 gives
+ * for them.  hit: NULL or uint8[first + count]; hit[f] != 0 draws the robot of frame f in the hit colour (the caller
+ * sets it when record f - 1 had a positive cost).
+ * camera 0 (fixed): centre c = (0, 0), half-width 2.25 (SynthReach 1.75), the whole arena; camera 1 (track): c = p of
+ * the frame's record, half-width 1.
+ * Sub-sample (a, b), 0 <= a, b < S = supersample, of pixel (row i, column j), all in float32 without fused
+ * multiply-adds, W = width, H = height:
+ *   h = half / float(min(W, H) * S);  x = c.x + float(2 * (j * S + b) + 1 - W * S) * h;
+ *   y = c.y + float(H * S - 2 * (i * S + a) - 1) * h   (y points up; the integers are exact in float32).
+ * Tests: a disc of centre o and squared radius r2 holds (x, y) iff dx * dx + dy * dy <= r2 with d = (x, y) - o.  A
+ * segment from s with extent e at squared half-width hw2: w = (x, y) - s, L2 = e.x * e.x + e.y * e.y,
+ * t = L2 == 0 ? 0 : min(max((w.x * e.x + w.y * e.y) / L2, 0), 1), d = w - t * e, inside iff d.x * d.x + d.y * d.y <=
+ * hw2 (a robot that stands still gives L2 == 0: the disc of squared radius hw2 round s).
+ * Layers, the later one wins; A = 2 (SynthReach 1.5) the arena's half-width:
+ *   1 outside    everywhere                                                     (40, 44, 52)
+ *   2 floor      |x| <= A and |y| <= A                                          (236, 236, 228)
+ *   3 circle tasks: cost region, on the floor where (level >= 1 and |x| > 0.75)
+ *     or (level == 2 and |y| > 0.75)                                            (244, 204, 196)
+ *     ring       0.9604 <= x * x + y * y <= 1.0404                              (96, 160, 96)
+ *   4 hazards    discs, r2 = 0.04 (SynthReach's one hazard 0.09)                (90, 100, 220)
+ *   5 goal       disc, r2 = 0.09 (SynthReach 0.0225); the circle tasks have none (70, 190, 90)
+ *   6 vases      discs, r2 = 0.01                                               (80, 200, 210)
+ *   7 trail      segments record g -> g + 1, e = p[g + 1] - p[g], hw2 = 0.0004  (250, 160, 40)
+ *   8 robot      disc round p, r2 = 0.01 (SynthReach 0.0025): Point             (200, 40, 40)
+ *                Car (130, 50, 170), either when hit                            (255, 0, 200)
+ *   9 heading    segment from p, e = (p + 0.2 * u) - p, hw2 = 0.0009; not SynthReach (20, 20, 20)
+ * with every constant the nearest float32.  A channel of a pixel is (sum over its S * S sub-samples + S * S / 2) /
+ * (S * S) in integers.
+ * OSA_EINVAL before any launch unless: state and rgb non-NULL, rgb 4-byte aligned, count >= 1, first >= 0, trail >= 0,
+ * 4 <= width <= 4096 with width % 4 == 0, 1 <= height <= 4096, 1 <= supersample <= 4, camera 0 or 1.
+ * OSA_EUNSUPPORTED when count * ceil(width * height / 1024) exceeds 2^31 - 1 (render fewer frames per call).
+ * Launch: 256 lanes per 1024 pixels of one frame, a lane 4 horizontally adjacent pixels and one 12-byte store; the
+ * frame's row and trail staged in LDS; workgroups are independent (no atomics, no flags). */
+int osa_render_episode(int env_kind, const float* state, long stride, int first, int count, int trail,
+                       const uint8_t* hit, int camera, int width, int height, int supersample, uint8_t* rgb,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,7 @@ SIGNATURES: dict[str, tuple] = {
     'osa_eval_episodes': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _F, _F, _U, _I, _F, _I, _I, _F, _F,
                                _I, _D, _D, _P, _P, _P, _P, _P]),
     'osa_eval_trace_floats': (_I, [_I, _I, _I, _I]),
+    'osa_render_episode': (_I, [_I, _P, _L, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 

@@ -74,20 +74,43 @@ class Agent:  # the reference exposes AlgoWrapper under this name (omnisafe/__in
         size > 1 only rank 0 evaluates (no collective is entered); the other ranks return ``{}``."""
         if dist.world_size() > 1 and dist.rank() != 0:
             return {}
+        ev, log_dir = self._evaluator()
+        out = {}
+        for name in self._saved_models():
+            ev.load_saved(save_dir=log_dir, model_name=name)
+            out[name] = ev.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria)
+        return out
+
+    def render(self, num_episodes: int = 10, render_mode: str = 'rgb_array', camera_name: str = 'track',
+               width: int = 256, height: int = 256) -> dict:
+        """algo_wrapper.py:234-269: every ``torch_save/*.pt`` of this run, in epoch order, through
+        :meth:`omnisafe_amd.evaluator.Evaluator.render`; ``{model_name: save_replay_path}`` with the replays under
+        ``<log_dir>/video/<model name without .pt>``.  Rank 0 only, like ``evaluate``."""
+        if dist.world_size() > 1 and dist.rank() != 0:
+            return {}
+        ev, log_dir = self._evaluator()
+        out = {}
+        for name in self._saved_models():
+            ev.load_saved(save_dir=log_dir, model_name=name, render_mode=render_mode, camera_name=camera_name,
+                          width=width, height=height)
+            out[name] = os.path.join(log_dir, 'video', name.split('.')[0])
+            ev.render(num_episodes=num_episodes, save_replay_path=out[name])
+        return out
+
+    def _evaluator(self):
         from .evaluator import Evaluator
 
-        log_dir = self.agent.logger.log_dir
-        save = os.path.join(log_dir, 'torch_save')
+        ev = Evaluator(seed=int(self.cfgs.seed), device=str(self.cfgs.train_cfgs.device),
+                       verbose=bool(getattr(self.cfgs.logger_cfgs, 'verbose', True)))
+        return ev, self.agent.logger.log_dir
+
+    def _saved_models(self) -> list[str]:
+        """The ``torch_save/*.pt`` of this run in epoch order."""
+        save = os.path.join(self.agent.logger.log_dir, 'torch_save')
         names = [n for n in os.listdir(save) if n.endswith('.pt') and os.path.isfile(os.path.join(save, n))]
 
         def epoch(name: str) -> tuple[int, str]:
             stem = name[:-3].rsplit('-', 1)[-1]
             return (int(stem), name) if stem.isdigit() else (1 << 62, name)
 
-        ev = Evaluator(seed=int(self.cfgs.seed), device=str(self.cfgs.train_cfgs.device),
-                       verbose=bool(getattr(self.cfgs.logger_cfgs, 'verbose', True)))
-        out = {}
-        for name in sorted(names, key=epoch):
-            ev.load_saved(save_dir=log_dir, model_name=name)
-            out[name] = ev.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria)
-        return out
+        return sorted(names, key=epoch)

@@ -176,8 +176,19 @@ class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
         self._t_base += self._t
         self._t = 0
 
-    def render(self):
-        return None
+    def render(self, lane: int = 0, width: int = 256, height: int = 256, camera_name: str = 'fixed') -> np.ndarray:
+        """The current state of env ``lane`` as an (height, width, 3) uint8 picture: osa_render_episode with one frame
+        and no trail (2 x 2 sub-samples; the picture is specified in include/omnisafe_amd.h)."""
+        if not self.state_width:
+            raise NotImplementedError(f'{type(self).__name__} has no state to draw')
+        from . import render as render_mod
+
+        if not 0 <= lane < self._num_envs:
+            raise IndexError(f'lane {lane} of {self._num_envs} envs')
+        frame = render_mod.rasterise(self.eval_kind(self._env_id), self.state, lane * self.state_width,
+                                     self.state_width, 0, 1, 0, None, render_mod.camera_index(camera_name),
+                                     width, height, 2)
+        return frame[0].cpu().numpy()
 
     def close(self) -> None:
         return None

@@ -1,8 +1,11 @@
-"""``Evaluator`` -- deterministic evaluation of a saved checkpoint (mirror of omnisafe/evaluator.py:355-490).
+"""``Evaluator`` -- deterministic evaluation and rendering of a saved checkpoint (mirror of
+omnisafe/evaluator.py:355-629).
 
 ``load_saved(save_dir, model_name)`` reads what this package's logger writes (``config.json``,
 ``torch_save/<model_name>`` with keys ``pi`` and, with ``obs_normalize``, ``obs_normalizer``); ``evaluate()`` plays
-``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does.
+``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does; ``render()`` plays them
+the same way and writes one animated PNG per episode, rasterised on the device from the state rows of the trace
+(osa_render_episode, csrc/render_kernels.hip; the picture is specified in include/omnisafe_amd.h).
 
 Two paths, one semantics:
   persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, SynthNavCircle*-v0,
@@ -26,12 +29,14 @@ from __future__ import annotations
 
 import json
 import os
+import time
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, apng
 from . import envs as envs_mod
+from . import render as render_mod
 from .config import Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
@@ -58,10 +63,19 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         self._normalizer: Normalizer | None = None
         self.episode_lengths: list[float] = []
         self.path: str | None = None  # path of the last evaluate(): 'persistent' or 'per-step'
+        self.render_clock: dict[str, float] = {}  # seconds of the last render(): play, raster, copy, encode
 
     # ------------------------------------------------------------------ loading
-    def load_saved(self, save_dir: str, model_name: str) -> None:
-        """evaluator.py:355-398 (no render options: the device envs do not render)."""
+    def load_saved(self, save_dir: str, model_name: str, render_mode: str = 'rgb_array',
+                   camera_name: str | None = None, width: int = 256, height: int = 256) -> None:
+        """evaluator.py:355-398.  The render options are the defaults of later ``render()`` calls; the device envs
+        render to arrays only."""
+        if render_mode != 'rgb_array':
+            raise NotImplementedError(f'render_mode={render_mode!r}: the device envs render to rgb_array only')
+        if camera_name is not None:
+            render_mod.camera_index(camera_name)
+        self._render_defaults = {'camera_name': camera_name or 'fixed', 'width': int(width), 'height': int(height)}
+        self._save_dir, self._model_name = save_dir, model_name
         with open(os.path.join(save_dir, 'config.json'), encoding='utf-8') as f:
             self._dict_cfgs = json.load(f)
         self._cfgs = Config.dict2config(self._dict_cfgs)
@@ -245,6 +259,72 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
                 break
         self.trace = tr
         return ret, cost, length
+
+    # ------------------------------------------------------------------ rendering
+    def render(self, num_episodes: int = 1, save_replay_path: str | None = None,  # pylint: disable=too-many-locals
+               max_render_steps: int = 2000, cost_criteria: float = 1.0, *, width: int | None = None,
+               height: int | None = None, camera_name: str | None = None, trail: int = 50, supersample: int = 2,
+               fps: float = 30, frame_skip: int = 1):
+        """evaluator.py:511-629: plays ``num_episodes`` episodes as ``evaluate`` does and writes, per episode k,
+        ``<save_replay_path>/eval-episode-<k>.png`` (animated PNG of records 0 .. min(length, max_render_steps) - 1,
+        every ``frame_skip``-th frame, 1 / fps seconds each) and ``eval-episode-<k>-path.png`` (the last of those
+        records with the whole path behind it), and appends ``result.txt`` in the reference's wording.
+        ``save_replay_path`` defaults to ``<save_dir>/video/<model name without .pt>``; ``width``, ``height`` and
+        ``camera_name`` ('fixed' or 'track') default to what ``load_saved`` was given.  Returns
+        ``(episode_rewards, episode_costs)``."""
+        if self._actor is None:
+            raise ValueError('The policy must be loaded (load_saved) before rendering the agent.')
+        opts = self._render_defaults
+        width, height = int(width or opts['width']), int(height or opts['height'])
+        camera = render_mod.camera_index(camera_name or opts['camera_name'])
+        cls = envs_mod.ENV_REGISTRY.get(self._env_id)
+        if self._user_env is not None or cls not in DEVICE_ENVS or not cls.trace_state_floats:
+            what = 'an env object given as env=' if self._user_env is not None else self._env_id
+            raise ValueError(f'{what} has no state row to draw: render() takes the geometric device envs '
+                             '(SynthReach-v0, SynthNav*-v0)')
+        if frame_skip < 1 or max_render_steps < 1 or trail < 0 or fps <= 0:
+            raise ValueError('render() needs frame_skip >= 1, max_render_steps >= 1, trail >= 0 and fps > 0')
+        if save_replay_path is None:
+            save_replay_path = os.path.join(self._save_dir, 'video', self._model_name.split('.')[0])
+        os.makedirs(save_replay_path, exist_ok=True)
+        result_path = os.path.join(save_replay_path, 'result.txt')
+        if self._verbose:
+            print(f'Saving the replay video to {save_replay_path},\n and the result to {result_path}.')
+        clock = {'play': 0.0, 'raster': 0.0, 'copy': 0.0, 'encode': 0.0}
+        t0 = time.perf_counter()
+        rewards, costs = self.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria, trace=True)
+        torch.cuda.synchronize(self._device)
+        clock['play'] = time.perf_counter() - t0
+        tr = self.trace.contiguous()  # [T][K][rec]; a record ends with the state row before its step
+        T, K, rec = tr.shape
+        state_w = cls.trace_state_floats
+        kind = cls.eval_kind(self._env_id)
+        # hit[f]: record f - 1 had a positive cost (the cost column is two in front of the alive flag and the state)
+        hit = torch.zeros(K, T, dtype=torch.uint8, device=tr.device)
+        hit[:, 1:] = (tr[:-1, :, rec - state_w - 2] > 0).t()
+        for k in range(int(num_episodes)):
+            frames = int(min(self.episode_lengths[k], max_render_steps, T))
+            at = (kind, tr, k * rec + rec - state_w, K * rec)
+            chunks = render_mod.stream_frames(*at, frames, trail, hit[k], camera, width, height, supersample,
+                                              frame_skip, clock)
+            t0 = time.perf_counter()
+            before = clock['raster'] + clock['copy']
+            apng.write_apng(os.path.join(save_replay_path, f'eval-episode-{k}.png'), chunks, fps, level=1)
+            still = render_mod.rasterise(*at, frames - 1, 1, frames, hit[k], camera, width, height, supersample)
+            apng.write_png(os.path.join(save_replay_path, f'eval-episode-{k}-path.png'), still[0].cpu().numpy())
+            clock['encode'] += time.perf_counter() - t0 - (clock['raster'] + clock['copy'] - before)
+            with open(result_path, 'a+', encoding='utf-8') as f:
+                print(f'Episode {k} results:', file=f)
+                print(f'Episode reward: {rewards[k]}', file=f)
+                print(f'Episode cost: {costs[k]}', file=f)
+                print(f'Episode length: {self.episode_lengths[k]}', file=f)
+        with open(result_path, 'a+', encoding='utf-8') as f:
+            print('Evaluation results:', file=f)
+            print(f'Average episode reward: {np.mean(rewards)}', file=f)
+            print(f'Average episode cost: {np.mean(costs)}', file=f)
+            print(f'Average episode length: {np.mean(self.episode_lengths)}', file=f)
+        self.render_clock = clock
+        return rewards, costs
 
 
 __all__ = ['Evaluator']

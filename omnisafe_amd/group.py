@@ -208,3 +208,9 @@ class AgentGroup:
     def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0) -> list[dict]:
         """``Agent.evaluate`` of every member, in member order."""
         return [a.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria) for a in self.agents]
+
+    def render(self, num_episodes: int = 10, render_mode: str = 'rgb_array', camera_name: str = 'track',
+               width: int = 256, height: int = 256) -> list[dict]:
+        """``Agent.render`` of every member, in member order."""
+        return [a.render(num_episodes=num_episodes, render_mode=render_mode, camera_name=camera_name, width=width,
+                         height=height) for a in self.agents]
