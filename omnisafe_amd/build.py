@@ -113,6 +113,66 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     return LIB_PATH
 
 
+CUSTOM_SRC = os.path.join(CSRC, 'custom', 'custom_env.hip')  # (a sub-directory: sources() takes every csrc/*.hip)
+CUSTOM_DIR = os.path.join(LIB_DIR, 'custom')
+CUSTOM_FLAGS = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wall', '-Wno-unused-function']
+
+
+def custom_env_path(header: str, struct: str) -> str:
+    """Where the library of description ``struct`` of ``header`` lives: ``lib/custom/<struct>-<digest>.so``, the digest
+    taken over the header's bytes, the struct name, source_digest(), csrc/custom/custom_env.hip (which source_digest()
+    does not see) and the flags -- a changed header or package is another file, an unchanged one a cache hit.  (Files
+    the header includes itself are not followed.)"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update(open(header, 'rb').read())
+    h.update(b'\0' + struct.encode() + b'\0' + source_digest().encode() + b'\0' + ' '.join(CUSTOM_FLAGS).encode())
+    h.update(b'\0' + open(CUSTOM_SRC, 'rb').read())
+    return os.path.join(CUSTOM_DIR, f'{struct}-{h.hexdigest()[:16]}.so')
+
+
+def build_custom_env(header: str, struct: str, verbose: bool = False) -> str:
+    """Compile the env description ``struct`` of the user's ``header`` (include/omnisafe_amd_env.h) with the generic
+    per-step kernel and the evaluation kernel into a library of its own; returns its path.  One hipcc command straight
+    to the shared library, no object file; a cached library starts no compiler.  A successful build removes the older
+    ``<struct>-*.so`` of the directory (libraries of earlier versions of the header or the package), so iterating on a
+    header leaves one library per struct name."""
+    import tempfile
+
+    if not struct.isidentifier():
+        raise ValueError(f'{struct!r} is not the name of a struct')
+    header = os.path.abspath(header)
+    path = custom_env_path(header, struct)
+    if os.path.exists(path):
+        return path
+    os.makedirs(CUSTOM_DIR, exist_ok=True)
+    # a name of this call's own, renamed when complete: concurrent builds (threads or processes) of the same library and
+    # interrupted ones leave no half-written file behind
+    fd, tmp = tempfile.mkstemp(prefix=f'{struct}.', suffix='.tmp', dir=CUSTOM_DIR)
+    os.close(fd)
+    cmd = [_hipcc(), *CUSTOM_FLAGS, f'-DOSA_CUSTOM_ENV_HEADER="{header}"', f'-DOSA_CUSTOM_ENV={struct}', CUSTOM_SRC,
+           '-o', tmp]
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, check=False)
+    if done.returncode != 0:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        from ._lib import OsaError  # (_lib imports this module)
+
+        raise OsaError(f'{struct} of {header} does not compile as a device env:\n{done.stderr}')
+    os.chmod(tmp, 0o755)  # (mkstemp made it 0600)
+    os.replace(tmp, path)
+    for old in glob.glob(os.path.join(CUSTOM_DIR, f'{struct}-*.so')):
+        if old != path:
+            try:
+                os.remove(old)  # (a process that has it loaded keeps its mapping)
+            except OSError:
+                pass
+    return path
+
+
 if __name__ == '__main__':
     build_library(force='--force' in sys.argv)
     print(LIB_PATH)

@@ -1,0 +1,198 @@
+// One env description that is not in this tree, as a library of its own (omnisafe_amd.build.build_custom_env):
+//   hipcc ... -DOSA_CUSTOM_ENV_HEADER="<absolute path of the header>" -DOSA_CUSTOM_ENV=<struct> custom_env.hip
+// The header is included behind env_device.h and inside a `fp contract(off)` region: its arithmetic is float32 without
+// fused multiply-adds, and it may use everything env_device.h has (osa_philox, osa_u01, osa_nav_*, OsaNavEnv<...>).
+// The description contract and the three entry points are specified in include/omnisafe_amd_env.h.  This file is in a
+// directory of its own because every csrc/*.hip goes into libomnisafe_amd.so.
+#include "../env_frame.h"
+#include "../eval_episodes.h"
+#include "../../../include/omnisafe_amd_env.h"
+
+#if !defined(OSA_CUSTOM_ENV_HEADER) || !defined(OSA_CUSTOM_ENV)
+#error "custom_env.hip needs -DOSA_CUSTOM_ENV_HEADER=\"<header>\" and -DOSA_CUSTOM_ENV=<struct>"
+#endif
+
+#pragma clang fp contract(off)
+#include OSA_CUSTOM_ENV_HEADER
+#pragma clang fp contract(fast)
+
+using OsaCustomEnv = OSA_CUSTOM_ENV;
+
+// ---- the contract, checked member by member before anything is instantiated --------------------------------------
+#define OSA_HAS_CONSTANT(NAME)                                 \
+  template <class E, class = void>                             \
+  struct OsaHas_##NAME : std::false_type {};                   \
+  template <class E>                                           \
+  struct OsaHas_##NAME<E, std::void_t<decltype(E::NAME)>> : std::true_type {}
+OSA_HAS_CONSTANT(STATE);
+OSA_HAS_CONSTANT(OBS);
+OSA_HAS_CONSTANT(DYN);
+OSA_HAS_CONSTANT(ACT);
+OSA_HAS_CONSTANT(TRACE);
+OSA_HAS_CONSTANT(LDS_ROW);
+#undef OSA_HAS_CONSTANT
+template <class E, class = void>
+struct OsaHas_Regs : std::false_type {};
+template <class E>
+struct OsaHas_Regs<E, std::void_t<typename E::Regs>> : std::true_type {};
+
+static_assert(OsaHas_STATE<OsaCustomEnv>::value, "custom env: the description has no member STATE (floats per state row)");
+static_assert(OsaHas_OBS<OsaCustomEnv>::value, "custom env: the description has no member OBS (observation columns)");
+static_assert(OsaHas_DYN<OsaCustomEnv>::value, "custom env: the description has no member DYN (state floats a transition changes)");
+static_assert(OsaHas_ACT<OsaCustomEnv>::value, "custom env: the description has no member ACT (action columns)");
+static_assert(OsaHas_TRACE<OsaCustomEnv>::value, "custom env: the description has no member TRACE (state floats of a trace record)");
+static_assert(OsaHas_LDS_ROW<OsaCustomEnv>::value, "custom env: the description has no member LDS_ROW (must be false)");
+static_assert(OsaHas_Regs<OsaCustomEnv>::value, "custom env: the description has no member struct Regs");
+
+// The functions, asked for only where what they need is there (one message per missing member, not a cascade).
+template <class E, class = void>
+struct OsaHasLoad : std::false_type {};
+template <class E>
+struct OsaHasLoad<E, std::void_t<decltype(E::load(std::declval<typename E::Regs&>(), (const float*)nullptr))>>
+    : std::true_type {};
+template <class E, class = void>
+struct OsaHasStore : std::false_type {};
+template <class E>
+struct OsaHasStore<E, std::void_t<decltype(E::store(std::declval<const typename E::Regs&>(), (float*)nullptr))>>
+    : std::true_type {};
+template <class E, class = void>
+struct OsaHasFresh : std::false_type {};
+template <class E>
+struct OsaHasFresh<E, std::void_t<decltype(E::fresh(std::declval<typename E::Regs&>(), std::declval<const OsaEnvAt&>(),
+                                                    (const float*)nullptr))>> : std::true_type {};
+template <class E, class = void>
+struct OsaHasObsCol : std::false_type {};
+template <class E>
+struct OsaHasObsCol<E, std::void_t<decltype(E::obs_col(std::declval<const typename E::Regs&>(), (const float*)nullptr,
+                                                       0, 0))>> : std::true_type {};
+template <class E, class = void>
+struct OsaHasStateCol : std::false_type {};
+template <class E>
+struct OsaHasStateCol<E, std::void_t<decltype(E::state_col(std::declval<const typename E::Regs&>(),
+                                                           (const float*)nullptr, 0))>> : std::true_type {};
+template <class E, class = void>
+struct OsaHasTransition2 : std::false_type {};
+template <class E>
+struct OsaHasTransition2<
+    E, std::void_t<decltype(E::transition(std::declval<typename E::Regs&>(), (const float*)nullptr,
+                                          std::declval<const OsaEnvAt&>(), 0.f, 0.f, std::declval<float&>(),
+                                          std::declval<float&>()))>> : std::true_type {};
+
+template <class E, bool = OsaHas_Regs<E>::value>
+struct OsaCustomFunctions {
+  static constexpr bool load = true, store = true, fresh = true, obs_col = true, state_col = true, transition = true;
+};
+template <class E>
+struct OsaCustomFunctions<E, true> {
+  static constexpr bool load = OsaHasLoad<E>::value, store = OsaHasStore<E>::value, fresh = OsaHasFresh<E>::value,
+                        obs_col = OsaHasObsCol<E>::value, state_col = OsaHasStateCol<E>::value,
+                        transition = OsaTakesActionRow<E>::value || OsaHasTransition2<E>::value;
+};
+static_assert(OsaCustomFunctions<OsaCustomEnv>::load, "custom env: the description has no load(Regs&, const float* srow)");
+static_assert(OsaCustomFunctions<OsaCustomEnv>::store, "custom env: the description has no store(const Regs&, float* srow)");
+static_assert(OsaCustomFunctions<OsaCustomEnv>::fresh,
+              "custom env: the description has no fresh(Regs&, const OsaEnvAt&, const float* row)");
+static_assert(OsaCustomFunctions<OsaCustomEnv>::obs_col,
+              "custom env: the description has no obs_col(const Regs&, const float* row, int level, int col)");
+static_assert(OsaCustomFunctions<OsaCustomEnv>::state_col,
+              "custom env: the description has no state_col(const Regs&, const float* row, int col)");
+static_assert(OsaCustomFunctions<OsaCustomEnv>::transition,
+              "custom env: the description has no transition(Regs&, const float* row, const OsaEnvAt&, float a0, float "
+              "a1, float& r, float& c) and no transition(..., const float* act, float& r, float& c)");
+
+// The constants' ranges, each asked for only where the constant exists.
+template <class E, bool = OsaHas_STATE<E>::value && OsaHas_OBS<E>::value && OsaHas_DYN<E>::value &&
+                          OsaHas_ACT<E>::value && OsaHas_TRACE<E>::value && OsaHas_LDS_ROW<E>::value>
+struct OsaCustomRanges {
+  static constexpr bool registers = true, state = true, obs = true, dyn = true, act = true, trace = true,
+                        complete = false;
+};
+template <class E>
+struct OsaCustomRanges<E, true> {
+  static constexpr bool registers = !E::LDS_ROW, state = E::STATE >= 1 && E::STATE <= 64, obs = E::OBS >= 1,
+                        dyn = E::DYN >= 0 && E::DYN <= E::STATE, act = E::ACT >= 1 && E::ACT <= 32,
+                        trace = E::TRACE >= 0 && E::TRACE <= E::STATE, complete = true;
+};
+static_assert(OsaCustomRanges<OsaCustomEnv>::registers,
+              "custom env: LDS_ROW must be false (a description with an object row in LDS needs a kernel of its own, "
+              "like osa_goal_env_kernel; out-of-tree descriptions keep their state in registers)");
+static_assert(OsaCustomRanges<OsaCustomEnv>::state, "custom env: STATE must be 1 .. 64 floats");
+static_assert(OsaCustomRanges<OsaCustomEnv>::obs, "custom env: OBS must be at least 1");
+static_assert(OsaCustomRanges<OsaCustomEnv>::dyn, "custom env: DYN must be 0 .. STATE");
+static_assert(OsaCustomRanges<OsaCustomEnv>::act, "custom env: ACT must be 1 .. 32 action columns");
+static_assert(OsaCustomRanges<OsaCustomEnv>::trace, "custom env: TRACE must not exceed STATE");
+
+constexpr int OSA_CUSTOM_LANES = OsaEnvLanes<OsaCustomEnv>::value;
+constexpr int OSA_CUSTOM_LEVELS = OsaEnvLevels<OsaCustomEnv>::value;
+static_assert(OSA_CUSTOM_LANES == 16 || OSA_CUSTOM_LANES == 32 || OSA_CUSTOM_LANES == 64,
+              "custom env: LANES must be 16, 32 or 64");
+static_assert(OSA_CUSTOM_LEVELS >= 0 && OSA_CUSTOM_LEVELS <= 2, "custom env: LEVELS (the highest level) must be 0 .. 2");
+
+// Everything below needs the whole contract; with a part missing the messages above are the only ones.
+template <class E, bool = OsaCustomRanges<E>::complete && OsaCustomRanges<E>::registers && OsaCustomRanges<E>::state &&
+                          OsaCustomRanges<E>::obs && OsaCustomRanges<E>::act && OsaCustomRanges<E>::trace &&
+                          OsaCustomFunctions<E>::load && OsaCustomFunctions<E>::store && OsaCustomFunctions<E>::fresh &&
+                          OsaCustomFunctions<E>::obs_col && OsaCustomFunctions<E>::state_col &&
+                          OsaCustomFunctions<E>::transition>
+struct OsaCustomLib {
+  static void info(int*) {}
+  static int step(const OsaStepArgs&, void*) { return OSA_EUNSUPPORTED; }
+  template <class... A>
+  static int eval(A...) {
+    return OSA_EUNSUPPORTED;
+  }
+};
+template <class E>
+struct OsaCustomLib<E, true> {
+  static void info(int* out) {
+    const int v[8] = {E::STATE, E::OBS, E::DYN, E::ACT, E::TRACE, OSA_CUSTOM_LEVELS, OSA_CUSTOM_LANES, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+  }
+  static int step(const OsaStepArgs& a, void* stream) {
+    OSA_REQUIRE(a.level <= OSA_CUSTOM_LEVELS);
+    return osa_env_step(osa_custom_env_kernel<E, OSA_CUSTOM_LANES>, E::OBS, 64 / OSA_CUSTOM_LANES, true, true, a,
+                        stream, E::ACT);
+  }
+  template <class... A>
+  static int eval(int level, A... rest) {
+    OSA_REQUIRE(level >= 0 && level <= OSA_CUSTOM_LEVELS);
+    return osa_eval_launch<E>(level, rest...);
+  }
+};
+
+extern "C" {
+
+int osa_custom_env_info(int* out) {
+  OSA_REQUIRE(out);
+  OsaCustomLib<OsaCustomEnv>::info(out);
+  return OSA_OK;
+}
+
+int osa_custom_env_step(unsigned long long seed, unsigned long long step, const unsigned long long* step_base, int N,
+                        int obs_dim, int horizon, int level, float* state, int* steps, const float* action,
+                        int ld_action, float* obs, int ld_obs, float* reward, float* cost, uint8_t* terminated,
+                        uint8_t* truncated, float* final_obs, int ld_final, int reset_only, void* stream) {
+  return OsaCustomLib<OsaCustomEnv>::step(
+      {seed, step, step_base, N, obs_dim, horizon, level, 0.f, state, steps, action, ld_action, obs, ld_obs, reward,
+       cost, terminated, truncated, final_obs, ld_final, reset_only},
+      stream);
+}
+
+int osa_custom_eval_episodes(int level, int K, int obs_dim, int act_dim, int hidden, const float* params,
+                             const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
+                             const float* old_min, const float* old_max, float min_action, float max_action,
+                             unsigned long long seed, int horizon, float cost_p, int max_steps, int saute,
+                             float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
+                             double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
+                             void* stream) {
+  const int rc = osa_eval_check(K, obs_dim, act_dim, params, norm_mean, norm_std, norm_count, old_min, old_max,
+                                min_action, max_action, horizon, max_steps, saute, saute_budget, saute_gamma, ep_ret,
+                                ep_cost, ep_len);
+  if (rc != OSA_OK) return rc;
+  return OsaCustomLib<OsaCustomEnv>::eval(level, K, obs_dim, act_dim, hidden, params, norm_mean, norm_std, norm_count,
+                                          norm_clip, old_min, old_max, min_action, max_action, seed, horizon, cost_p,
+                                          max_steps, saute, saute_budget, saute_gamma, early_terminated, cost_limit,
+                                          cost_criteria, ep_ret, ep_cost, ep_len, trace, stream);
+}
+
+}  // extern "C"

@@ -5,6 +5,9 @@
 // a Philox4x32-10 draw keyed by (seed, stream position `step`, env index n), so a caller that replays env n at
 // positions 0, 1, 2, ... sees the same episode as the per-step launches.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "mlp_device.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -621,3 +624,28 @@ static_assert(OsaPointCircle::STATE == 8 && OsaPointCircle::OBS == 28 && OsaPoin
 static_assert(OsaCarGoal::STATE == 64 && OsaCarGoal::OBS == 72 && OsaCarGoal::DYN == 12, "SynthNavCarGoal");
 static_assert(OsaCarCircle::STATE == 12 && OsaCarCircle::OBS == 40 && OsaCarCircle::DYN == 12, "SynthNavCarCircle");
 #pragma clang fp contract(fast)
+
+// How the kernels call a description's transition.  `act` is the env's unclamped action row (global memory in a
+// per-step kernel, the LDS action row in the evaluation kernel).  The descriptions above take its first two columns by
+// value; one with ACT > 2 states the row form instead,
+//   transition(Regs&, const float* row, const OsaEnvAt&, const float* act, float& r, float& c)
+// and reads act[0 .. ACT).  A description with ACT = 1 in the two-column form gets a1 = 0: the row has no second
+// column, and for the last env act[1] would lie behind the caller's buffer.
+template <class E, class = void>
+struct OsaTakesActionRow : std::false_type {};
+template <class E>
+struct OsaTakesActionRow<
+    E, std::void_t<decltype(E::transition(std::declval<typename E::Regs&>(), (const float*)nullptr,
+                                          std::declval<const OsaEnvAt&>(), (const float*)nullptr,
+                                          std::declval<float&>(), std::declval<float&>()))>> : std::true_type {};
+template <class E>
+__device__ __forceinline__ void osa_env_transition(typename E::Regs& s, const float* __restrict__ row,
+                                                   const OsaEnvAt& at, const float* __restrict__ act, float& r,
+                                                   float& c) {
+  if constexpr (OsaTakesActionRow<E>::value)
+    E::transition(s, row, at, act, r, c);
+  else if constexpr (E::ACT >= 2)
+    E::transition(s, row, at, act[0], act[1], r, c);
+  else
+    E::transition(s, row, at, act[0], 0.f, r, c);
+}

@@ -1,0 +1,127 @@
+// The frame of the per-step kernels of the device envs (env_device.h), the same for every family and written once:
+// the arguments, the device-resident part of the Philox stream position, the truncation every `horizon` steps with the
+// gymnasium vector auto-reset convention (the returned obs is the post-reset obs, the pre-reset obs is handed back as
+// final_observation where the caller asks for it), what an env's first lane writes at the end, and the argument checks
+// and the launch of every entry point.  rollout_kernels.hip builds the kernels of the built-in families on it;
+// osa_custom_env_kernel below is the kernel of any register-state description, which csrc/custom/custom_env.hip
+// instantiates for a description that is not in this tree.
+#pragma once
+#include "env_device.h"
+
+struct OsaStepArgs {
+  unsigned long long seed, step;
+  const unsigned long long* step_base;
+  int N, D, horizon, level;
+  float cost_p;
+  float* state;
+  int* steps;
+  const float* action;
+  int ld_a;
+  float* obs;
+  int ld;
+  float *reward, *cost;
+  uint8_t *terminated, *truncated;
+  float* final_obs;
+  int ld_f, reset_only;
+};
+
+// The stream position of the launch: the host's part and the device-resident one.
+__device__ __forceinline__ unsigned long long osa_step_pos(const OsaStepArgs& a) {
+  return a.step_base ? a.step + *a.step_base : a.step;
+}
+// Whether this step of env n truncates (the final observation, then a reset); `count`: the steps of its episode, this
+// one included.  (Asked after the transition, whose arithmetic hides the load; asked first, the scalar unit waits for
+// it before anything else: profiles/env_frame_timing.json, first_form.)
+__device__ __forceinline__ uint8_t osa_step_trunc(const OsaStepArgs& a, int n, int& count) {
+  count = a.steps[n] + 1;
+  return (count >= a.horizon) ? 1 : 0;
+}
+// What the first lane of env n writes at the end, besides the state (count, trunc: 0 after a reset alone).
+__device__ __forceinline__ void osa_step_end(const OsaStepArgs& a, int n, float r, float c, uint8_t trunc, int count) {
+  if (!a.reset_only) {
+    a.reward[n] = r;
+    a.cost[n] = c;
+    a.terminated[n] = 0;
+    a.truncated[n] = trunc;
+  }
+  a.steps[n] = trunc ? 0 : count;
+}
+
+// The argument checks and the launch of every env entry point: `envs` envs per 64-lane workgroup, at least min_obs
+// observation columns; has_state: the env has a state matrix and takes actions, at least min_act columns of them (the
+// built-in families: two); has_level: it takes a level.
+template <class Kernel>
+static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bool has_level, const OsaStepArgs& a,
+                        void* stream, int min_act = 2) {
+  OSA_REQUIRE(a.N > 0 && a.D >= min_obs && (a.state || !has_state) && a.steps && a.obs && a.ld >= a.D);
+  if (has_level) OSA_REQUIRE(a.level >= 0 && a.level <= 2 && (!a.final_obs || a.ld_f >= a.D));
+  if (!a.reset_only) {
+    OSA_REQUIRE(a.reward && a.cost && a.terminated && a.truncated && a.horizon > 0);
+    OSA_REQUIRE(!has_state || (a.action && a.ld_a >= min_act));
+  }
+  hipLaunchKernelGGL(kernel, dim3((a.N + envs - 1) / envs), dim3(64), 0, osa_stream(stream), a);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The per-step kernel of ANY description that keeps its state in registers (E::LDS_ROW == false): osa_circle_env_kernel
+// with the family a template parameter.  LANES lanes per env, 64 / LANES envs per 64-lane workgroup.  Every lane of an
+// env computes the whole transition from the state row (redundant, wave-uniform work inside the env's lanes) and the
+// strided column loop writes the observation row: lane l the columns l, l + LANES, ..., zeros past E::OBS in a wider
+// row; the same loop writes final_obs on a truncating step.  Lane 0 of an env writes the state, reward, cost, flags and
+// the step counter.  No LDS, no barrier, no cross-lane operation: the lanes of a missing last env leave at once.
+// The description gets no row pointer (`row` == nullptr: its state is what load() put into Regs) and the unclamped
+// action row of the env in global memory.
+// LANES: E::LANES where the description declares it (16, 32 or 64), else 32 -- the value measured for the Circle
+// kernels (28 and 40 columns: 3.75 us against 4.55 us with 64 lanes, profiles/circle_env_timing.json) and for no other
+// shape; profiles/custom_env_timing.json has 16 / 32 / 64 for OsaReachEnv.
+// ------------------------------------------------------------------------------------------------
+template <class E, class = void>
+struct OsaEnvLanes {
+  static constexpr int value = 32;
+};
+template <class E>
+struct OsaEnvLanes<E, std::void_t<decltype(E::LANES)>> {
+  static constexpr int value = E::LANES;
+};
+// The highest level a description takes: E::LEVELS where it declares it, else 2 (what osa_env_step lets through).
+template <class E, class = void>
+struct OsaEnvLevels {
+  static constexpr int value = 2;
+};
+template <class E>
+struct OsaEnvLevels<E, std::void_t<decltype(E::LEVELS)>> {
+  static constexpr int value = E::LEVELS;
+};
+
+#pragma clang fp contract(off)
+template <class E, int LANES>
+__global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaStepArgs a) {
+  static_assert(!E::LDS_ROW, "osa_custom_env_kernel: the description keeps its state row in registers");
+  static_assert(LANES == 16 || LANES == 32 || LANES == 64, "osa_custom_env_kernel: 16, 32 or 64 lanes per env");
+  const int n = (64 / LANES) * blockIdx.x + threadIdx.x / LANES, lane = threadIdx.x % LANES;
+  if (n >= a.N) return;
+  const OsaEnvAt at = {a.seed, osa_step_pos(a), n, a.level, 0.f};
+  float* __restrict__ srow = a.state + (long)n * E::STATE;
+  typename E::Regs s;
+  E::load(s, srow);
+  uint8_t trunc = 0;
+  int count = 0;
+  float r = 0.f, c = 0.f;
+  if (!a.reset_only) {
+    osa_env_transition<E>(s, nullptr, at, a.action + (long)n * a.ld_a, r, c);
+    trunc = osa_step_trunc(a, n, count);
+    if (trunc && a.final_obs)
+      for (int k = lane; k < a.D; k += LANES)
+        a.final_obs[(long)n * a.ld_f + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
+  }
+  if (a.reset_only || trunc) E::fresh(s, at, nullptr);
+  for (int k = lane; k < a.D; k += LANES)
+    a.obs[(long)n * a.ld + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
+  if (lane == 0) {
+    E::store(s, srow);
+    osa_step_end(a, n, r, c, trunc, count);
+  }
+}
+#pragma clang fp contract(fast)

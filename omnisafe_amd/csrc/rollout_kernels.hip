@@ -1,7 +1,7 @@
 // Rollout-side kernels: running observation normaliser (K2), action scaling (K3), per-step episode
 // accounting + bootstrap selection (the per-env Python loop of OnPolicyAdapter.rollout), and the
 // synthetic fixed-shape vector environment used by the throughput benchmark.
-#include "env_device.h"
+#include "env_frame.h"
 
 // ------------------------------------------------------------------------------------------------
 // K2  Normalizer._push + normalize  (omnisafe/common/normalizer.py:88-139)
@@ -280,50 +280,10 @@ __global__ __launch_bounds__(256) void osa_saute_step_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// The per-step kernels of the device envs (env_device.h).  Their frame is the same for every family and written once:
-// the arguments, the device-resident part of the Philox stream position, the truncation every `horizon` steps with the
-// gymnasium vector auto-reset convention (the returned obs is the post-reset obs, the pre-reset obs is handed back as
-// final_observation where the caller asks for it) and what an env's first lane writes at the end.
+// The per-step kernels of the built-in device envs (env_device.h).  Their frame -- OsaStepArgs, osa_step_pos /
+// osa_step_trunc / osa_step_end, and osa_env_step, the argument checks and the launch of every entry point -- is in
+// env_frame.h, which a description built out of tree (csrc/custom/custom_env.hip) shares.
 // ------------------------------------------------------------------------------------------------
-struct OsaStepArgs {
-  unsigned long long seed, step;
-  const unsigned long long* step_base;
-  int N, D, horizon, level;
-  float cost_p;
-  float* state;
-  int* steps;
-  const float* action;
-  int ld_a;
-  float* obs;
-  int ld;
-  float *reward, *cost;
-  uint8_t *terminated, *truncated;
-  float* final_obs;
-  int ld_f, reset_only;
-};
-
-// The stream position of the launch: the host's part and the device-resident one.
-__device__ __forceinline__ unsigned long long osa_step_pos(const OsaStepArgs& a) {
-  return a.step_base ? a.step + *a.step_base : a.step;
-}
-// Whether this step of env n truncates (the final observation, then a reset); `count`: the steps of its episode, this
-// one included.  (Asked after the transition, whose arithmetic hides the load; asked first, the scalar unit waits for
-// it before anything else: profiles/env_frame_timing.json, first_form.)
-__device__ __forceinline__ uint8_t osa_step_trunc(const OsaStepArgs& a, int n, int& count) {
-  count = a.steps[n] + 1;
-  return (count >= a.horizon) ? 1 : 0;
-}
-// What the first lane of env n writes at the end, besides the state (count, trunc: 0 after a reset alone).
-__device__ __forceinline__ void osa_step_end(const OsaStepArgs& a, int n, float r, float c, uint8_t trunc, int count) {
-  if (!a.reset_only) {
-    a.reward[n] = r;
-    a.cost[n] = c;
-    a.terminated[n] = 0;
-    a.truncated[n] = trunc;
-  }
-  a.steps[n] = trunc ? 0 : count;
-}
-
 // Synth*-v0, the benchmark's stand-in for Safety-Gymnasium (whose MuJoCo physics is third-party CPU code outside the
 // reference repository): one workgroup per env row, threads over feature pairs.
 __global__ __launch_bounds__(256) void osa_synth_env_kernel(OsaStepArgs a) {
@@ -703,22 +663,6 @@ __global__ __launch_bounds__(1024) void osa_gather_mean_kernel(const float* __re
   }
   s = osa_block_sum<1024>(s, red);
   if (threadIdx.x == 0) *out = (float)(s / (double)n);
-}
-
-// The argument checks and the launch of every env entry point: `envs` envs per 64-lane workgroup, at least min_obs
-// observation columns; has_state: the env has a state matrix and takes actions; has_level: it takes a level.
-template <class Kernel>
-static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bool has_level, const OsaStepArgs& a,
-                        void* stream) {
-  OSA_REQUIRE(a.N > 0 && a.D >= min_obs && (a.state || !has_state) && a.steps && a.obs && a.ld >= a.D);
-  if (has_level) OSA_REQUIRE(a.level >= 0 && a.level <= 2 && (!a.final_obs || a.ld_f >= a.D));
-  if (!a.reset_only) {
-    OSA_REQUIRE(a.reward && a.cost && a.terminated && a.truncated && a.horizon > 0);
-    OSA_REQUIRE(!has_state || (a.action && a.ld_a >= 2));
-  }
-  hipLaunchKernelGGL(kernel, dim3((a.N + envs - 1) / envs), dim3(64), 0, osa_stream(stream), a);
-  OSA_CHECK_LAUNCH();
-  return OSA_OK;
 }
 
 extern "C" {

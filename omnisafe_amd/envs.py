@@ -32,6 +32,8 @@ SYNTH_DIMS = {
 }
 
 ENV_REGISTRY: dict[str, Callable[..., Any]] = {}
+# the ids of register_device_env, in a registry of their own: ENV_REGISTRY is the closed list of the built-in ids
+CUSTOM_ENV_REGISTRY: dict[str, type] = {}
 
 
 def env_register(cls):
@@ -51,6 +53,8 @@ def make(env_id: str, num_envs: int = 1, device='cuda:0', **env_cfgs):
     host and driven through :class:`omnisafe_amd.host_env.HostEnvBridge` (one D2H / H2D pair per vector step)."""
     if env_id in ENV_REGISTRY:
         return ENV_REGISTRY[env_id](env_id, num_envs=num_envs, device=device, **env_cfgs)
+    if env_id in CUSTOM_ENV_REGISTRY:
+        return CUSTOM_ENV_REGISTRY[env_id](env_id, num_envs=num_envs, device=device, **env_cfgs)
     from .host_env import make_reference_env
 
     env = make_reference_env(env_id, num_envs=num_envs, device=device, **env_cfgs)
@@ -60,7 +64,7 @@ def make(env_id: str, num_envs: int = 1, device='cuda:0', **env_cfgs):
     return env
 
 
-class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
+class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
     """Host side of a vector CMDP that lives entirely in HBM: one launch of the subclass's entry point per ``reset``
     / ``step`` on buffers allocated once.  Observations are double-buffered (the caller may still hold the previous
     one); all envs reset together, so the truncating steps are known on the host and ``info['final_observation']`` /
@@ -69,12 +73,18 @@ class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
     replays with the same by-value positions 0..T while the device part advances, so every epoch still draws fresh
     numbers.
 
+    Two classes derive from it: :class:`DeviceVectorEnv`, whose direct subclasses are the built-in families of
+    libomnisafe_amd.so, and :class:`CustomDeviceEnv`, the envs of ``register_device_env`` with a library each.
+
     A subclass states class-level facts only: ``entry_point``, ``levels`` (id -> level, empty without levels),
     ``obs_act_dims``, ``state_width`` (floats per row of ``state``; 0: no state matrix), ``default_horizon``, and for
     the evaluator ``eval_kind_base`` (OSA_EVAL_ENV_* of level 0) and ``trace_state_floats`` (leading state floats in a
     trace record)."""
 
     entry_point: str
+    eval_entry_point = 'osa_eval_episodes'
+    takes_level = False  # the entry point takes a level even while `levels` is empty (a custom class without ids)
+    render_state = True  # whether the rasteriser (csrc/render_kernels.hip) knows the state row
     levels: dict[str, int] = {}
     obs_act_dims = (60, 2)
     state_width = 0
@@ -97,9 +107,14 @@ class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
         """env_kind of osa_eval_episodes."""
         return cls.eval_kind_base + cls.levels.get(env_id, 0)
 
+    @classmethod
+    def library(cls):
+        """The library that exports ``entry_point`` and ``eval_entry_point``, its prototypes declared."""
+        return _lib.load(require_gpu=True)
+
     def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int | None = None,
                  seed: int = 0, **_unused) -> None:
-        self._lib = _lib.load(require_gpu=True)
+        self._lib = self.library()
         self._step_fn = getattr(self._lib, self.entry_point)
         self._env_id = env_id
         self._level = self.levels.get(env_id, 0)
@@ -142,7 +157,7 @@ class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
                 and action.stride(1) == 1
             ld_a = action.stride(0)
         mid = (_lib.ptr(self.state), _lib.ptr(self._steps), _lib.ptr(action), ld_a)
-        return (self._level, *mid) if self.levels else mid
+        return (self._level, *mid) if (self.levels or self.takes_level) else mid
 
     def _launch(self, middle: tuple, reset_only: int) -> torch.Tensor:
         self._flip ^= 1
@@ -192,6 +207,12 @@ class DeviceVectorEnv:  # pylint: disable=too-many-instance-attributes
 
     def close(self) -> None:
         return None
+
+
+class DeviceVectorEnv(DeviceEnvProtocol):
+    """The built-in families: every DIRECT subclass is one family of libomnisafe_amd.so (csrc/env_device.h), which the
+    evaluator and the plugin enumerate through ``__subclasses__()``.  An env of the user's own is no subclass of this
+    class: ``register_device_env`` derives it from :class:`CustomDeviceEnv`."""
 
 
 @env_register
@@ -308,3 +329,111 @@ class NavCarCircleVectorEnv(DeviceVectorEnv):
     state_width = trace_state_floats = 12
     default_horizon = 500
     eval_kind_base = 64
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Device envs of the user's own: a description struct in a header of theirs (include/omnisafe_amd_env.h), compiled with
+# the generic per-step kernel and the evaluation kernel into a library of its own (build.build_custom_env).
+# ----------------------------------------------------------------------------------------------------------------
+class CustomDeviceEnv(DeviceEnvProtocol):
+    """A device env whose kernels live in a library of its own.  ``register_device_env`` makes one subclass per
+    description; its dimensions are what the compiled library reports (osa_custom_env_info).  ``eval_kind`` is the
+    level: the first argument of the library's osa_custom_eval_episodes."""
+
+    entry_point = 'osa_custom_env_step'
+    eval_entry_point = 'osa_custom_eval_episodes'
+    takes_level = True
+    graph_safe = True
+    render_state = False  # (a state row the rasteriser has never heard of)
+    header: str
+    struct: str
+    lib_path: str
+    lanes = 32
+    max_level = 0
+    _support_envs: list[str] = []
+    _cdll = None
+
+    @classmethod
+    def library(cls):
+        _lib.load(require_gpu=True)  # (no GPU: the same loud failure as the built-in envs; error texts come from there)
+        return cls._cdll
+
+    def render(self, *args, **kwargs):
+        # (the ValueError of Evaluator.render for an env without a drawable state row)
+        raise ValueError(f'{self._env_id} has no state row to draw: render() takes the geometric device envs '
+                         '(SynthReach-v0, SynthNav*-v0)')
+
+
+def _bind_custom(path: str):
+    """dlopen a custom library and declare its three prototypes; returns (CDLL, info[8])."""
+    import ctypes as C
+
+    lib = C.CDLL(path)
+    lib.osa_custom_env_info.restype, lib.osa_custom_env_info.argtypes = C.c_int, [C.POINTER(C.c_int)]
+    lib.osa_custom_env_step.restype, lib.osa_custom_env_step.argtypes = _lib.SIGNATURES['osa_nav_env_step']
+    lib.osa_custom_eval_episodes.restype, lib.osa_custom_eval_episodes.argtypes = _lib.SIGNATURES['osa_eval_episodes']
+    info = (C.c_int * 8)()
+    _lib_code = lib.osa_custom_env_info(info)
+    if _lib_code != 0:
+        raise _lib.OsaError(f'osa_custom_env_info of {path} failed ({_lib_code})')
+    return lib, list(info)
+
+
+def register_device_env(header: str, struct: str, ids, default_horizon: int = 1000) -> type:
+    """Make the env description ``struct`` of the C++ header ``header`` available as device envs.  ``ids``: an
+    ``{env_id: level}`` dict, or a list of ids that are all level 0.  Builds (or finds cached) the description's
+    library, reads every dimension from it and returns the env class; ``make``, ``Agent``, ``AgentGroup`` and
+    ``Evaluator`` then take the ids like built-in ones.  KeyError: an id is taken already; ValueError: a level the
+    description does not have."""
+    from . import build as _build
+
+    levels = dict(ids) if isinstance(ids, dict) else {env_id: 0 for env_id in ids}
+    if not levels:
+        raise ValueError('register_device_env needs at least one env id')
+    for env_id in levels:
+        if env_id in ENV_REGISTRY or env_id in CUSTOM_ENV_REGISTRY:
+            raise KeyError(f'{env_id} is registered already')
+    path = _build.build_custom_env(header, struct)
+    cdll, (state, obs, _dyn, act, trace, max_level, lanes, _) = _bind_custom(path)
+    for env_id, level in levels.items():
+        if not isinstance(level, int) or not 0 <= level <= max_level:
+            raise ValueError(f'{env_id}: level {level!r}, but {struct} has levels 0 .. {max_level}')
+    # one class per struct name (the plugin's key is 'OmnisafeAmdCustom' + struct): further ids of the same library and
+    # default horizon join the class that is there, anything else under that name is refused
+    cls = next((c for c in custom_env_classes() if c.struct == struct), None)
+    if cls is not None:
+        if cls.lib_path != path or cls.default_horizon != int(default_horizon):
+            raise ValueError(f'a struct {struct} is registered already ({cls.header}, default_horizon '
+                             f'{cls.default_horizon}, ids {cls._support_envs}): unregister its ids first, or name '  # noqa: SLF001
+                             'the other description differently')
+        cls.levels.update(levels)
+        cls._support_envs.extend(levels)  # noqa: SLF001
+    else:
+        cls = type(struct + 'VectorEnv', (CustomDeviceEnv,), {
+            '__doc__': f'Device env {struct} of {header} (register_device_env).', '__module__': __name__,
+            '_support_envs': list(levels), 'levels': levels, 'obs_act_dims': (obs, act), 'state_width': state,
+            'trace_state_floats': trace, 'default_horizon': int(default_horizon), 'max_level': max_level,
+            'lanes': lanes, 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll})
+    for env_id in levels:
+        CUSTOM_ENV_REGISTRY[env_id] = cls
+    return cls
+
+
+def unregister_device_env(*ids: str) -> None:
+    """Drop ids that ``register_device_env`` entered (KeyError for any other); envs that exist keep working."""
+    for env_id in ids:
+        if env_id not in CUSTOM_ENV_REGISTRY:
+            raise KeyError(f'{env_id} is no registered custom env (known: {custom_envs()})')
+    for env_id in ids:
+        cls = CUSTOM_ENV_REGISTRY.pop(env_id)
+        cls._support_envs.remove(env_id)  # noqa: SLF001
+        del cls.levels[env_id]
+
+
+def custom_envs() -> list[str]:
+    return sorted(CUSTOM_ENV_REGISTRY)
+
+
+def custom_env_classes() -> list[type]:
+    """The classes with at least one registered id, in the order of their first registration."""
+    return list(dict.fromkeys(CUSTOM_ENV_REGISTRY.values()))

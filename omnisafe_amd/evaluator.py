@@ -9,9 +9,9 @@ the same way and writes one animated PNG per episode, rasterised on the device f
 
 Two paths, one semantics:
   persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, SynthNavCircle*-v0,
-              SynthNavCarGoal*-v0, SynthNavCarCircle*-v0, Synth*-v0):
-              every episode in ONE launch of osa_eval_episodes (csrc/eval_kernels.hip), episode k = env index k of a
-              fresh env.
+              SynthNavCarGoal*-v0, SynthNavCarCircle*-v0, Synth*-v0, and the ids of register_device_env):
+              every episode in ONE launch of osa_eval_episodes (csrc/eval_kernels.hip; a custom env: its own library's
+              osa_custom_eval_episodes, the same kernel template), episode k = env index k of a fresh env.
   per-step    everything else (general networks, host envs, an env object given as ``env=``): the existing launches
               per vector step -- Normalizer.apply, ConstraintActorCritic.step(deterministic=True, nets_mask=1) with
               ActionScale fused, env.step -- and the same float64 sums in the same order.
@@ -46,10 +46,23 @@ TIME_LIMIT = 1000  # evaluator.py:179-180
 DEVICE_ENVS = tuple(envs_mod.DeviceVectorEnv.__subclasses__())
 
 
+def _device_env_class(env_id: str):
+    """The class of a device env id -- a built-in family or one of register_device_env -- or None: what decides whether
+    the evaluator knows the env's dimensions without building it, may play it in the persistent kernel, lets its own
+    horizon end the episodes and can ask it for its state rows."""
+    cls = envs_mod.ENV_REGISTRY.get(env_id)
+    return cls if cls in DEVICE_ENVS else envs_mod.CUSTOM_ENV_REGISTRY.get(env_id)
+
+
+def _is_device_env(env) -> bool:
+    return isinstance(env, DEVICE_ENVS + (envs_mod.CustomDeviceEnv,))
+
+
 def _env_kind(env) -> int:
-    """env_kind of osa_eval_episodes (OSA_EVAL_ENV_* of the family + level); an env of the caller's own counts as
-    OSA_EVAL_ENV_SYNTH, whose trace record has no state floats."""
-    return env.eval_kind(env._env_id) if isinstance(env, DEVICE_ENVS) else 0
+    """env_kind of osa_eval_episodes (OSA_EVAL_ENV_* of the family + level; the level alone for a custom env, whose
+    library has one description); an env of the caller's own counts as OSA_EVAL_ENV_SYNTH, whose trace record has no
+    state floats."""
+    return env.eval_kind(env._env_id) if _is_device_env(env) else 0
 
 
 class Evaluator:  # pylint: disable=too-many-instance-attributes
@@ -104,8 +117,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     def _env_dims(self) -> tuple[int, int]:
         if self._user_env is not None:
             return (int(self._user_env.observation_space.shape[0]), int(self._user_env.action_space.shape[0]))
-        cls = envs_mod.ENV_REGISTRY.get(self._env_id)
-        if cls in DEVICE_ENVS:
+        cls = _device_env_class(self._env_id)
+        if cls is not None:
             return cls.dims(self._env_id)
         env = envs_mod.make(self._env_id, num_envs=1, device=self._device, **self._env_cfgs)
         dims = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
@@ -115,7 +128,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     # ------------------------------------------------------------------ evaluation
     def _persistent_ok(self) -> bool:
         return (self._user_env is None and not self._actor.general
-                and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS)
+                and _device_env_class(self._env_id) is not None)
 
     def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, trace: bool = False):
         """evaluator.py:399-490: ``(episode_rewards, episode_costs)``; ``episode_lengths`` is kept as an attribute.
@@ -160,13 +173,16 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         hi = torch.as_tensor(env.action_space.high, **f32).reshape(-1).contiguous()
         return lo, hi
 
-    def _trace_floats(self, kind: int, obs_dim: int, act_dim: int) -> int:
-        return int(_lib.load().osa_eval_trace_floats(kind, obs_dim, act_dim, int(self._saute)))
+    def _trace_floats(self, env, obs_dim: int, act_dim: int) -> int:
+        if isinstance(env, envs_mod.CustomDeviceEnv):  # (include/omnisafe_amd_env.h: osa_custom_eval_episodes)
+            return obs_dim + int(self._saute) + act_dim + 3 + env.trace_state_floats
+        return int(_lib.load().osa_eval_trace_floats(_env_kind(env), obs_dim, act_dim, int(self._saute)))
 
     def _run_persistent(self, K: int, cost_criteria: float, trace: bool):
-        lib = _lib.load(require_gpu=True)
         env = self._make_env(K)
         kind = _env_kind(env)
+        entry = env.eval_entry_point
+        play = getattr(env.library(), entry)
         obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
         lo, hi = self._scale_bounds(env)
         horizon = int(env.max_episode_steps)
@@ -176,17 +192,17 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         length = torch.zeros(K, dtype=torch.int32, device=dev)
         tr = None
         if trace:
-            tr = torch.zeros(horizon, K, self._trace_floats(kind, obs_dim, act_dim), dtype=torch.float32, device=dev)
+            tr = torch.zeros(horizon, K, self._trace_floats(env, obs_dim, act_dim), dtype=torch.float32, device=dev)
         nm = self._normalizer
         ac = self._actor
-        _lib.check(lib.osa_eval_episodes(
+        _lib.check(play(
             kind, K, obs_dim, act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(nm._mean) if nm else None,
             _lib.ptr(nm._std) if nm else None, _lib.ptr(nm._count) if nm else None,
             float(nm._clip_value) if nm else 0.0, _lib.ptr(lo), _lib.ptr(hi), -1.0, 1.0,
             env._seed & 0xFFFFFFFFFFFFFFFF, horizon, env._cost_p, horizon,
             int(self._saute), self._budget if self._saute else 0.0, self._saute_gamma if self._saute else 0.0,
             int(self._early_terminated), self._cost_limit, cost_criteria, _lib.ptr(ret), _lib.ptr(cost),
-            _lib.ptr(length), _lib.ptr(tr), _lib.stream_ptr()), 'osa_eval_episodes')
+            _lib.ptr(length), _lib.ptr(tr), _lib.stream_ptr()), entry)
         self.trace = tr
         env.close()
         return ret, cost, length
@@ -213,7 +229,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         K = int(env.num_envs)
         obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
         lo, hi = self._scale_bounds(env)
-        device_env = self._user_env is None and envs_mod.ENV_REGISTRY.get(self._env_id) in DEVICE_ENVS
+        device_env = self._user_env is None and _device_env_class(self._env_id) is not None
         max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
         state_w = getattr(env, 'trace_state_floats', 0)  # state floats of a trace record
         f64 = dict(dtype=torch.float64, device=dev)
@@ -227,7 +243,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             gamma = torch.tensor([self._saute_gamma], dtype=torch.float32, device=dev)
         tr = None
         if trace:
-            tr = torch.zeros(max_steps, K, self._trace_floats(_env_kind(env), obs_dim, act_dim), dtype=torch.float32,
+            tr = torch.zeros(max_steps, K, self._trace_floats(env, obs_dim, act_dim), dtype=torch.float32,
                              device=dev)
         obs, _ = env.reset()
         for t in range(max_steps):
@@ -277,8 +293,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         opts = self._render_defaults
         width, height = int(width or opts['width']), int(height or opts['height'])
         camera = render_mod.camera_index(camera_name or opts['camera_name'])
-        cls = envs_mod.ENV_REGISTRY.get(self._env_id)
-        if self._user_env is not None or cls not in DEVICE_ENVS or not cls.trace_state_floats:
+        cls = _device_env_class(self._env_id)
+        if self._user_env is not None or cls is None or not (cls.trace_state_floats and cls.render_state):
             what = 'an env object given as env=' if self._user_env is not None else self._env_id
             raise ValueError(f'{what} has no state row to draw: render() takes the geometric device envs '
                              '(SynthReach-v0, SynthNav*-v0)')

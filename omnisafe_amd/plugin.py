@@ -83,11 +83,14 @@ def install(algorithms: tuple[str, ...] | None = None) -> list[str]:
     # make the synthetic ids valid env ids for the reference's config checks (envs/core.py:362-386)
     reg = ref_env_core.ENV_REGISTRY
     known = set(reg.support_envs())
-    for cls in amd_envs.DeviceVectorEnv.__subclasses__():
+    # (the built-in families, then the classes register_device_env has made so far, keyed by their struct)
+    keyed = [('OmnisafeAmd' + cls.__name__, cls) for cls in amd_envs.DeviceVectorEnv.__subclasses__()]
+    keyed += [('OmnisafeAmdCustom' + cls.struct, cls) for cls in amd_envs.custom_env_classes()]
+    for key, cls in keyed:
         new_ids = [e for e in cls._support_envs if e not in known]  # noqa: SLF001
         if new_ids:
-            reg._class['OmnisafeAmd' + cls.__name__] = cls  # noqa: SLF001
-            reg._support_envs['OmnisafeAmd' + cls.__name__] = new_ids  # noqa: SLF001
+            reg._class[key] = cls  # noqa: SLF001
+            reg._support_envs[key] = new_ids  # noqa: SLF001
     del omnisafe
     return swapped
 
