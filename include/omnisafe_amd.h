@@ -621,6 +621,23 @@ int osa_gmlp_minibatch_ext(const osa_gmlp_desc* desc, float* params, float* adam
                            const osa_ppo_hparams* hp, int loss_kind, int mode, int nets_mask, const float* vec,
                            float fvp_scale, float* ws, size_t ws_floats, float* step_stats,
                            const osa_surrogate_ext* ext, void* stream);
+/* The launch plan of osa_gmlp_minibatch_ext for these arguments IN THIS PROCESS (the once-per-process switches
+ * OSA_GMLP_DEEP, OSA_GMLP_XCD_ORDER, OSA_GMLP_ROW_SPLIT, OSA_GMLP_TOP_FUSE as the launchers read them): the launchers'
+ * own decision functions, walked without a launch.  Host only, no GPU needed.  out[0 .. n) receives
+ *   [0] ints of the whole record   [1] 1 skinny step (B <= 64) / 0 tiled   [2] fusedn: clip norm from the Gram matrices
+ *   [3..5] per network: top layer's forward pass inside the launch below   [6..8] per network: loss inside the top
+ *   layer's backward launch   [9] sk_maxT1: workgroups per network of the skinny weight-gradient launch
+ *   [10..33] sk_tk[net][layer]: K tiles per 64-row tile of that launch   [34..57] S[net][layer]: row splits of the tiled
+ *   weight-gradient GEMM   [58] launches of the tiled step's GEMM kernel (0 for a skinny step), then per launch, in
+ *   launch order, OSA_GMLP_PLAN_LAUNCH ints:
+ *   TM, TN, BK, AT, BT (the instantiation of the GEMM kernel), splits (grid.z per problem), row split S (0: the launch
+ *   does not slice K through slabs), problems, Si[3] (per problem, under a row split), splits[3] (per problem), and
+ *   whether the launch remaps its tiles to the XCDs (OSA_GMLP_XCD_ORDER).
+ * OSA_EINVAL with out[0] set when n is too short. */
+#define OSA_GMLP_PLAN_HEAD 59
+#define OSA_GMLP_PLAN_LAUNCH 15
+int osa_gmlp_plan(const osa_gmlp_desc* desc, long B, int loss_kind, int mode, int nets_mask, const osa_ppo_hparams* hp,
+                  int* out, int n);
 /* osa_adam_apply for general networks; fin8x3: 24 floats of device scratch. */
 int osa_gmlp_adam_apply(const osa_gmlp_desc* desc, float* params, float* adam_m, float* adam_v, int* adam_step,
                         float* grads, const osa_ppo_hparams* hp, int nets_mask, float* fin8x3, void* stream);

@@ -53,6 +53,7 @@ SIGNATURES: dict[str, tuple] = {
                                 _I, _P, _F, _P, C.c_size_t, _P, _P]),
     'osa_gmlp_minibatch_ext': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _I,
                                     _I, _P, _F, _P, C.c_size_t, _P, _P, _P]),
+    'osa_gmlp_plan': (_I, [_P, _L, _I, _I, _I, _P, _P, _I]),
     'osa_gmlp_adam_apply': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'osa_gmlp_actor_stats': (_I, [_P, _P, _P, _I, _L, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P,
                                   C.c_size_t, _P, _P]),

@@ -417,14 +417,18 @@ __global__ __launch_bounds__(256) void gm_gemm_kernel(GArgs g) {
     }
 }
 
-template <int TM, int TN, int BK, bool AT, bool BT>
-int gm_launch(const GArgs& g_, int maxM, int maxN, hipStream_t st) {
-  static const int xcd_sw = [] {  // (A/B switch: OSA_GMLP_XCD_ORDER=0 keeps the dispatch order)
+int gm_xcd_order() {  // (A/B switch, read once: OSA_GMLP_XCD_ORDER=0 keeps the dispatch order)
+  static const int xcd_sw = [] {
     const char* v = getenv("OSA_GMLP_XCD_ORDER");
     return (v != nullptr && v[0] == '0' && v[1] == 0) ? 0 : 1;
   }();
+  return xcd_sw;
+}
+
+template <int TM, int TN, int BK, bool AT, bool BT>
+int gm_launch(const GArgs& g_, int maxM, int maxN, hipStream_t st) {
   GArgs g = g_;
-  g.xcd = xcd_sw;
+  g.xcd = gm_xcd_order();
   constexpr size_t lds = (size_t)2 * ((AT ? BK * (TM + 8) : TM * (BK + 4)) + (BT ? BK * (TN + 8) : TN * (BK + 4))) * sizeof(float);
   if constexpr (lds > 64 * 1024) {
     static OsaPerDeviceOnce attr_set;
@@ -443,20 +447,33 @@ int gm_launch(const GArgs& g_, int maxM, int maxN, hipStream_t st) {
 #ifndef GM_BK
 #define GM_BK 16  // K step of the launches with enough workgroups (A/B: -DGM_BK=32)
 #endif
-// one grouped launch; the tile follows the largest problem (64-wide tiles for skinny ones), the K step the number of
-// workgroups the launch will have
-template <bool AT, bool BT>
-int gm_gemm(const GArgs& g, hipStream_t st) {
-  int maxM = 0, maxN = 0;
-  for (int i = 0; i < g.nprob; ++i) {
-    const int nc = g.p[i].ones_n >= 0 ? (g.p[i].ldc > g.p[i].N + 1 ? g.p[i].ldc : g.p[i].N + 1) : g.p[i].N;
-    if (g.p[i].M > maxM) maxM = g.p[i].M;
-    if (nc > maxN) maxN = nc;
-  }
-  if (g.nprob == 0 || maxM == 0) return OSA_OK;
+
+// ---- the launch plan.  Which kernel a launch takes, how a K range is sliced and which launches a skinny step fuses are
+// pure host functions of the shapes (gm_pick_tile, gm_rows_plan, gs_plan, gm_splits) that the launchers themselves
+// call; osa_gmlp_plan walks the same launchers with a recorder set and `dry` on, so that what it reports is what a step
+// of this process does -- the once-per-process switches (OSA_GMLP_DEEP, _XCD_ORDER, _ROW_SPLIT, _TOP_FUSE) included.
+struct GPlanRec {
+  int* out;
+  int n, cap;
+  bool dry;          // record only: nothing is launched, no pointer is followed
+  int rowS, Si[3];   // the row split of the launch about to be recorded (gm_gemm_rows), 0: none
+  int launches;
+};
+thread_local GPlanRec* gm_plan = nullptr;
+inline void gm_plan_put(int v) {
+  if (gm_plan->n < gm_plan->cap) gm_plan->out[gm_plan->n] = v;
+  ++gm_plan->n;
+}
+
+// the tile of one grouped launch follows its largest problem (64-wide tiles for skinny ones), the K step the number
+// of workgroups the launch will have
+struct GTile {
+  int TM, TN, BK;
+};
+GTile gm_pick_tile(int maxM, int maxN, int nprob, int splits) {
   bool bigM = maxM > 64, bigN = maxN > 64;
   auto count = [&](int tm, int tn) {
-    return (long)((maxM + tm - 1) / tm) * ((maxN + tn - 1) / tn) * g.nprob * g.splits;
+    return (long)((maxM + tm - 1) / tm) * ((maxN + tn - 1) / tn) * nprob * splits;
   };
   // a launch that would leave most of the chip idle takes the 64-wide tiles (twice / four times the workgroups)
   if (bigN && count(bigM ? 128 : 64, 128) < 128) bigN = false;
@@ -467,11 +484,37 @@ int gm_gemm(const GArgs& g, hipStream_t st) {
     return v == nullptr ? -1 : (v[0] == '1' ? 1 : 0);
   }();
   const bool deep = deep_sw >= 0 ? deep_sw == 1 : wgs < 256;  // few workgroups: latency-bound -> K step 64
+  return GTile{bigM ? 128 : 64, bigN ? 128 : 64, deep ? 64 : GM_BK};
+}
+
+// one grouped launch
+template <bool AT, bool BT>
+int gm_gemm(const GArgs& g, hipStream_t st) {
+  int maxM = 0, maxN = 0;
+  for (int i = 0; i < g.nprob; ++i) {
+    const int nc = g.p[i].ones_n >= 0 ? (g.p[i].ldc > g.p[i].N + 1 ? g.p[i].ldc : g.p[i].N + 1) : g.p[i].N;
+    if (g.p[i].M > maxM) maxM = g.p[i].M;
+    if (nc > maxN) maxN = nc;
+  }
+  if (g.nprob == 0 || maxM == 0) return OSA_OK;
+  const GTile t = gm_pick_tile(maxM, maxN, g.nprob, g.splits);
+  if (gm_plan) {  // one record per launch: OSA_GMLP_PLAN_LAUNCH ints
+    gm_plan_put(t.TM); gm_plan_put(t.TN); gm_plan_put(t.BK); gm_plan_put(AT); gm_plan_put(BT); gm_plan_put(g.splits);
+    gm_plan_put(gm_plan->rowS);
+    gm_plan_put(g.nprob);
+    for (int i = 0; i < 3; ++i) gm_plan_put(gm_plan->rowS && i < g.nprob ? gm_plan->Si[i] : 0);
+    for (int i = 0; i < 3; ++i) gm_plan_put(i < g.nprob ? g.p[i].splits : 0);
+    gm_plan_put(gm_xcd_order());
+    gm_plan->rowS = 0;
+    ++gm_plan->launches;
+    if (gm_plan->dry) return OSA_OK;
+  }
+  const bool deep = t.BK == 64;
 #define GM_GO(TM_, TN_)                                                              \
   return deep ? gm_launch<TM_, TN_, 64, AT, BT>(g, maxM, maxN, st) : gm_launch<TM_, TN_, GM_BK, AT, BT>(g, maxM, maxN, st)
-  if (bigM && bigN) GM_GO(128, 128);
-  if (bigM) GM_GO(128, 64);
-  if (bigN) GM_GO(64, 128);
+  if (t.TM == 128 && t.TN == 128) GM_GO(128, 128);
+  if (t.TM == 128) GM_GO(128, 64);
+  if (t.TN == 128) GM_GO(64, 128);
   GM_GO(64, 64);
 #undef GM_GO
 }
@@ -512,8 +555,13 @@ __global__ __launch_bounds__(256) void gm_rows_epilogue_kernel(GEpiArgs a) {
   e.C[(long)m * e.ldc + n] = v;
 }
 
-template <bool AT, bool BT>
-int gm_gemm_rows(GArgs g, float* scratch, size_t scratch_floats, hipStream_t st) {
+// The K slices of one launch of gm_gemm_rows: S for the launch (1: no split, the plain grouped launch), Si <= S per
+// problem (a problem whose K is short keeps slices of at least 128).
+struct GRowPlan {
+  int S, Si[3];
+};
+GRowPlan gm_rows_plan(const GArgs& g, bool have_scratch, size_t scratch_floats) {
+  GRowPlan r = {1, {1, 1, 1}};
   int maxM = 0, maxN = 0, maxK = 0;
   for (int i = 0; i < g.nprob; ++i) {
     if (g.p[i].M > maxM) maxM = g.p[i].M;
@@ -524,20 +572,42 @@ int gm_gemm_rows(GArgs g, float* scratch, size_t scratch_floats, hipStream_t st)
     const char* v = getenv("OSA_GMLP_ROW_SPLIT");
     return v != nullptr && v[0] == '0' && v[1] == 0;
   }();
-  if (off || g.nprob == 0 || maxM > GM_ROW_SPLIT_ROWS || maxK < 512 || scratch == nullptr) return gm_gemm<AT, BT>(g, st);
+  if (off || g.nprob == 0 || maxM > GM_ROW_SPLIT_ROWS || maxK < 512 || !have_scratch) return r;
   const long tiles = (long)((maxM + 63) / 64) * ((maxN + 63) / 64) * g.nprob;
   long S = 1;  // a power of two: equal slices, whole K steps
   while (S < GM_ROW_SPLITS && tiles * S < 320 && maxK / (2 * S) >= 128) S *= 2;
+  if (S < 2) return r;
+  size_t off_f = 0;
+  for (int i = 0; i < g.nprob; ++i) {
+    const GProb& p = g.p[i];
+    int Si = (int)S;
+    while (Si > 1 && p.K / Si < 128) Si /= 2;
+    const size_t need = (size_t)Si * p.M * p.ldc;
+    if (off_f + need > scratch_floats) return GRowPlan{1, {1, 1, 1}};  // (the slabs do not fit: no split)
+    r.Si[i] = Si;
+    off_f += (need + 3) / 4 * 4;
+  }
+  r.S = (int)S;
+  return r;
+}
+
+template <bool AT, bool BT>
+int gm_gemm_rows(GArgs g, float* scratch, size_t scratch_floats, hipStream_t st) {
+  int maxM = 0, maxN = 0;
+  for (int i = 0; i < g.nprob; ++i) {
+    if (g.p[i].M > maxM) maxM = g.p[i].M;
+    if (g.p[i].N > maxN) maxN = g.p[i].N;
+  }
+  const GRowPlan rp = gm_rows_plan(g, scratch != nullptr, scratch_floats);
+  const long S = rp.S;
   if (S < 2) return gm_gemm<AT, BT>(g, st);
   GEpiArgs ea = {};
   size_t off_f = 0;
   for (int i = 0; i < g.nprob; ++i) {
     GProb& p = g.p[i];
     if (p.accumulate || p.ones_n >= 0 || p.cb) return OSA_EINVAL;  // (weight-gradient problems never come here)
-    int Si = (int)S;
-    while (Si > 1 && p.K / Si < 128) Si /= 2;
+    const int Si = rp.Si[i];
     const size_t need = (size_t)Si * p.M * p.ldc;
-    if (off_f + need > scratch_floats) return gm_gemm<AT, BT>(g, st);
     GEpi& e = ea.e[ea.n++];
     e.slab = scratch + off_f; e.C = p.C; e.bias = p.bias; e.aux = p.aux; e.M = p.M; e.N = p.N; e.ldc = p.ldc;
     e.ldaux = p.ldaux; e.act = p.act; e.dact = p.dact; e.S = Si; e.slab_stride = (long)p.M * p.ldc;
@@ -546,8 +616,13 @@ int gm_gemm_rows(GArgs g, float* scratch, size_t scratch_floats, hipStream_t st)
     off_f += (need + 3) / 4 * 4;
   }
   g.splits = (int)S;
+  if (gm_plan) {
+    gm_plan->rowS = (int)S;
+    for (int i = 0; i < 3; ++i) gm_plan->Si[i] = rp.Si[i];
+  }
   const int rc = gm_gemm<AT, BT>(g, st);
   if (rc != OSA_OK) return rc;
+  if (gm_plan && gm_plan->dry) return OSA_OK;
   hipLaunchKernelGGL(gm_rows_epilogue_kernel, dim3((unsigned)(((long)maxM * maxN + 255) / 256), ea.n), dim3(256), 0, st, ea);
   return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
 }
@@ -938,6 +1013,53 @@ bool gs_enabled() {  // (A/B and test switch: OSA_GMLP_SKINNY=0 keeps small mini
   return !(v != nullptr && v[0] == '0' && v[1] == 0);
 }
 
+// which of the two steps a minibatch of B rows takes
+bool gm_takes_skinny(long B, int loss_kind) { return B <= GS_MAX_ROWS && loss_kind != 2 && gs_enabled(); }
+
+int gm_minibatch_tiled(const GLayout& lo, const GWs& w, float* params, float* adam_m, float* adam_v, int* adam_step,
+                       float* grads, const float* obs, int ld_obs, const float* act, int ld_act, const float* logp,
+                       const float* target_value_r, const float* target_value_c, const float* adv_r,
+                       const float* adv_c, const long* idx, long B, const float* lagrange, const osa_ppo_hparams* hp,
+                       int loss_kind, int mode, int mask, const float* vec, float fvp_scale, float* ws,
+                       float* step_stats, const osa_surrogate_ext* ext, hipStream_t st, bool dry);
+
+// What a skinny step fuses, from the shapes, the networks in `mask` and the mode:
+//   fusedn      (round 6) mode 0: the clip norm comes out of the forward / top / backward launches (gs_gram_norm) and the
+//               top layer's forward pass rides in the launch below it -- 2 L - 1 launches instead of 2 L + 1.  Every
+//               active network needs a hidden layer and a top layer of at most 32 outputs; OSA_GMLP_NORM_FUSE=0 keeps
+//               round 5's launches (A/B, tests)
+//   top_in_fwd  per network: its top layer's forward pass inside the launch of the layer below (outputs <= 8 wide)
+//   fuse        the loss inside the top layer's backward launch: top layers up to 32 wide
+struct GSPlan {
+  bool fusedn, fuse, top_in_fwd[3];
+};
+GSPlan gs_plan(const GLayout& lo, int mask, int mode) {
+  GSPlan s;
+  const char* nf = getenv("OSA_GMLP_NORM_FUSE");  // (read per call: the tests switch it inside one process)
+  s.fusedn = mode == 0 && !(nf != nullptr && nf[0] == '0' && nf[1] == 0);
+  s.fuse = true;
+  for (int net = 0; net < 3; ++net) {
+    if (!((mask >> net) & 1)) continue;
+    const GNet& n = lo.n[net];
+    if (n.L < 2 || n.ldh[n.L - 1] > 32) s.fusedn = false;
+    if (n.ldh[n.L - 1] > 32) s.fuse = false;
+  }
+  {
+    const char* v = getenv("OSA_GMLP_TOP_FUSE");
+    if (v != nullptr && v[0] == '0' && v[1] == 0) s.fusedn = false;
+  }
+  static const bool fuse_on = [] {  // (A/B switch: OSA_GMLP_TOP_FUSE=0 keeps the loss a launch of its own)
+    const char* v = getenv("OSA_GMLP_TOP_FUSE");
+    return !(v != nullptr && v[0] == '0' && v[1] == 0);
+  }();
+  s.fuse = s.fuse && fuse_on;
+  for (int net = 0; net < 3; ++net) {
+    const GNet& n = lo.n[net];
+    s.top_in_fwd[net] = ((mask >> net) & 1) && s.fusedn && n.ldh[n.L - 1] <= 8;
+  }
+  return s;
+}
+
 // One optimiser step (or its gradient: mode 1 / 2) of a minibatch of B <= 64 rows on the skinny kernels: L forward
 // launches (layer 0 reads the minibatch's rows in place: no gather), loss + top layer's backward in one launch, L - 2
 // more backward-data launches, ONE weight-gradient launch over all layers (norm partials), then clip + Adam from
@@ -950,23 +1072,12 @@ int gm_minibatch_skinny(const GLayout& lo, const GWs& w, float* params, float* a
                         int loss_kind, int mode, int mask, float* ws, float* step_stats, const osa_surrogate_ext* ext,
                         hipStream_t st) {
   int maxL = 0;
-  // (round 6) mode 0: the clip norm comes out of the forward / top / backward launches (gs_gram_norm) and the top layer's
-  // forward pass rides in the launch below it -- 2 L - 1 launches instead of 2 L + 1.  Every active network needs a
-  // hidden layer and a top layer of at most 32 outputs; OSA_GMLP_NORM_FUSE=0 keeps round 5's launches (A/B, tests).
-  const char* nf = getenv("OSA_GMLP_NORM_FUSE");  // (read per call: the tests switch it inside one process)
-  bool fusedn = mode == 0 && !(nf != nullptr && nf[0] == '0' && nf[1] == 0);
-  for (int net = 0; net < 3; ++net) {
-    if (!((mask >> net) & 1)) continue;
-    const GNet& n = lo.n[net];
-    if (n.L > maxL) maxL = n.L;
-    if (n.L < 2 || n.ldh[n.L - 1] > 32) fusedn = false;
-  }
-  {
-    const char* v = getenv("OSA_GMLP_TOP_FUSE");
-    if (v != nullptr && v[0] == '0' && v[1] == 0) fusedn = false;
-  }
+  for (int net = 0; net < 3; ++net)
+    if (((mask >> net) & 1) && lo.n[net].L > maxL) maxL = lo.n[net].L;
+  const GSPlan sp = gs_plan(lo, mask, mode);
+  const bool fusedn = sp.fusedn;
   const float c2 = hp->use_critic_norm ? 2.f * hp->critic_norm_coef : 0.f;
-  auto top_in_fwd = [&](const GNet& n) { return fusedn && n.ldh[n.L - 1] <= 8; };  // the top layer's forward pass fused
+  auto top_in_fwd = [&](const GNet& n) { return sp.top_in_fwd[&n - lo.n]; };  // the top layer's forward pass fused
   // ---- forward, layer by layer (the networks of a layer in one launch).  No gather launch: layer 0 reads the caller's
   // observation rows through the minibatch's indices, the loss its scalars and action rows likewise
   for (int l = 0; l < maxL; ++l) {
@@ -1023,14 +1134,13 @@ int gm_minibatch_skinny(const GLayout& lo, const GWs& w, float* params, float* a
   const GNet& an = lo.n[0];
   GLossArgs la = {};
   la.R = B; la.act_dim = lo.act_dim; la.lda = lo.lda;
-  bool fuse = true;  // loss inside the top layer's backward launch: top layers up to 32 wide
+  const bool fuse = sp.fuse;  // loss inside the top layer's backward launch: top layers up to 32 wide
   for (int net = 0; net < 3; ++net) {
     const GNet& n = lo.n[net];
     la.out[net] = ws + w.h[net][n.L - 1];
     la.ldo[net] = n.ldh[n.L - 1];
     la.dz[net] = ws + w.zs[net][n.L - 1];
     la.ldz[net] = n.ldh[n.L - 1];
-    if (((mask >> net) & 1) && n.ldh[n.L - 1] > 32) fuse = false;
   }
   la.log_std = params + an.oLS; la.lagrange = lagrange;
   la.clip = hp->clip; la.loss_kind = loss_kind; la.nets_mask = mask;
@@ -1039,11 +1149,6 @@ int gm_minibatch_skinny(const GLayout& lo, const GWs& w, float* params, float* a
   la.scal = ws + w.scal; la.actg = ws + w.actg;  // (fused: gathered by the first launch)
   la.sp[0] = logp; la.sp[1] = adv_r; la.sp[2] = adv_c; la.sp[3] = target_value_r; la.sp[4] = target_value_c;
   gm_fill_ext(la, ext, idx, step_stats);
-  static const bool fuse_on = [] {  // (A/B switch: OSA_GMLP_TOP_FUSE=0 keeps the loss a launch of its own)
-    const char* v = getenv("OSA_GMLP_TOP_FUSE");
-    return !(v != nullptr && v[0] == '0' && v[1] == 0);
-  }();
-  fuse = fuse && fuse_on;
   if (fuse) {
     GSArgs g = {};
     g.R = (int)B;
@@ -1253,12 +1358,31 @@ int osa_gmlp_minibatch_ext(const osa_gmlp_desc* desc, float* params, float* adam
   hipStream_t st = osa_stream(stream);
   int mask = nets_mask & (hp->use_cost ? 7 : 3);
   if (loss_kind == 2) mask = 1;
-  if (B <= GS_MAX_ROWS && loss_kind != 2 && gs_enabled())
+  if (gm_takes_skinny(B, loss_kind))
     return gm_minibatch_skinny(lo, w, params, adam_m, adam_v, adam_step, grads, obs, ld_obs, act, ld_act, logp,
                                target_value_r, target_value_c, adv_r, adv_c, idx, B, lagrange, hp, loss_kind, mode, mask,
                                ws, step_stats, ext, st);
-  if ((rc = gm_gather(lo, w, ws, B, idx, obs, ld_obs, loss_kind == 2 ? nullptr : act, ld_act, logp, adv_r, adv_c,
-                      target_value_r, target_value_c, st)) != OSA_OK)
+  return gm_minibatch_tiled(lo, w, params, adam_m, adam_v, adam_step, grads, obs, ld_obs, act, ld_act, logp,
+                            target_value_r, target_value_c, adv_r, adv_c, idx, B, lagrange, hp, loss_kind, mode, mask, vec,
+                            fvp_scale, ws, step_stats, ext, st, false);
+}
+
+}  // extern "C"
+
+namespace {
+
+// One optimiser step (or its gradient) of a minibatch on the tiled GEMM: gather, forward, loss, per layer from the top
+// the weight-gradient and backward-data launches, slab sum + norms, clip + Adam.  `dry`: the launch plan only
+// (osa_gmlp_plan) -- the GEMM launchers record their choices, nothing is launched and no pointer is followed.
+int gm_minibatch_tiled(const GLayout& lo, const GWs& w, float* params, float* adam_m, float* adam_v, int* adam_step,
+                       float* grads, const float* obs, int ld_obs, const float* act, int ld_act, const float* logp,
+                       const float* target_value_r, const float* target_value_c, const float* adv_r,
+                       const float* adv_c, const long* idx, long B, const float* lagrange, const osa_ppo_hparams* hp,
+                       int loss_kind, int mode, int mask, const float* vec, float fvp_scale, float* ws,
+                       float* step_stats, const osa_surrogate_ext* ext, hipStream_t st, bool dry) {
+  int rc;
+  if (!dry && (rc = gm_gather(lo, w, ws, B, idx, obs, ld_obs, loss_kind == 2 ? nullptr : act, ld_act, logp, adv_r, adv_c,
+                              target_value_r, target_value_c, st)) != OSA_OK)
     return rc;
   if ((rc = gm_forward(lo, w, ws, params, B, mask, st)) != OSA_OK) return rc;
   const GNet& an = lo.n[0];
@@ -1311,8 +1435,10 @@ int osa_gmlp_minibatch_ext(const osa_gmlp_desc* desc, float* params, float* adam
   la.dls = ws + w.dls; la.lpart = ws + w.lpart; la.nblk = w.nblk;
   la.tmean = ws + w.t[an.L - 1]; la.ldt = an.ldh[an.L - 1]; la.fvp_scale = fvp_scale;
   gm_fill_ext(la, ext, idx, step_stats);
-  hipLaunchKernelGGL(gm_loss_kernel, dim3(w.nblk, 3), dim3(256), 0, st, la);
-  OSA_CHECK_LAUNCH();
+  if (!dry) {
+    hipLaunchKernelGGL(gm_loss_kernel, dim3(w.nblk, 3), dim3(256), 0, st, la);
+    OSA_CHECK_LAUNCH();
+  }
   // ---- backward: weight (+ bias) gradients into the slabs, then dZ of the layer below
   int maxL = 0;
   for (int net = 0; net < 3; ++net)
@@ -1354,6 +1480,7 @@ int osa_gmlp_minibatch_ext(const osa_gmlp_desc* desc, float* params, float* adam
     for (int net = 0; net < 3; ++net)
       if (((mask >> net) & 1) && lo.n[net].L - 1 - step > 0) cur[net] ^= 1;
   }
+  if (dry) return OSA_OK;
   // ---- slab sum, L2 / entropy terms, norms; clip factor and Adam scalars; clip (+ Adam)
   GRedArgs ra = {};
   ra.P = lo.P; ra.nblk = w.nblk; ra.nb = w.nb; ra.act_dim = lo.act_dim; ra.lda = lo.lda;
@@ -1381,6 +1508,50 @@ int osa_gmlp_minibatch_ext(const osa_gmlp_desc* desc, float* params, float* adam
                        ws + w.fin, params, adam_m, adam_v, grads, hp->beta1, hp->beta2, hp->adam_eps);
   OSA_CHECK_LAUNCH();
   return OSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The launch plan of osa_gmlp_minibatch_ext(desc, ..., B, ..., loss_kind, mode, nets_mask, ...) in this process, as a
+// flat record (include/omnisafe_amd.h has the layout).  Host only: launches nothing, needs no GPU.
+int osa_gmlp_plan(const osa_gmlp_desc* desc, long B, int loss_kind, int mode, int nets_mask, const osa_ppo_hparams* hp,
+                  int* out, int n) {
+  OSA_REQUIRE(desc && hp && out && n >= OSA_GMLP_PLAN_HEAD && B > 0);
+  OSA_REQUIRE(mode >= 0 && mode <= 2 && loss_kind >= 0 && loss_kind <= 2);
+  GLayout lo;
+  int rc = gm_make_layout(desc, &lo);
+  if (rc != OSA_OK) return rc;
+  const GWs w = gm_ws(lo, B);
+  int mask = nets_mask & (hp->use_cost ? 7 : 3);
+  if (loss_kind == 2) mask = 1;
+  GPlanRec rec = {out, 0, n, true, 0, {0, 0, 0}, 0};
+  gm_plan = &rec;
+  const bool skinny = gm_takes_skinny(B, loss_kind);
+  const GSPlan sp = skinny ? gs_plan(lo, mask, mode) : GSPlan{false, false, {false, false, false}};
+  gm_plan_put(0);  // [0] the ints of the whole record (below)
+  gm_plan_put(skinny);
+  gm_plan_put(sp.fusedn);
+  for (int net = 0; net < 3; ++net) gm_plan_put(sp.top_in_fwd[net]);
+  for (int net = 0; net < 3; ++net) gm_plan_put(skinny && sp.fuse && ((mask >> net) & 1));
+  gm_plan_put(skinny ? w.sk_maxT1 : 0);
+  for (int net = 0; net < 3; ++net)
+    for (int l = 0; l < GM_MAXL; ++l) gm_plan_put(skinny && l < lo.n[net].L ? w.sk_tk[net][l] : 0);
+  for (int net = 0; net < 3; ++net)
+    for (int l = 0; l < GM_MAXL; ++l) gm_plan_put(w.S[net][l]);
+  gm_plan_put(0);  // [OSA_GMLP_PLAN_HEAD - 1] the launches of the tiled step
+  if (!skinny) {
+    static float nowhere[4];  // (a base for the pointer arithmetic of the launch descriptions; never followed)
+    rc = gm_minibatch_tiled(lo, w, nowhere, nowhere, nowhere, nullptr, nowhere, nowhere, lo.ldx, nowhere, lo.lda, nowhere,
+                            nowhere, nowhere, nowhere, nowhere, nullptr, B, nowhere, hp, loss_kind, mode, mask, nowhere,
+                            0.f, nowhere, nowhere, nullptr, nullptr, true);
+  }
+  gm_plan = nullptr;
+  if (rc != OSA_OK) return rc;
+  out[0] = rec.n;
+  if (OSA_GMLP_PLAN_HEAD - 1 < n) out[OSA_GMLP_PLAN_HEAD - 1] = rec.launches;
+  return rec.n <= n ? OSA_OK : OSA_EINVAL;  // (too short: out[0] says how many ints the record needs)
 }
 
 int osa_gmlp_adam_apply(const osa_gmlp_desc* desc, float* params, float* adam_m, float* adam_v, int* adam_step,

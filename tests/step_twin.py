@@ -33,6 +33,20 @@ twin and the kernels see the same numbers.
 `case_table()` is the table of the 64-row step (tests/test_step_oracle_gpu.py); `form_table()` that of the other forms
 of the same step -- several blocks + slab reduce, the chunked, wide and split passes, the large-batch partial
 gradients (tests/test_step_forms_gpu.py).  The twin itself is the same for all: a step of n rows is a step of n rows.
+
+General networks.  A case may carry `actor_hidden` / `critic_hidden` (0 to 7 hidden widths; None: [64, 64]) and
+`actor_act` / `critic_act` (ACTIVATIONS: tanh, relu, sigmoid, softplus, identity -- computed as the reference's torch
+modules do, utils/model.py get_activation, never through the output as the kernels take their derivatives).  With the
+defaults every number of the cases above is what it was.  `general_table()` is the table of the layer-wise path
+(csrc/general_mlp.hip + csrc/skinny_mlp.h; tests/test_general_step_gpu.py): per mechanism of that path the smallest
+shape that reaches it, named by the features `plan_features` reads from osa_gmlp_plan, the launchers' own decisions.
+Of the 24 instantiations (TM, TN, BK, form) of gm_gemm_kernel the table launches 15:
+    64 x 64 x 64 NT NN TN;  128 x 128 x 64 NT NN TN;  128 x 128 x 16 NT NN TN;  128 x 64 x 64 NT NN TN;
+    128 x 64 x 16 TN;  64 x 128 x 64 TN;  64 x 128 x 16 TN
+and no shape under the table's cost limits reaches the other nine (tests/test_step_twin.py COVERED_KERNELS says why):
+    64 x 64 x 16 in all three forms (K step 16 needs 256 workgroups, which a launch that was refused 128-wide tiles for
+    having fewer than 128 of them cannot have);  64 x 128 NT / NN at either K step (a minibatch of at most 64 rows on
+    the tiled step with a layer of 5 400 columns);  128 x 64 x 16 NT and NN (10 900 rows).
 """
 from __future__ import annotations
 
@@ -47,18 +61,42 @@ NETS = ('actor', 'reward_critic', 'cost_critic')
 F32 = np.float32
 
 
-def tensor_shapes(net: str, obs_dim: int, act_dim: int) -> 'OrderedDict[str, tuple]':
+ACTIVATIONS = ('tanh', 'relu', 'sigmoid', 'softplus', 'identity')  # the OSA_ACT_* kinds, in the order of their codes
+
+
+def tensor_shapes(net: str, obs_dim: int, act_dim: int, hidden=None) -> 'OrderedDict[str, tuple]':
     """The reference's named_parameters of one network, in its order (log_std first: a module's own parameters come
-    before its sub-modules')."""
+    before its sub-modules').  `hidden`: the widths of its hidden layers (utils/model.py build_mlp_network: Linear
+    layers at the Sequential's indices 0, 2, 4, ...); None: [64, 64]."""
     out = act_dim if net == 'actor' else 1
     pre = 'mean' if net == 'actor' else 'critic_0'
+    sizes = [obs_dim] + [int(h) for h in ((H, H) if hidden is None else hidden)] + [out]
     sh = OrderedDict()
     if net == 'actor':
         sh['log_std'] = (act_dim,)
-    for j, (o, i) in zip((0, 2, 4), ((H, obs_dim), (H, H), (out, H))):
-        sh[f'{pre}.{j}.weight'] = (o, i)
-        sh[f'{pre}.{j}.bias'] = (o,)
+    for j in range(len(sizes) - 1):
+        sh[f'{pre}.{2 * j}.weight'] = (sizes[j + 1], sizes[j])
+        sh[f'{pre}.{2 * j}.bias'] = (sizes[j + 1],)
     return sh
+
+
+def case_hidden(case: dict, net: str) -> list:
+    """The hidden widths of one network of a case ([64, 64] where the case does not say)."""
+    h = case.get('actor_hidden' if net == 'actor' else 'critic_hidden')
+    return [H, H] if h is None else list(h)
+
+
+def case_act(case: dict, net: str) -> str:
+    return case.get('actor_act' if net == 'actor' else 'critic_act', 'tanh')
+
+
+def case_shapes(case: dict, net: str) -> 'OrderedDict[str, tuple]':
+    return tensor_shapes(net, case['obs_dim'], case['act_dim'], case_hidden(case, net))
+
+
+def out_bias(case: dict) -> str:
+    """The name of the critics' output bias."""
+    return f"critic_0.{2 * len(case_hidden(case, 'reward_critic'))}.bias"
 
 
 def _f32(x) -> float:
@@ -66,10 +104,23 @@ def _f32(x) -> float:
     return float(F32(x))
 
 
-def _mlp(p: dict, pre: str, x: torch.Tensor) -> torch.Tensor:
-    h = torch.tanh(x @ p[f'{pre}.0.weight'].T + p[f'{pre}.0.bias'])
-    h = torch.tanh(h @ p[f'{pre}.2.weight'].T + p[f'{pre}.2.bias'])
-    return h @ p[f'{pre}.4.weight'].T + p[f'{pre}.4.bias']
+# the hidden activations as the reference's torch modules compute them (utils/model.py get_activation: nn.Tanh,
+# nn.ReLU, nn.Sigmoid, nn.Softplus with its defaults beta = 1, threshold = 20, nn.Identity)
+_ACT = {'tanh': torch.tanh, 'relu': torch.relu, 'sigmoid': torch.sigmoid,
+        'softplus': torch.nn.functional.softplus, 'identity': lambda z: z}
+
+
+def _mlp(p: dict, pre: str, x: torch.Tensor, act: str = 'tanh', pre_acts: list | None = None) -> torch.Tensor:
+    """Linear layers {pre}.0, {pre}.2, ... with `act` between them and none after the last.  `pre_acts`: a list that
+    receives the hidden layers' pre-activations."""
+    n = sum(1 for k in p if k.startswith(pre + '.') and k.endswith('.weight'))
+    h = x
+    for j in range(n - 1):
+        z = h @ p[f'{pre}.{2 * j}.weight'].T + p[f'{pre}.{2 * j}.bias']
+        if pre_acts is not None:
+            pre_acts.append(z)
+        h = _ACT[act](z)
+    return h @ p[f'{pre}.{2 * (n - 1)}.weight'].T + p[f'{pre}.{2 * (n - 1)}.bias']
 
 
 DEFAULT_HP = dict(clip=0.2, entropy_coef=0.0, critic_norm_coef=0.001, max_grad_norm=40.0, lr_actor=3e-4, lr_critic=3e-4,
@@ -90,7 +141,7 @@ def adam(p, m, v, g, lr: float, b1: float, b2: float, eps: float, t: int):
 
 
 def step(state: dict, batch: dict, hp: dict, lam: float, loss_kind: int, ext: dict | None = None,
-         dtype=torch.float64, nets=NETS) -> dict:
+         dtype=torch.float64, nets=NETS, acts: dict | None = None) -> dict:
     """One optimiser step of the networks in `nets` on the rows of `batch`.
 
     state   {'params' | 'm' | 'v': {net: {tensor name: array}}, 't': {net: steps taken so far}}
@@ -98,6 +149,7 @@ def step(state: dict, batch: dict, hp: dict, lam: float, loss_kind: int, ext: di
             looks at the behaviour policy also old_mean (n, A) and old_log_std (A,)
     hp      the fields of osa_ppo_hparams (DEFAULT_HP for what is missing)
     ext     None or the scalar fields of osa_surrogate_ext
+    acts    {net: hidden activation}, tanh for what is missing (the depth and widths are those of state['params'])
 
     Returns {net: {...}} with the losses, (actor) mean ratio / entropy / penalty, sum p^2, the UNCLIPPED gradient per
     reference tensor, its norm, the clip factor, p', m', v', the new step count and the two bias-correction factors;
@@ -112,8 +164,10 @@ def step(state: dict, batch: dict, hp: dict, lam: float, loss_kind: int, ext: di
     for net in nets:
         p = OrderedDict((k, as_t(v).clone().requires_grad_(True)) for k, v in state['params'][net].items())
         r = {}
+        act = (acts or {}).get(net, 'tanh')
+        zs = []  # the hidden layers' pre-activations (coverage checks)
         if net == 'actor':
-            dist = torch.distributions.Normal(_mlp(p, 'mean', b['obs']), torch.exp(p['log_std']))
+            dist = torch.distributions.Normal(_mlp(p, 'mean', b['obs'], act, zs), torch.exp(p['log_std']))
             logp_ = dist.log_prob(b['act']).sum(-1)
             ratio = torch.exp(logp_ - b['logp'])
             adv = (b['adv_r'] - lam * b['adv_c']) / (1.0 + lam)
@@ -146,7 +200,7 @@ def step(state: dict, batch: dict, hp: dict, lam: float, loss_kind: int, ext: di
                      mask=mask[:, 0], cost_surrogate=(ratio * b['adv_c']).mean().detach())
             lr = f['lr_actor']
         else:
-            v = torch.squeeze(_mlp(p, 'critic_0', b['obs']), -1)
+            v = torch.squeeze(_mlp(p, 'critic_0', b['obs'], act, zs), -1)
             mse = torch.nn.functional.mse_loss(v, b['target_value_r' if net == 'reward_critic' else 'target_value_c'])
             total = mse
             if hp['use_critic_norm']:
@@ -165,7 +219,8 @@ def step(state: dict, batch: dict, hp: dict, lam: float, loss_kind: int, ext: di
                                                 lr, f['beta1'], f['beta2'], f['adam_eps'], t)
         ss, ib = bias_corrections(lr, f['beta1'], f['beta2'], t)
         r.update(psq=sum(w.detach().pow(2).sum() for w in p.values()), grads=OrderedDict(zip(p.keys(), grads)),
-                 gnorm=gnorm, coef=coef, p=new_p, m=new_m, v=new_v, t=t, step_size=ss, inv_bc2_sqrt=ib)
+                 gnorm=gnorm, coef=coef, p=new_p, m=new_m, v=new_v, t=t, step_size=ss, inv_bc2_sqrt=ib,
+                 pre_acts=[z.detach() for z in zs])
         out[net] = r
     return out
 
@@ -195,12 +250,16 @@ def case_nets(case: dict) -> tuple:
     return nets
 
 
+def case_acts(case: dict) -> dict:
+    return {net: case_act(case, net) for net in NETS}
+
+
 def case_step(case: dict, state: dict, k: int, dtype=torch.float64, order=None) -> dict:
     """Minibatch k of the case's pass, taken from `state` (`order`: its rows in another order -- the same step)."""
     s, n = minibatches(case['M'], case['B'])[k]
     idx = case['perm'][s:s + n]
     return step(state, rows(case['data'], idx if order is None else idx[order]), case['hp'], case['lam'],
-                case['loss_kind'], case['ext'], dtype, case_nets(case))
+                case['loss_kind'], case['ext'], dtype, case_nets(case), case_acts(case))
 
 
 def run_pass(case: dict, dtype=torch.float64, state: dict | None = None) -> tuple:
@@ -232,7 +291,9 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
               norm_clip=None, use_max_grad_norm: int = 1, use_cost: bool = True, update_actor: bool = True,
               update_critics: bool = True, seeded_moments: bool = False, t0=(0, 0, 0), lr_actor: float = 3e-4,
               lr_critic: float = 3e-4, ext: dict | None = None, trust: bool = False, p3o: str | None = None,
-              w1_scale: float = 1.0, target_c_scale: float = 5.0) -> dict:
+              w1_scale: float = 1.0, target_c_scale: float = 5.0, actor_hidden=None, critic_hidden=None,
+              actor_act: str = 'tanh', critic_act: str = 'tanh', fan_scale: bool = False, z_shift=None,
+              seed: int = 0) -> dict:
     """One case of the GPU table.
 
     norm_clip  None: max_grad_norm = 1000 bites nowhere (the clip code runs, its factor is 1);  (net index | 'all', factor): max_grad_norm = factor x the
@@ -246,9 +307,25 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
     target_c_scale  spread of the cost critic's targets.  Its gradient is a mean of n signed residuals and shrinks like
                1 / sqrt n: at n = 2085 the default 5 leaves its norm at 1.63 next to the actor's 1.54, and a clip factor
                taken from the wrong network would pass; the large-batch cases pass 20 (norm about 6, as at 64 rows)
+    actor_hidden, critic_hidden   hidden widths, 0 to 7 of them (None: [64, 64]);  actor_act, critic_act: one of
+               ACTIVATIONS.  The defaults are the cases of case_table() / form_table(), number for number.
+    fan_scale  multiplies every weight matrix of more than 64 inputs by sqrt(64 / inputs) after it is drawn (what
+               w1_scale does for the first layer alone): a 1040-wide layer feeds the next one pre-activations of the
+               same size as a 64-wide one
+    z_shift    (scale, offset): the first-layer weights x scale and the first-layer biases + offset, after they are
+               drawn -- places the first-layer pre-activations where an activation's branches are (softplus above
+               its threshold of 20 and far below 0, sigmoid near 1)
+    seed       added to the seed of the case's random streams (a ReLU case whose draw puts a pre-activation at the
+               kink takes another one: check_coverage asserts the distance)
     """
-    rs = np.random.RandomState(20240 + 131 * obs_dim + 17 * act_dim + 7 * B + M)
-    shapes = {net: tensor_shapes(net, obs_dim, act_dim) for net in NETS}
+    rs = np.random.RandomState(20240 + 131 * obs_dim + 17 * act_dim + 7 * B + M + seed)
+    arch = dict(actor_hidden=None if actor_hidden is None else [int(h) for h in actor_hidden],
+                critic_hidden=None if critic_hidden is None else [int(h) for h in critic_hidden],
+                actor_act=actor_act, critic_act=critic_act, obs_dim=obs_dim, act_dim=act_dim)
+    assert actor_act in ACTIVATIONS and critic_act in ACTIVATIONS
+    assert all(len(case_hidden(arch, net)) <= 7 for net in NETS)
+    acts = case_acts(arch)
+    shapes = {net: case_shapes(arch, net) for net in NETS}
     params = {net: OrderedDict((k, rs.uniform(-0.2, 0.2, s).astype(F32)) for k, s in sh.items())
               for net, sh in shapes.items()}
     params['actor']['log_std'] = np.linspace(-0.5, 0.3, act_dim).astype(F32)
@@ -256,6 +333,17 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
         for net in NETS:
             k = ('mean' if net == 'actor' else 'critic_0') + '.0.weight'
             params[net][k] = (params[net][k] * F32(w1_scale)).astype(F32)
+    if fan_scale:
+        for net in NETS:
+            for k, w in params[net].items():
+                if w.ndim == 2 and w.shape[1] > 64:
+                    params[net][k] = (w * F32(math.sqrt(64.0 / w.shape[1]))).astype(F32)
+    if z_shift is not None:
+        for net in NETS:
+            pre = 'mean' if net == 'actor' else 'critic_0'
+            if len(case_hidden(arch, net)) > 0:
+                params[net][pre + '.0.weight'] = (params[net][pre + '.0.weight'] * F32(z_shift[0])).astype(F32)
+                params[net][pre + '.0.bias'] = (params[net][pre + '.0.bias'] + F32(z_shift[1])).astype(F32)
     m, v = _zero_like_state(shapes), _zero_like_state(shapes)
     # (the streams are drawn whether used or not: a case and its zero-moment twin share every other number)
     for net in NETS:
@@ -275,7 +363,8 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
     # actor's norm is near 1.5, the cost critic's targets are wide.
     obs64 = torch.from_numpy(data['obs'].astype(np.float64))
     with torch.no_grad():
-        vr = _mlp({k: torch.from_numpy(w.astype(np.float64)) for k, w in params['reward_critic'].items()}, 'critic_0', obs64)
+        vr = _mlp({k: torch.from_numpy(w.astype(np.float64)) for k, w in params['reward_critic'].items()}, 'critic_0', obs64,
+                  acts['reward_critic'])
     data['target_value_r'] = (vr[:, 0].numpy() + data['target_value_r']).astype(F32)
     # ---- clip cells: position k of the permutation gets cell k mod 6 = (range, sign of A); the two log-ratios of a
     # range alternate from one group of six to the next
@@ -292,7 +381,7 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
     delta = lr_tab[2 * (cell // 2) + (pos // 6) % 2]
     with torch.no_grad():
         p64 = {k: torch.from_numpy(w.astype(np.float64)) for k, w in params['actor'].items()}
-        mean = _mlp(p64, 'mean', torch.from_numpy(data['obs'].astype(np.float64)))
+        mean = _mlp(p64, 'mean', torch.from_numpy(data['obs'].astype(np.float64)), acts['actor'])
         dist = torch.distributions.Normal(mean, torch.exp(p64['log_std']))
         logp_new = dist.log_prob(torch.from_numpy(data['act'].astype(np.float64))).sum(-1).numpy()
     data['logp'] = (logp_new - delta).astype(F32)
@@ -321,6 +410,8 @@ def make_case(obs_dim: int, act_dim: int, B: int = 64, M: int = 100, *, loss_kin
                 loss_kind=loss_kind, ext=ext, use_cost=bool(use_cost), update_actor=bool(update_actor),
                 update_critics=bool(update_critics), seeded_moments=bool(seeded_moments), trust=bool(trust), p3o=p3o,
                 norm_clip=norm_clip, w1_scale=float(w1_scale))
+    if (actor_hidden, critic_hidden, actor_act, critic_act) != (None, None, 'tanh', 'tanh'):
+        case.update(arch, z_shift=z_shift)
     if update_actor:
         g0 = float(case_step(dict(case, update_critics=False, ext=None), state, 0)['actor']['gnorm'])
         scale = F32(2.0 ** round(math.log2(1.5 / g0)))
@@ -399,6 +490,50 @@ def check_coverage(case: dict) -> dict:
     if case.get('w1_scale', 1.0) != 1.0:
         info['saturated'] = first_layer_saturation(case)
         assert max(info['saturated'].values()) <= 0.02, info['saturated']
+    info.update(activation_coverage(case))
+    return info
+
+
+def activation_coverage(case: dict) -> dict:
+    """Conditions on the hidden pre-activations of every minibatch of the case at its initial state (where the GPU
+    tests take the gradient), per network the case updates:
+      relu      no pre-activation of any hidden layer sits at the kink: min |z64| >= 64 max |z32 - z64|, both from
+                the twin's own float32 and float64 runs -- float32 and float64 (and the kernels, whose forward error
+                is of the size of the float32 run's) take the same side everywhere;
+      softplus  (a case with z_shift) first-layer pre-activations above 20, torch's linear branch, exist, and at
+                least a quarter lie below -3, where the output h = log1p(exp z) is small and a derivative taken
+                through it as 1 - exp(-h) cancels;
+      sigmoid   (a case with z_shift) at least 5 % of the first-layer units have h > 0.99."""
+    info = {}
+    nets = case_nets(case)
+    kinds = {net: case_act(case, net) for net in nets if len(case_hidden(case, net)) > 0}
+    probe = case.get('z_shift') is not None
+    if not ('relu' in kinds.values() or (probe and {'softplus', 'sigmoid'} & set(kinds.values()))):
+        return info
+    for k in range(len(minibatches(case['M'], case['B']))):
+        r64 = case_step(case, case['state'], k)
+        r32 = case_step(case, case['state'], k, torch.float32) if 'relu' in kinds.values() else None
+        for net, kind in kinds.items():
+            z64 = [z.numpy() for z in r64[net]['pre_acts']]
+            if kind == 'relu':
+                for l, z in enumerate(z64):
+                    lo = float(np.abs(z).min())
+                    d = float(np.abs(r32[net]['pre_acts'][l].numpy().astype(np.float64) - z).max())
+                    assert lo >= 64.0 * d, (net, k, l, lo, d)
+                    info['relu_margin'] = min(info.get('relu_margin', np.inf), lo / max(d, 1e-300))
+            elif probe and kind == 'softplus':
+                c = info.setdefault('softplus', {}).setdefault(net, [0, 0, 0])
+                c[0] += int((z64[0] > 20.0).sum())
+                c[1] += int((z64[0] < -3.0).sum())
+                c[2] += z64[0].size
+            elif probe and kind == 'sigmoid':
+                c = info.setdefault('sigmoid', {}).setdefault(net, [0, 0])
+                c[0] += int((1.0 / (1.0 + np.exp(-z64[0])) > 0.99).sum())
+                c[1] += z64[0].size
+    for net, (above, below, n) in info.get('softplus', {}).items():
+        assert above >= 1 and 4 * below >= n, (net, above, below, n)
+    for net, (sat, n) in info.get('sigmoid', {}).items():
+        assert 20 * sat >= n, (net, sat, n)
     return info
 
 
@@ -567,6 +702,98 @@ def form_table() -> 'OrderedDict[str, dict]':
     return t
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the third table: general networks -- the layer-wise path of csrc/general_mlp.hip + csrc/skinny_mlp.h
+# (tests/test_general_step_gpu.py).  Every shape is the smallest that reaches the mechanism the case is named for;
+# tests/test_step_twin.py asserts from osa_gmlp_plan that it does.
+# ---------------------------------------------------------------------------------------------------------------------
+GENERAL_BASE = dict(obs_dim=20, act_dim=3, B=37, M=70, actor_hidden=[30, 7], critic_hidden=[50, 1, 9])
+GENERAL_SMALL = dict(obs_dim=20, act_dim=3, B=37, M=70, actor_hidden=[24, 12], critic_hidden=[24, 12])
+GENERAL_TILED = dict(obs_dim=20, act_dim=3, actor_hidden=[24, 12], critic_hidden=[12, 24])
+
+
+def general_table() -> 'OrderedDict[str, dict]':
+    """name -> dict(kw = make_case keyword arguments, env = environment of the run, features = what osa_gmlp_plan
+    must report for the case: the vocabulary of tests/test_step_twin.py plan_features)."""
+    t = OrderedDict()
+
+    def add(name, features, env=None, **kw):
+        assert name not in t
+        t[name] = dict(kw=kw, env=dict(env or {}), features=tuple(features))
+
+    base, small = GENERAL_BASE, GENERAL_SMALL
+    fused = ('skinny', 'fusedn', 'top-in-fwd:all', 'loss-fused')
+    # ---- skinny step (B <= 64): rows 1, 3, 37, 64; the ways the top layer fuses
+    add('sk-a2-rows1', fused, **dict(small, obs_dim=1, act_dim=2, B=1, M=6))
+    add('sk-a8-one-hidden-rows64', fused, obs_dim=61, act_dim=8, B=64, M=65, actor_hidden=[64], critic_hidden=[64])
+    add('sk-a9-odd-widths-rows3', ('skinny', 'fusedn', 'top-in-fwd:critics', 'loss-fused'), **dict(base, act_dim=9, B=3, M=9))
+    add('sk-a32-h65', ('skinny', 'fusedn', 'top-in-fwd:critics', 'loss-fused', 'tk2'),
+        **dict(base, act_dim=32, actor_hidden=[65, 65], critic_hidden=[17, 65]))
+    add('sk-a33-plain-loss', ('skinny', 'no-fusedn', 'loss-plain'), **dict(base, act_dim=33, actor_hidden=[20], critic_hidden=[20]))
+    add('sk-a33-normclip-all', ('skinny', 'no-fusedn', 'loss-plain'),
+        **dict(base, act_dim=33, actor_hidden=[20], critic_hidden=[20], norm_clip=('all', 0.5)))
+    add('sk-nohidden-actor', ('skinny', 'no-fusedn', 'loss-fused'), **dict(base, actor_hidden=[], critic_hidden=[20]))
+    add('sk-nohidden-all', ('skinny', 'no-fusedn', 'loss-fused'), **dict(base, actor_hidden=[], critic_hidden=[]))
+    add('sk-seven-layers', fused, **dict(base, actor_hidden=[16, 12, 10, 9, 8, 6, 5], critic_hidden=[16, 12, 10, 9, 8, 6, 5]))
+    add('sk-k1040', fused, **dict(base, obs_dim=376, M=43, actor_hidden=[1040, 20], critic_hidden=[1040, 20], fan_scale=True))
+    add('sk-k4-k20', fused, **dict(base, actor_hidden=[4, 20], critic_hidden=[20, 4]))
+    # (a fused top layer below a layer of more than 1024 columns: more than 64 partial slabs, summed by the loop of
+    # gs_top_kernel and not by its register path)
+    add('sk-top1040', fused, **dict(base, actor_hidden=[20, 1040], critic_hidden=[20, 1040], fan_scale=True))
+    # ---- the loss, clip and mask variants on the base networks ([30, 7] / [50, 1, 9]: no width a multiple of 4)
+    add('sk-base', fused, **base)
+    add('sk-l2-off', fused, **dict(base, use_critic_norm=0))
+    add('sk-l2-0.05', fused, **dict(base, critic_norm_coef=0.05))
+    add('sk-l2-0.05-clipped', fused, **dict(base, critic_norm_coef=0.05, norm_clip=(1, 0.5)))
+    for net in range(3):
+        add(f'sk-normclip-{NETS[net]}', fused, **dict(base, norm_clip=(net, 0.5)))
+    add('sk-normclip-off', fused, **dict(base, use_max_grad_norm=0))
+    add('sk-entropy-0.05', fused, **dict(base, entropy_coef=0.05))
+    add('sk-actor-off', fused, **dict(base, update_actor=False))
+    add('sk-critics-off', fused, **dict(base, update_critics=False))
+    add('sk-nocost', fused, **dict(base, use_cost=False))
+    add('sk-losskind1', fused, **dict(base, loss_kind=1))
+    ext = dict(base, update_critics=False)
+    add('sk-focops-mask', fused, **dict(ext, loss_kind=1, ext=FOCOPS, trust=True))
+    add('sk-p3o-active', fused, **dict(ext, ext=dict(cost_kappa=2.0), p3o='active'))
+    add('sk-p3o-inactive', fused, **dict(ext, ext=dict(cost_kappa=2.0), p3o='inactive'))
+    add('sk-seeded', fused, **dict(base, seeded_moments=True, t0=(3, 5, 7)))
+    # ---- activations: one case each, and actor and critics of different depth and kind
+    add('sk-mixed-relu-softplus', fused, **dict(base, actor_act='relu', critic_act='softplus'))
+    for kind in ACTIVATIONS:
+        shift = {'softplus': (16.0, -5.0), 'sigmoid': (8.0, 1.0)}.get(kind)
+        add(f'sk-act-{kind}', fused, **dict(small, actor_act=kind, critic_act=kind, z_shift=shift))
+    # ---- tiled step (B > 64, or B = 64 with the skinny kernels switched off)
+    tiled = GENERAL_TILED
+    add('tl-skinny-off-B64', ('tiled', 'S1'), env={'OSA_GMLP_SKINNY': '0'}, **dict(tiled, B=64, M=64))
+    add('tl-B65', ('tiled', 'S1', 'row-split-off'), **dict(tiled, B=65, M=65))
+    add('tl-B255', ('tiled', 'S1'), **dict(tiled, B=255, M=255))
+    add('tl-B256', ('tiled', 'S2'), **dict(tiled, B=256, M=256))
+    add('tl-B257', ('tiled', 'S2', 'row-split-off'), **dict(tiled, B=257, M=257))
+    add('tl-B300', ('tiled', 'S2'), **dict(tiled, B=300, M=300))
+    add('tl-B130-tail', ('tiled', 'S1'), **dict(tiled, B=130, M=200, seeded_moments=True, t0=(3, 5, 7)))
+    add('tl-normclip-all', ('tiled',), **dict(tiled, B=130, M=130, norm_clip=('all', 0.5)))
+    add('tl-losskind1-sigmoid', ('tiled',), **dict(tiled, B=130, M=130, loss_kind=1, actor_act='sigmoid', critic_act='softplus'))
+    add('tl-focops-mask-B200', ('tiled',), **dict(tiled, B=200, M=200, update_critics=False, loss_kind=1, ext=FOCOPS, trust=True))
+    add('tl-rowsplit-512', ('tiled', 'rowS4'), **dict(tiled, B=65, M=65, actor_hidden=[512, 16], critic_hidden=[16, 512], fan_scale=True))
+    add('tl-rowsplit-mixed', ('tiled', 'rowS4', 'Si<S'),
+        **dict(tiled, B=65, M=65, actor_hidden=[512, 16], critic_hidden=[130, 16], fan_scale=True))
+    add('tl-rowsplit-1040', ('tiled', 'rowS8'), **dict(tiled, B=65, M=65, actor_hidden=[1040, 8], critic_hidden=[1040, 8], fan_scale=True))
+    add('tl-ragged-64-65-129', ('tiled', 'NT', 'NN', 'TN'),
+        **dict(tiled, obs_dim=63, B=130, M=130, actor_hidden=[64, 65, 129], critic_hidden=[64, 65, 129], fan_scale=True))
+    # ---- the instantiations of gm_gemm_kernel beyond 64 x 64 x 64, by the launcher's arithmetic on workgroup counts
+    # (gm_pick_tile: 128-wide tiles where they still give 128 workgroups, K step 16 from 256 workgroups)
+    h512 = dict(tiled, actor_hidden=[512, 512], critic_hidden=[512, 512], fan_scale=True)
+    add('tl-h512-B384', ('tiled', 'S3', 'k128x128x64TN', 'TM128xTN128', 'BK64'), **dict(h512, B=384, M=384))
+    add('tl-h512-B700', ('tiled', 'S5', 'k128x128x16TN', 'k128x64x64NT', 'k128x64x64NN', 'BK16', 'TM128'), **dict(h512, B=700, M=700))
+    thin = dict(tiled, actor_hidden=[1040, 64], critic_hidden=[1040, 64], fan_scale=True)
+    add('tl-h1040x64-B640', ('tiled', 'k64x128x64TN', 'k128x64x64TN', 'k128x128x64NN', 'k128x128x64NT', 'TN128'),
+        **dict(thin, B=640, M=640))
+    add('tl-h1040x64-B1280', ('tiled', 'k64x128x16TN', 'k128x64x16TN', 'k128x128x16NN', 'k128x128x16NT'),
+        **dict(thin, B=1280, M=1280, target_c_scale=LARGE_TARGET_C))
+    return t
+
+
 def empty_chunks(B: int, n: int) -> int:
     """64-row chunks of a B-row step that a minibatch of n rows leaves without a row (chunk c holds rows 64 c ...)."""
     return (B + 63) // 64 - (n + 63) // 64
@@ -626,7 +853,8 @@ def f32_error(case: dict) -> tuple:
                 if net != 'actor':
                     v64 = r64[net]['value'].numpy() if order is None else r64[net]['value'].numpy()[order]
                     rms = float(np.sqrt(np.mean((r32[net]['value'].numpy().astype(np.float64) - v64) ** 2)))
-                    errs[OUT_BIAS_ROWS] = 2.0 / math.sqrt(n) * rms / abs(float(r64[net]['grads'][OUT_BIAS]))
+                    ob = out_bias(case)  # (OUT_BIAS wherever the critics have two hidden layers)
+                    errs[ob + '/rows'] = 2.0 / math.sqrt(n) * rms / abs(float(r64[net]['grads'][ob]))
                 for dst in (worst,) if order is not None else (worst, single):
                     o = dst.setdefault(net, {})
                     for name, e in errs.items():
@@ -665,3 +893,108 @@ def load_f32_error(path: str) -> tuple:
             worst[name][net] = dict(zip(ks, row[:len(ks)]))
             single[name][net] = dict(zip(ks, row[len(ks):]))
     return worst, single
+
+
+def pack_general_error(table: dict) -> dict:
+    """{case: (worst, single)} -> the layout of tests/golden/general_twin_f32_error.json: per case and network
+    {tensor or scalar: [worst, single]} (the networks of general_table() differ from case to case: no shared keys)."""
+    return {'cases': {name: {net: {k: [float(f'{worst[net][k]:.2e}'), float(f'{single[net][k]:.2e}')] for k in worst[net]}
+                             for net in worst} for name, (worst, single) in table.items()}}
+
+
+def load_general_error(path: str) -> tuple:
+    """-> (worst, single), each {case: {network: {tensor or scalar: error}}}, as load_f32_error."""
+    import json
+
+    blob = json.load(open(path))['cases']
+    return tuple({name: {net: {k: v[i] for k, v in d.items()} for net, d in nets.items()} for name, nets in blob.items()}
+                 for i in (0, 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the launch plan of a case on the layer-wise path: osa_gmlp_plan, host only
+# ---------------------------------------------------------------------------------------------------------------------
+PLAN_HEAD, PLAN_LAUNCH = 59, 15  # OSA_GMLP_PLAN_HEAD, OSA_GMLP_PLAN_LAUNCH (include/omnisafe_amd.h)
+
+
+def gmlp_desc(case: dict):
+    """The osa_gmlp_desc of a case's networks."""
+    from omnisafe_amd.models import ACTIVATIONS as CODES, GmlpDesc
+
+    d = GmlpDesc()
+    d.obs_dim, d.act_dim = case['obs_dim'], case['act_dim']
+    for i, net in enumerate(NETS):
+        widths = case_hidden(case, net) + [case['act_dim'] if net == 'actor' else 1]
+        d.n_layers[i] = len(widths)
+        for l, w in enumerate(widths):
+            d.width[i][l] = w
+        d.activation[i] = CODES[case_act(case, net)]
+    return d
+
+
+def gmlp_plan(case: dict, rows: int | None = None, mode: int = 0) -> dict:
+    """What osa_gmlp_minibatch_ext will launch for a minibatch of `rows` rows (the case's B) of the case, in THIS
+    process and its environment."""
+    import ctypes as C
+
+    from omnisafe_amd import _lib
+    from omnisafe_amd.models import HParams
+
+    lib = _lib.load()
+    hp = HParams()
+    hp.use_cost = int(case['use_cost'])
+    hp.use_critic_norm = int(case['hp']['use_critic_norm'])
+    mask = sum(1 << NETS.index(net) for net in case_nets(case))
+    out = (C.c_int * 4096)()
+    desc = gmlp_desc(case)
+    _lib.check(lib.osa_gmlp_plan(C.byref(desc), int(case['B'] if rows is None else rows), int(case['loss_kind']), mode,
+                                 mask, C.byref(hp), out, len(out)), 'osa_gmlp_plan')
+    r = list(out[:out[0]])
+    grid = lambda o: [r[o + 8 * i:o + 8 * i + 8] for i in range(3)]  # noqa: E731
+    plan = dict(skinny=bool(r[1]), fusedn=bool(r[2]), top_in_fwd=[bool(x) for x in r[3:6]],
+                loss_fused=[bool(x) for x in r[6:9]], sk_maxT1=r[9], sk_tk=grid(10), S=grid(34), mask=mask, launches=[])
+    assert len(r) == PLAN_HEAD + PLAN_LAUNCH * r[PLAN_HEAD - 1]
+    for i in range(r[PLAN_HEAD - 1]):
+        q = r[PLAN_HEAD + PLAN_LAUNCH * i:PLAN_HEAD + PLAN_LAUNCH * (i + 1)]
+        plan['launches'].append(dict(TM=q[0], TN=q[1], BK=q[2], AT=q[3], BT=q[4], splits=q[5], rowS=q[6], nprob=q[7],
+                                     Si=q[8:8 + q[7]], psplits=q[11:11 + q[7]], xcd=q[14]))
+    return plan
+
+
+def plan_features(plan: dict) -> set:
+    """The vocabulary of general_table()'s `features`."""
+    f = {'skinny' if plan['skinny'] else 'tiled'}
+    active = [i for i in range(3) if (plan['mask'] >> i) & 1]
+    if plan['skinny']:
+        f.add('fusedn' if plan['fusedn'] else 'no-fusedn')
+        fwd = [plan['top_in_fwd'][i] for i in active]
+        if all(fwd):
+            f.add('top-in-fwd:all')
+        elif 0 in active and not plan['top_in_fwd'][0] and any(fwd):
+            f.add('top-in-fwd:critics')
+        f.add('loss-fused' if all(plan['loss_fused'][i] for i in active) else 'loss-plain')
+        if any(tk == 2 for i in active for tk in plan['sk_tk'][i]):
+            f.add('tk2')
+        return f
+    f.add(f"S{max(s for i in active for s in plan['S'][i])}")
+    if not any(q['rowS'] for q in plan['launches']):
+        f.add('row-split-off')
+    for q in plan['launches']:
+        form = {(0, 0): 'NT', (0, 1): 'NN', (1, 1): 'TN'}[(q['AT'], q['BT'])]
+        f.add(form)
+        f.add(f"k{q['TM']}x{q['TN']}x{q['BK']}{form}")
+        f.add(f"BK{q['BK']}")
+        if q['rowS']:
+            f.add(f"rowS{q['rowS']}")
+            if min(q['Si']) < q['rowS']:
+                f.add('Si<S')
+        if q['TM'] == 128:
+            f.add('TM128xTN128' if q['TN'] == 128 else 'TM128')
+        elif q['TN'] == 128:
+            f.add('TN128')
+    return f
+
+
+def plan_kernels(plan: dict) -> set:
+    """The instantiations (TM, TN, BK, AT, BT) of gm_gemm_kernel a step of this plan launches."""
+    return {(q['TM'], q['TN'], q['BK'], q['AT'], q['BT']) for q in plan['launches']}

@@ -91,7 +91,8 @@ def unit(e32, net, what):
     """max(e32, 2^-22) of a tensor or scalar; for a critic's one-element output bias e32 is the larger of the
     tensor's own figure and the typical size of the sum of its rows' forward errors (step_twin.OUT_BIAS_ROWS)."""
     u = max(e32[net][what], T.FLOOR)
-    return max(u, e32[net][T.OUT_BIAS_ROWS]) if net != 'actor' and what == T.OUT_BIAS else u
+    rows = e32[net].get(what + '/rows') if net != 'actor' else None  # (T.OUT_BIAS_ROWS where the critics are [64, 64])
+    return u if rows is None else max(u, rows)
 
 
 def check_bias_columns(h, kind, stats, t_after, failures):
@@ -129,10 +130,12 @@ def reference(name):
     return ref
 
 
-def model_cfgs():
+def model_cfgs(case=None):
+    """[64, 64] tanh networks, or those a case of step_twin.general_table() names."""
     ns = types.SimpleNamespace
-    return ns(actor=ns(hidden_sizes=[64, 64], activation='tanh', lr=3e-4),
-              critic=ns(hidden_sizes=[64, 64], activation='tanh', lr=3e-4),
+    case = case or {}
+    return ns(actor=ns(hidden_sizes=T.case_hidden(case, 'actor'), activation=T.case_act(case, 'actor'), lr=3e-4),
+              critic=ns(hidden_sizes=T.case_hidden(case, 'reward_critic'), activation=T.case_act(case, 'reward_critic'), lr=3e-4),
               weight_initialization_mode='kaiming_uniform', actor_type='gaussian_learning', linear_lr_decay=True)
 
 
@@ -157,7 +160,7 @@ class Harness:
         self.case, self.path = case, path
         od, ad, M = case['obs_dim'], case['act_dim'], case['M']
         persistent, self.last_path, self.bias_columns, self.one_launch = self.form()
-        self.ac = ac = ConstraintActorCritic(Box(-np.inf, np.inf, (od,)), Box(-1, 1, (ad,)), model_cfgs(), 4, device=DEV)
+        self.ac = ac = ConstraintActorCritic(Box(-np.inf, np.inf, (od,)), Box(-1, 1, (ad,)), model_cfgs(case), 4, device=DEV)
         self.views = [getattr(ac, net) for net in T.NETS]
         self.index = [v._flat_index.cpu().numpy() for v in self.views]
         d = case['data']
@@ -203,7 +206,7 @@ class Harness:
         for i, net in enumerate(T.NETS):
             for which, blk in blocks.items():
                 flat, o, d = blk[i][self.index[i]], 0, {}
-                for k, s in T.tensor_shapes(net, self.case['obs_dim'], self.case['act_dim']).items():
+                for k, s in T.case_shapes(self.case, net).items():
                     n = int(np.prod(s))
                     d[k] = flat[o:o + n].reshape(s).copy()
                     o += n

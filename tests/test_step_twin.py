@@ -13,7 +13,12 @@ tests/test_step_oracle_gpu.py compare the 64-row step kernels with.
   * the cases of case_table() keep the entries of the measuring stick they had before form_table() joined the file;
   * the ragged tail of a pass is the step of its rows as a minibatch of their own;
   * the measuring stick tests/golden/step_twin_f32_error.json (float32 run against float64 run of the same code, per
-    case, network and tensor) reproduces within a factor 2.
+    case, network and tensor) reproduces within a factor 2;
+  * general networks (step_twin.general_table(), the table of tests/test_general_step_gpu.py): the default cases did
+    not move by a bit, the activations are torch.nn's, every case meets its coverage conditions (ReLU kink distance,
+    Softplus and Sigmoid saturation counts included), osa_gmlp_plan shows for every case the launch features it is
+    named for and for the table as a whole every mechanism and the listed instantiations of gm_gemm_kernel, and
+    tests/golden/general_twin_f32_error.json reproduces.
 
 Tolerances against the float32 reference: a logged scalar is a mean over <= 64 float32 terms after ~200-term dot
 products: relative error a few 1e-7 of the terms' scale (not of a mean that may cancel), hence rtol 2e-6 with an atol of
@@ -314,6 +319,171 @@ def test_f32_measuring_stick_reproduces(cases):
             assert sorted(g) == sorted(w[name]), name
             for net in g:
                 assert sorted(g[net]) == sorted(w[name][net]), (name, net)
+                for k, e in g[net].items():
+                    a, b = max(e, T.FLOOR), max(w[name][net][k], T.FLOOR)
+                    assert a <= 2 * b and b <= 2 * a, (which, name, net, k, e, w[name][net][k])
+
+
+# ------------------------------------------------------------------------------- general networks (general_table())
+GENERAL = T.general_table()
+GENERAL_ERR_FILE = os.path.join(HERE, 'golden', 'general_twin_f32_error.json')
+# inputs and float64 gradients of four default cases as the twin produced them before it learned general networks
+DEFAULT_CASES_SHA256 = '4dcc1cbfec348bcfd0853281ba14ad13c3035506defd219228f77664c898c974'
+# The instantiations (TM, TN, BK, AT, BT) of gm_gemm_kernel that general_table() launches: 15 of the 24.  The other nine:
+#   (64, 64, 16, *)      three: unreachable by shape.  K step 16 needs 256 workgroups of 64 x 64 tiles while the 128-wide
+#                        tiles were refused for giving fewer than 128; a 64 x 64 grid has at most twice the workgroups of
+#                        the 128 x 64 grid that was refused (OSA_GMLP_DEEP=0 forces it: a once-per-process switch)
+#   (64, 128, *, NT/NN)  four: row tiles of 64 mean a minibatch of at most 64 rows on the tiled step, and then 128
+#                        workgroups need a layer of 5 400 outputs (inputs, for NN): past the cost limits of the table
+#   (128, 64, 16, NT), (128, 64, 16 | 64, NN)   column tiles of 64 with row tiles of 128 on the minibatch's rows:
+#                        (128, 64, 64, NN) is in the table (a 64-wide layer under a 512-wide one at 700 rows); K step 16
+#                        needs 256 workgroups = 10 900 rows
+COVERED_KERNELS = {(64, 64, 64, 0, 0), (64, 64, 64, 0, 1), (64, 64, 64, 1, 1), (64, 128, 16, 1, 1), (64, 128, 64, 1, 1),
+                   (128, 64, 16, 1, 1), (128, 64, 64, 0, 0), (128, 64, 64, 0, 1), (128, 64, 64, 1, 1), (128, 128, 16, 0, 0),
+                   (128, 128, 16, 0, 1), (128, 128, 16, 1, 1), (128, 128, 64, 0, 0), (128, 128, 64, 0, 1), (128, 128, 64, 1, 1)}
+# what the table as a whole must reach, from osa_gmlp_plan
+REQUIRED_FEATURES = {'skinny', 'tiled', 'fusedn', 'no-fusedn', 'top-in-fwd:all', 'top-in-fwd:critics', 'loss-fused',
+                     'loss-plain', 'tk2', 'S1', 'S2', 'row-split-off', 'rowS4', 'rowS8', 'Si<S', 'TM128', 'TN128',
+                     'TM128xTN128', 'BK16', 'BK64', 'NT', 'NN', 'TN'}
+
+
+@pytest.fixture(scope='module')
+def general_cases():
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = T.make_case(**GENERAL[name]['kw'])
+        return cache[name]
+
+    return get
+
+
+def test_default_cases_did_not_move():
+    """actor_hidden / critic_hidden / the activations at their defaults: the cases of case_table() and form_table()
+    number for number -- parameters, moments, data, permutation, hyper-parameters, float64 gradients."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for kw in (dict(obs_dim=60, act_dim=2),
+               dict(obs_dim=65, act_dim=17, B=48, M=100, norm_clip=(1, 0.5), seeded_moments=True, t0=(3, 5, 7)),
+               dict(obs_dim=28, act_dim=8, update_critics=False, loss_kind=1, ext=T.FOCOPS, trust=True),
+               dict(obs_dim=376, act_dim=17, w1_scale=(64 / 376) ** 0.5)):
+        c = T.make_case(**kw)
+        for net in T.NETS:
+            for w in ('params', 'm', 'v'):
+                for k, a in c['state'][w][net].items():
+                    h.update(k.encode())
+                    h.update(np.ascontiguousarray(a).tobytes())
+        for k in sorted(c['data']):
+            h.update(k.encode())
+            h.update(np.ascontiguousarray(c['data'][k]).tobytes())
+        h.update(c['perm'].tobytes())
+        h.update(repr(sorted(c['hp'].items())).encode())
+        r = T.case_step(c, c['state'], 0)
+        for net in r:
+            for g in r[net]['grads'].values():
+                h.update(g.numpy().tobytes())
+    assert h.hexdigest() == DEFAULT_CASES_SHA256
+
+
+def test_activations_are_the_reference_modules():
+    """step_twin._ACT against torch.nn's modules of the same names (utils/model.py get_activation), float64, on a grid
+    that crosses Softplus's threshold of 20 and ReLU's kink."""
+    z = torch.linspace(-30.0, 30.0, 2401, dtype=torch.float64)
+    mods = dict(tanh=torch.nn.Tanh(), relu=torch.nn.ReLU(), sigmoid=torch.nn.Sigmoid(), softplus=torch.nn.Softplus(),
+                identity=torch.nn.Identity())
+    assert tuple(mods) == T.ACTIVATIONS
+    for kind, m in mods.items():
+        assert torch.equal(T._ACT[kind](z), m(z)), kind
+
+
+@pytest.mark.parametrize('name', list(GENERAL))
+def test_general_case_reaches_its_branches(general_cases, name):
+    """check_coverage: the clip cells, trust mask, P3O sign and norm-clip conditions of the 64-row table, and the
+    conditions on the hidden pre-activations (step_twin.activation_coverage: no ReLU unit at the kink, Softplus above
+    20 and below -3, saturated Sigmoid units) -- conditions on the inputs, not tolerances."""
+    case = general_cases(name)
+    info = T.check_coverage(case)
+    print(name, {k: v for k, v in info.items() if k != 'cells'})
+    kinds = {T.case_act(case, net) for net in T.case_nets(case) if T.case_hidden(case, net)}
+    assert ('relu_margin' in info) == ('relu' in kinds)
+    if case.get('z_shift') is not None:
+        assert ('softplus' in info) == ('softplus' in kinds) and ('sigmoid' in info) == ('sigmoid' in kinds)
+        assert 'softplus' in info or 'sigmoid' in info
+
+
+@pytest.mark.parametrize('name', list(GENERAL))
+def test_general_case_launches_what_it_is_named_for(general_cases, name, monkeypatch):
+    """osa_gmlp_plan -- the launchers' own decision functions, walked without a launch -- names every feature the case
+    is in the table for.  The once-per-process switches are left alone: every variant is reached by shape."""
+    for key, value in GENERAL[name]['env'].items():
+        monkeypatch.setenv(key, value)
+    case = general_cases(name)
+    plan = T.gmlp_plan(case)
+    got = T.plan_features(plan)
+    print(name, sorted(got))
+    assert got >= set(GENERAL[name]['features']), (name, sorted(set(GENERAL[name]['features']) - got))
+    assert plan['skinny'] == (case['B'] <= 64 and not GENERAL[name]['env'])
+    # modes 1 and 2 never take the Gram-formula norm; every minibatch of the pass stays on the case's step
+    for mode in (1, 2):
+        assert not T.gmlp_plan(case, mode=mode)['fusedn']
+    for _, n in T.minibatches(case['M'], case['B']):
+        assert T.gmlp_plan(case, rows=n)['skinny'] == (n <= 64 and not GENERAL[name]['env'])
+
+
+def test_general_table_reaches_every_mechanism(general_cases):
+    """Over the whole table: every feature of the launch plan, the instantiations of gm_gemm_kernel listed above, and
+    the shapes the plan does not show (rows, depths, widths, observation rows, activations)."""
+    feats, kernels = set(), set()
+    for name, e in GENERAL.items():
+        if e['env']:
+            continue
+        plan = T.gmlp_plan(general_cases(name))
+        feats |= T.plan_features(plan)
+        kernels |= T.plan_kernels(plan)
+    assert feats >= REQUIRED_FEATURES, sorted(REQUIRED_FEATURES - feats)
+    assert kernels == COVERED_KERNELS, (sorted(kernels - COVERED_KERNELS), sorted(COVERED_KERNELS - kernels))
+    cases = [general_cases(name) for name in GENERAL]
+    skinny = [c for c in cases if c['B'] <= 64]
+    rows = {n for c in skinny for _, n in T.minibatches(c['M'], c['B'])}
+    assert rows >= {1, 3, 37, 64}, sorted(rows)
+    assert {c['B'] for c in cases} >= {65, 255, 256, 257, 300}
+    assert {c['act_dim'] for c in skinny} >= {2, 8, 9, 32, 33}
+    assert {c['obs_dim'] for c in skinny} >= {1, 61, 376}
+    depths = {len(T.case_hidden(c, net)) for c in skinny for net in T.NETS}
+    assert depths >= {0, 1, 2, 3, 7}, depths
+    assert any(T.case_hidden(c, 'actor') == [] and T.case_hidden(c, 'reward_critic') != [] for c in skinny)
+    widths = {w for c in skinny for net in T.NETS for w in T.case_hidden(c, net)}
+    assert widths >= {1, 4, 7, 9, 17, 20, 30, 50, 65, 1040}, sorted(widths)
+    for net in ('actor', 'reward_critic'):
+        assert {T.case_act(c, net) for c in skinny} == set(T.ACTIVATIONS)
+    assert any(T.case_act(c, 'actor') != T.case_act(c, 'reward_critic')
+               and T.case_hidden(c, 'actor') != T.case_hidden(c, 'reward_critic') for c in skinny)
+    # 1040 only as one thin layer: no weight matrix beyond 1040 x 512
+    for c in cases:
+        for net in T.NETS:
+            sizes = [c['obs_dim']] + T.case_hidden(c, net)
+            assert all(a * b <= 1040 * 512 for a, b in zip(sizes, sizes[1:])), (sizes,)
+    # the uneven split: 300 rows in two slices of whole K steps
+    plan = T.gmlp_plan(general_cases('tl-B300'))
+    q = [x for x in plan['launches'] if x['AT']][0]
+    kper = -(-(-(-300 // q['splits'])) // q['BK']) * q['BK']
+    assert q['splits'] == 2 and 0 < 300 - kper < kper
+
+
+def test_general_measuring_stick_reproduces(general_cases):
+    """tests/golden/general_twin_f32_error.json (tools/step_twin_report.py --general-golden) against a fresh
+    measurement, as test_f32_measuring_stick_reproduces holds the 64-row file: within a factor 2 on max(e32, 2^-22)."""
+    want = T.load_general_error(GENERAL_ERR_FILE)
+    assert sorted(want[0]) == sorted(GENERAL)
+    for name in GENERAL:
+        got = T.f32_error(general_cases(name))
+        for which, g, w in zip(('worst', 'single'), got, want):
+            assert sorted(g) == sorted(w[name]), name
+            for net in g:
+                assert sorted(g[net]) == sorted(w[name][net]), (name, net)
+                assert T.out_bias(general_cases(name)) + '/rows' in g[net] or net == 'actor'
                 for k, e in g[net].items():
                     a, b = max(e, T.FLOOR), max(w[name][net][k], T.FLOOR)
                     assert a <= 2 * b and b <= 2 * a, (which, name, net, k, e, w[name][net][k])

@@ -6,6 +6,13 @@ profiles/step_forms_error.md from those of tests/test_step_forms_gpu.py (one fil
     OSA_STEP_TWIN_FIGURES=forms.json python -m pytest -m gpu tests/test_step_forms_gpu.py
     python tools/step_twin_report.py forms.json > profiles/step_forms_error.md
 
+profiles/general_twin_error.md likewise from tests/test_general_step_gpu.py (paths `general / apply`), and the
+measuring stick of that file, on the CPU (the float32 twin against the float64 twin for step_twin.general_table()):
+
+    python tools/step_twin_report.py --general-golden      # writes tests/golden/general_twin_f32_error.json
+    OSA_STEP_TWIN_FIGURES=general.json python -m pytest -m gpu tests/test_general_step_gpu.py
+    python tools/step_twin_report.py general.json > profiles/general_twin_error.md
+
 The columns of the tables are the paths found in the figures, in their order of appearance (`per-step / persistent`
 for the 64-row table; per-step, chunked, wide, split, split-spread, balanced, strided for the forms, where a case runs
 on the forms of its family only and the other cells stay `-`).
@@ -17,7 +24,28 @@ float32 figure (rows as drawn) where `measured` is the ratio against the worst o
 """
 import collections
 import json
+import os
 import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def general_golden() -> None:
+    """tests/golden/general_twin_f32_error.json: step_twin.f32_error of every case of general_table(), one thread."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+    import step_twin as T
+    import torch
+
+    torch.set_num_threads(1)
+    table = {}
+    for name, e in T.general_table().items():
+        table[name] = T.f32_error(T.make_case(**e['kw']))
+        print(name, file=sys.stderr)
+    blob = T.pack_general_error(table)
+    dst = os.path.join(ROOT, 'tests', 'golden', 'general_twin_f32_error.json')
+    with open(dst, 'w') as fh:
+        fh.write('{"cases": {\n' + ',\n'.join(f'{json.dumps(k)}: {json.dumps(v)}' for k, v in blob['cases'].items()) + '}}\n')
+    print(dst, os.path.getsize(dst), 'bytes', file=sys.stderr)
 
 
 def main(path: str) -> None:
@@ -27,6 +55,7 @@ def main(path: str) -> None:
         if f[1] not in paths:
             paths.append(f[1])
     narrow = paths == ['per-step', 'persistent']
+    general = 'general' in paths
     per_path = collections.defaultdict(lambda: (0.0, None))  # (class, path) -> worst
     by = collections.defaultdict(float)   # (class, case, net, what, path) -> worst over the steps
     worst = collections.defaultdict(lambda: (0.0, None))
@@ -48,13 +77,16 @@ def main(path: str) -> None:
     w = out.append
     cols_txt = ' / '.join(paths)
     w('# The 64-row optimiser step against its float64 twin: measured error ratios (MI355X)\n' if narrow else
+      '# The optimiser step of general networks against the float64 twin: measured error ratios (MI355X)\n' if general else
       '# The chunked, wide, split and large-batch steps against the float64 twin: measured error ratios (MI355X)\n')
     w('Written by `tools/step_twin_report.py` from one run of '
-      + ('`tests/test_step_oracle_gpu.py` ' if narrow else '`tests/test_step_forms_gpu.py` ') +
+      + ('`tests/test_step_oracle_gpu.py` ' if narrow else '`tests/test_general_step_gpu.py` ' if general
+         else '`tests/test_step_forms_gpu.py` ') +
       f'({len(fig)} figures, {len({f[0] for f in fig})} cases, '
       + ('both paths' if narrow else f'{len({(f[0], f[1]) for f in fig})} (case, form) pairs') + ').  A gradient or scalar entry is '
       '`error / max(e32, 2^-22)`: the relative L2 error of the kernel against `tests/step_twin.py` in float64, in units of '
-      'what the float32 run of the same twin loses (`tests/golden/step_twin_f32_error.json`), worst over the '
+      'what the float32 run of the same twin loses (`tests/golden/'
+      + ('general_twin' if general else 'step_twin') + '_f32_error.json`), worst over the '
       f'minibatches of the case.  Columns `{cols_txt}`' + ('' if narrow else ' (`-`: the case does not run on that form)') + '.\n')
     w('## Summary\n')
     w('| quantity | worst measured | where | bound in the test |')
@@ -68,6 +100,8 @@ def main(path: str) -> None:
             w(f'| {names[cls]} | {m:.2f} | {case}, {p}, {kind.split("/")[0]}, {net}, {what} | {bound[cls]:g} |')
     w('')
     w('K = the smallest power of two that is at least twice the worst measured ratio.\n' if narrow else
+      'The bounds are those of the 64-row table (`tests/test_step_oracle_gpu.py`; a clipped gradient of mode 1 adds the '
+      'clip factor\'s bound to its tensor\'s and is listed rescaled to K_GRAD); nothing was fitted to this path.\n' if general else
       'The bounds are those of the 64-row table (`tests/test_step_oracle_gpu.py`); nothing was fitted to these forms.  '
       + ('Every quantity stayed inside its bound in the units of the float32 twin (the sums over up to 6000 rows and '
          'the slab sums of the large-batch forms included): no unit was re-derived for these forms.\n'
@@ -134,4 +168,7 @@ def main(path: str) -> None:
 
 
 if __name__ == '__main__':
-    main(sys.argv[1])
+    if sys.argv[1] == '--general-golden':
+        general_golden()
+    else:
+        main(sys.argv[1])
