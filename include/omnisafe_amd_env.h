@@ -25,6 +25,8 @@
  *                                       float& reward, float& cost);  // any ACT: the env's action row, act[0 .. ACT)
  *     static __device__ float obs_col(const Regs&, const float* row, int level, int col);   // 0 for col >= OBS
  *     static __device__ float state_col(const Regs&, const float* row, int col);            // col < TRACE
+ *     static __device__ bool terminal(const Regs&, const float* row, const OsaEnvAt&);      // optional: true ends
+ *                                                                     // the episode (see TERMINATION below)
  *   };
  *
  * `row` is never a pointer the description may read (nullptr in the per-step kernel): it exists for the built-in
@@ -33,12 +35,23 @@
  * osa_philox(seed ^ MY_KEY, pos, ((unsigned long long)n << 20) + block, w) and osa_u01(w[i]) so that the per-step
  * launches (pos = 0 for the reset, then 1, 2, ...) and the evaluation kernel (episode k = env index k) play the same
  * episodes.  fresh() of a truncating step and the transition of the same step see the same pos.  Every lane of an
- * env runs load / transition / fresh with the same inputs, so they must be deterministic functions of their
- * arguments: no atomics, no cross-lane operations, no memory but the arguments.  All envs truncate together every
- * `horizon` steps; there is no termination.
+ * env runs load / transition / terminal / fresh with the same inputs, so they must be deterministic functions of their
+ * arguments: no atomics, no cross-lane operations, no memory but the arguments.
+ *
+ * TERMINATION.  Every env counts the steps of its episode (steps[n]) and truncates when the count reaches `horizon`.
+ * A description without terminal() never ends an episode otherwise, so its envs truncate together every `horizon`
+ * steps after a common reset.  One with terminal() is asked once per step, after transition(), on the post-transition
+ * state and with the OsaEnvAt of that transition; true ends the episode of that env alone:
+ *   - the step reports terminated = 1, truncated = 0 and the reward and cost of that transition; termination wins
+ *     over a time limit reached on the same step;
+ *   - the env is reset by fresh() at the same stream position, exactly as on a truncating step;
+ *   - final_obs is NOT written for a terminating env (only truncated paths are bootstrapped from it);
+ *   - a step truncates when steps[n] + 1 >= horizon and it is not terminal; steps[n] returns to 0 on either end.
+ * The evaluation kernel ends episode k on the same answer, with ep_len the steps played.
  *
  * A static_assert with a message that names the member rejects LDS_ROW == true, STATE outside 1 .. 64, ACT outside
- * 1 .. 32, TRACE > STATE and a missing member.
+ * 1 .. 32, TRACE > STATE, a missing member, and a member named terminal that cannot be called as stated above (it
+ * would silently be an env that never ends).
  */
 #ifndef OMNISAFE_AMD_ENV_H
 #define OMNISAFE_AMD_ENV_H
@@ -49,8 +62,8 @@
 extern "C" {
 #endif
 
-/* out[0 .. 8) = STATE, OBS, DYN, ACT, TRACE, LEVELS (the highest level), LANES, 0.  The Python side reads every
- * dimension from here. */
+/* out[0 .. 8) = STATE, OBS, DYN, ACT, TRACE, LEVELS (the highest level), LANES, and 1 where the description has
+ * terminal() (else 0).  The Python side reads every dimension from here. */
 int osa_custom_env_info(int out[8]);
 
 /* One reset (reset_only != 0) or one step of N envs: the argument list and the semantics of osa_nav_env_step

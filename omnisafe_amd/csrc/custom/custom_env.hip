@@ -78,15 +78,31 @@ struct OsaHasTransition2<
                                           std::declval<const OsaEnvAt&>(), 0.f, 0.f, std::declval<float&>(),
                                           std::declval<float&>()))>> : std::true_type {};
 
+// terminal() is optional (OsaHasTerminal, env_device.h: whether it can be called), so a member of that NAME which cannot
+// be called that way must not pass for "no termination".  The name alone: a lookup of `terminal` in a class derived
+// from E and from a class that has one is ambiguous exactly when E has a member of that name, whatever its kind.
+struct OsaTerminalName {
+  int terminal;
+};
+template <class E>
+struct OsaTerminalProbe : E, OsaTerminalName {};
+template <class E, class = void>
+struct OsaNamesTerminal : std::true_type {};
+template <class E>
+struct OsaNamesTerminal<E, std::void_t<decltype(&OsaTerminalProbe<E>::terminal)>> : std::false_type {};
+
 template <class E, bool = OsaHas_Regs<E>::value>
 struct OsaCustomFunctions {
-  static constexpr bool load = true, store = true, fresh = true, obs_col = true, state_col = true, transition = true;
+  static constexpr bool load = true, store = true, fresh = true, obs_col = true, state_col = true, transition = true,
+                        terminal = true, terminates = false;
 };
 template <class E>
 struct OsaCustomFunctions<E, true> {
   static constexpr bool load = OsaHasLoad<E>::value, store = OsaHasStore<E>::value, fresh = OsaHasFresh<E>::value,
                         obs_col = OsaHasObsCol<E>::value, state_col = OsaHasStateCol<E>::value,
-                        transition = OsaTakesActionRow<E>::value || OsaHasTransition2<E>::value;
+                        transition = OsaTakesActionRow<E>::value || OsaHasTransition2<E>::value,
+                        terminates = OsaHasTerminal<E>::value,
+                        terminal = terminates || !OsaNamesTerminal<E>::value;
 };
 static_assert(OsaCustomFunctions<OsaCustomEnv>::load, "custom env: the description has no load(Regs&, const float* srow)");
 static_assert(OsaCustomFunctions<OsaCustomEnv>::store, "custom env: the description has no store(const Regs&, float* srow)");
@@ -99,6 +115,9 @@ static_assert(OsaCustomFunctions<OsaCustomEnv>::state_col,
 static_assert(OsaCustomFunctions<OsaCustomEnv>::transition,
               "custom env: the description has no transition(Regs&, const float* row, const OsaEnvAt&, float a0, float "
               "a1, float& r, float& c) and no transition(..., const float* act, float& r, float& c)");
+static_assert(OsaCustomFunctions<OsaCustomEnv>::terminal,
+              "custom env: the description has a member terminal that cannot be called as bool terminal(const Regs&, "
+              "const float* row, const OsaEnvAt&); it would be an env that never ends");
 
 // The constants' ranges, each asked for only where the constant exists.
 template <class E, bool = OsaHas_STATE<E>::value && OsaHas_OBS<E>::value && OsaHas_DYN<E>::value &&
@@ -133,7 +152,7 @@ template <class E, bool = OsaCustomRanges<E>::complete && OsaCustomRanges<E>::re
                           OsaCustomRanges<E>::obs && OsaCustomRanges<E>::act && OsaCustomRanges<E>::trace &&
                           OsaCustomFunctions<E>::load && OsaCustomFunctions<E>::store && OsaCustomFunctions<E>::fresh &&
                           OsaCustomFunctions<E>::obs_col && OsaCustomFunctions<E>::state_col &&
-                          OsaCustomFunctions<E>::transition>
+                          OsaCustomFunctions<E>::transition && OsaCustomFunctions<E>::terminal>
 struct OsaCustomLib {
   static void info(int*) {}
   static int step(const OsaStepArgs&, void*) { return OSA_EUNSUPPORTED; }
@@ -145,7 +164,8 @@ struct OsaCustomLib {
 template <class E>
 struct OsaCustomLib<E, true> {
   static void info(int* out) {
-    const int v[8] = {E::STATE, E::OBS, E::DYN, E::ACT, E::TRACE, OSA_CUSTOM_LEVELS, OSA_CUSTOM_LANES, 0};
+    const int v[8] = {E::STATE,          E::OBS,           E::DYN, E::ACT, E::TRACE,
+                      OSA_CUSTOM_LEVELS, OSA_CUSTOM_LANES, OsaCustomFunctions<E>::terminates ? 1 : 0};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
   }
   static int step(const OsaStepArgs& a, void* stream) {

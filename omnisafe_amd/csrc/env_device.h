@@ -649,3 +649,23 @@ __device__ __forceinline__ void osa_env_transition(typename E::Regs& s, const fl
   else
     E::transition(s, row, at, act[0], 0.f, r, c);
 }
+
+// Whether the transition just made ends the episode of its own accord.  A description may state
+//   terminal(const Regs&, const float* row, const OsaEnvAt&) -> bool
+// on the post-transition state with the OsaEnvAt of that transition; one without the member (every built-in family)
+// never terminates, and the answer is a compile-time false that leaves its kernels as they were.
+template <class E, class = void>
+struct OsaHasTerminal : std::false_type {};
+template <class E>
+struct OsaHasTerminal<
+    E, std::void_t<decltype(static_cast<bool>(E::terminal(std::declval<const typename E::Regs&>(),
+                                                          (const float*)nullptr, std::declval<const OsaEnvAt&>())))>>
+    : std::true_type {};
+template <class E>
+__device__ __forceinline__ bool osa_env_terminal(const typename E::Regs& s, const float* __restrict__ row,
+                                                 const OsaEnvAt& at) {
+  if constexpr (OsaHasTerminal<E>::value)
+    return E::terminal(s, row, at);
+  else
+    return false;
+}

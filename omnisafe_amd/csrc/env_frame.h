@@ -36,15 +36,18 @@ __device__ __forceinline__ uint8_t osa_step_trunc(const OsaStepArgs& a, int n, i
   count = a.steps[n] + 1;
   return (count >= a.horizon) ? 1 : 0;
 }
-// What the first lane of env n writes at the end, besides the state (count, trunc: 0 after a reset alone).
-__device__ __forceinline__ void osa_step_end(const OsaStepArgs& a, int n, float r, float c, uint8_t trunc, int count) {
+// What the first lane of env n writes at the end, besides the state (count, trunc: 0 after a reset alone).  term: the
+// description ended the episode itself (osa_env_terminal; never together with trunc); the built-in families have no
+// such end and leave it at 0.
+__device__ __forceinline__ void osa_step_end(const OsaStepArgs& a, int n, float r, float c, uint8_t trunc, int count,
+                                             uint8_t term = 0) {
   if (!a.reset_only) {
     a.reward[n] = r;
     a.cost[n] = c;
-    a.terminated[n] = 0;
+    a.terminated[n] = term;
     a.truncated[n] = trunc;
   }
-  a.steps[n] = trunc ? 0 : count;
+  a.steps[n] = (trunc || term) ? 0 : count;
 }
 
 // The argument checks and the launch of every env entry point: `envs` envs per 64-lane workgroup, at least min_obs
@@ -71,6 +74,12 @@ static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bo
 // strided column loop writes the observation row: lane l the columns l, l + LANES, ..., zeros past E::OBS in a wider
 // row; the same loop writes final_obs on a truncating step.  Lane 0 of an env writes the state, reward, cost, flags and
 // the step counter.  No LDS, no barrier, no cross-lane operation: the lanes of a missing last env leave at once.
+// A description with a terminal() member (osa_env_terminal, env_device.h) ends episodes per env: asked after the
+// transition, true gives terminated = 1, truncated = 0, no final_obs row and a reset by fresh() at the same position;
+// the time limit is per env as well (steps[n] + 1 >= horizon and not terminal), and steps[n] returns to 0 on either
+// end.  The envs that share a wave (4 / 2 / 1 per workgroup at 16 / 32 / 64 lanes) may then diverge at fresh() and at
+// the final_obs loop; that is correct as written because no lane waits for another -- the wave runs both sides under
+// the exec mask and every lane of an env takes the same side.
 // The description gets no row pointer (`row` == nullptr: its state is what load() put into Regs) and the unclamped
 // action row of the env in global memory.
 // LANES: E::LANES where the description declares it (16, 32 or 64), else 32 -- the value measured for the Circle
@@ -106,22 +115,24 @@ __global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaStepArgs a) {
   float* __restrict__ srow = a.state + (long)n * E::STATE;
   typename E::Regs s;
   E::load(s, srow);
-  uint8_t trunc = 0;
+  uint8_t trunc = 0, term = 0;
   int count = 0;
   float r = 0.f, c = 0.f;
   if (!a.reset_only) {
     osa_env_transition<E>(s, nullptr, at, a.action + (long)n * a.ld_a, r, c);
+    term = osa_env_terminal<E>(s, nullptr, at) ? 1 : 0;  // (a compile-time 0 without E::terminal)
     trunc = osa_step_trunc(a, n, count);
+    if (term) trunc = 0;  // termination wins over a time limit reached on the same step
     if (trunc && a.final_obs)
       for (int k = lane; k < a.D; k += LANES)
         a.final_obs[(long)n * a.ld_f + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
   }
-  if (a.reset_only || trunc) E::fresh(s, at, nullptr);
+  if (a.reset_only || trunc || term) E::fresh(s, at, nullptr);
   for (int k = lane; k < a.D; k += LANES)
     a.obs[(long)n * a.ld + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
   if (lane == 0) {
     E::store(s, srow);
-    osa_step_end(a, n, r, c, trunc, count);
+    osa_step_end(a, n, r, c, trunc, count, term);
   }
 }
 #pragma clang fp contract(fast)

@@ -119,6 +119,8 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
       for (int q = 0; q < E::TRACE; ++q) rec[in_w + nd.act_dim + 3 + q] = E::state_col(s, srow, q);
     }
     osa_env_transition<E>(s, srow, at, arow, rw, cs);
+    // the description's own end of the episode (a compile-time false for one without terminal(): the built-in families)
+    const bool env_terminal = osa_env_terminal<E>(s, srow, at);
     if (rec && g == 0) {
       rec[in_w + nd.act_dim + 0] = rw;
       rec[in_w + nd.act_dim + 1] = cs;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
       cost = cost + pow(a.cost_criteria, (double)len) * (double)cs;
       const bool term = a.early_terminated && cost >= a.cost_limit;
       len += 1;
-      if (term || trunc) {
+      if (term || trunc || env_terminal) {
         alive = false;
         if (g == 0) {
           a.ep_ret[k] = ret;

@@ -68,7 +68,8 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
     """Host side of a vector CMDP that lives entirely in HBM: one launch of the subclass's entry point per ``reset``
     / ``step`` on buffers allocated once.  Observations are double-buffered (the caller may still hold the previous
     one); all envs reset together, so the truncating steps are known on the host and ``info['final_observation']`` /
-    ``info['_final_observation']`` appear on exactly those.  Philox stream position = ``_t_base`` (device) + ``_t``
+    ``info['_final_observation']`` appear on exactly those (a class with ``terminates``: on every step from the
+    ``horizon``-th after a reset on, see ``step``).  Philox stream position = ``_t_base`` (device) + ``_t``
     (host, passed by value); ``commit()`` folds the host part into the device part: a captured hipGraph of an epoch
     replays with the same by-value positions 0..T while the device part advances, so every epoch still draws fresh
     numbers.
@@ -95,6 +96,7 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
     need_time_limit_wrapper = False
     need_evaluation = False
     graph_safe = True  # every step is a fixed sequence of launches on device tensors (no host-side data flow)
+    terminates = False  # whether an env ends episodes of its own (a custom description with terminal()); see step()
     _cost_p = 0.0
 
     @classmethod
@@ -181,7 +183,15 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
         obs = self._launch(self._middle_args(action), 0)
         self._since_reset += 1
         info: dict[str, Any] = {}
-        if self._since_reset % self._horizon == 0:  # every env truncates on this step
+        if self.terminates:
+            # Episodes end per env, so which steps truncate is known to the device alone.  No env can truncate earlier
+            # than `horizon` steps after the common reset: from there on every step hands out the final observations
+            # under the device's `truncated` mask (often all zeros), and none before -- still a function of
+            # host-known numbers only, so the captured rollout graph keeps replaying.
+            have_final = self._since_reset >= self._horizon
+        else:
+            have_final = self._since_reset % self._horizon == 0  # every env truncates on this step
+        if have_final:
             info['final_observation'] = self._final
             info['_final_observation'] = self._trunc
         return obs, self._reward, self._cost, self._term, self._trunc, info
@@ -337,8 +347,9 @@ class NavCarCircleVectorEnv(DeviceVectorEnv):
 # ----------------------------------------------------------------------------------------------------------------
 class CustomDeviceEnv(DeviceEnvProtocol):
     """A device env whose kernels live in a library of its own.  ``register_device_env`` makes one subclass per
-    description; its dimensions are what the compiled library reports (osa_custom_env_info).  ``eval_kind`` is the
-    level: the first argument of the library's osa_custom_eval_episodes."""
+    description; its dimensions are what the compiled library reports (osa_custom_env_info), and so is ``terminates``:
+    whether the description has a ``terminal()`` member and ends episodes per env.  ``eval_kind`` is the level: the
+    first argument of the library's osa_custom_eval_episodes."""
 
     entry_point = 'osa_custom_env_step'
     eval_entry_point = 'osa_custom_eval_episodes'
@@ -394,7 +405,7 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
         if env_id in ENV_REGISTRY or env_id in CUSTOM_ENV_REGISTRY:
             raise KeyError(f'{env_id} is registered already')
     path = _build.build_custom_env(header, struct)
-    cdll, (state, obs, _dyn, act, trace, max_level, lanes, _) = _bind_custom(path)
+    cdll, (state, obs, _dyn, act, trace, max_level, lanes, terminates) = _bind_custom(path)
     for env_id, level in levels.items():
         if not isinstance(level, int) or not 0 <= level <= max_level:
             raise ValueError(f'{env_id}: level {level!r}, but {struct} has levels 0 .. {max_level}')
@@ -413,7 +424,7 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
             '__doc__': f'Device env {struct} of {header} (register_device_env).', '__module__': __name__,
             '_support_envs': list(levels), 'levels': levels, 'obs_act_dims': (obs, act), 'state_width': state,
             'trace_state_floats': trace, 'default_horizon': int(default_horizon), 'max_level': max_level,
-            'lanes': lanes, 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll})
+            'lanes': lanes, 'terminates': bool(terminates), 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll})
     for env_id in levels:
         CUSTOM_ENV_REGISTRY[env_id] = cls
     return cls
