@@ -1,6 +1,6 @@
 /* omnisafe_amd_env.h -- a device env of your own: the description contract and the C ABI of the library that
  * omnisafe_amd.build.build_custom_env(header, struct) makes of it (csrc/custom/custom_env.hip).  libomnisafe_amd.so
- * exports none of these symbols; every custom library exports all three.  Error codes are omnisafe_amd.h's.
+ * exports none of these symbols; every custom library exports all five.  Error codes are omnisafe_amd.h's.
  *
  * THE DESCRIPTION is a struct of static members in a header of yours.  The header is compiled for gfx950 behind
  * csrc/env_device.h, inside a `#pragma clang fp contract(off)` region: float32, no fused multiply-adds.
@@ -27,6 +27,12 @@
  *     static __device__ float state_col(const Regs&, const float* row, int col);            // col < TRACE
  *     static __device__ bool terminal(const Regs&, const float* row, const OsaEnvAt&);      // optional: true ends
  *                                                                     // the episode (see TERMINATION below)
+ *     static constexpr float DRAW_VIEW = ..;    // optional, with draw(): half-width of the fixed camera's view, > 0
+ *     static constexpr float DRAW_TRACK = ..;   // optional: half-width of the tracking camera's view (default 1)
+ *     static __device__ void position(const float* rec, float& x, float& y);   // with draw(): what the trail and
+ *                                                                     // the tracking camera follow
+ *     static __device__ void draw(const float* rec, const OsaDrawAt&, OsaScene&);           // optional: the picture
+ *                                                                     // of a state row (see DRAWING below)
  *   };
  *
  * `row` is never a pointer the description may read (nullptr in the per-step kernel): it exists for the built-in
@@ -49,9 +55,43 @@
  *   - a step truncates when steps[n] + 1 >= horizon and it is not terminal; steps[n] returns to 0 on either end.
  * The evaluation kernel ends episode k on the same answer, with ep_len the steps played.
  *
+ * DRAWING.  A description with draw() can be looked at: osa_custom_render_episode rasterises frames of its state rows
+ * (csrc/scene_render.h), which Evaluator.render, Agent.render, AgentGroup.render and the env's render() call.  Without
+ * the member the description "does not draw": osa_custom_render_episode returns OSA_EUNSUPPORTED, and nothing else
+ * about the library differs.
+ *   - `rec` is the TRACE leading floats of a state row: in a replay the tail of a trace record, in env.render() the
+ *     leading floats of the env's row of the state matrix.  These are the same floats (state_col(col) of a traced
+ *     state is srow[col] of the stored one for col < TRACE); the per-step evaluator path relies on that already.
+ *     draw() and position() may read rec[0 .. TRACE) and nothing else.
+ *   - OsaDrawAt {int level; int hit; int frame;}: the level the caller names, the caller's hit[f] != 0 (the evaluator:
+ *     the step into this record had a positive cost), and the record's index f.
+ *   - draw() paints by appending primitives to the scene in painter's order (a later primitive wins); a frame starts
+ *     as the background everywhere (OSA_COLOUR_OUTSIDE).  Each test is float32 without fused multiply-adds, on the
+ *     sub-sample (x, y) with dx = x - ox, dy = y - oy:
+ *         scene.disc(ox, oy, r2, colour)             dx*dx + dy*dy <= r2
+ *         scene.ring(ox, oy, lo2, hi2, colour)       lo2 <= dx*dx + dy*dy && dx*dx + dy*dy <= hi2
+ *         scene.box(x0, y0, x1, y1, colour)          x0 <= x && x <= x1 && y0 <= y && y <= y1
+ *         scene.segment(ax, ay, bx, by, hw2, colour) the segment test of osa_render_episode (omnisafe_amd.h) with
+ *                                                    e = b - a and L2 = ex*ex + ey*ey, computed once when staged
+ *         scene.trail(hw2, colour)                   at most once (a second call is ignored): the path through
+ *                                                    position() of records max(0, f - trail) .. f, segment by segment
+ *                                                    at half-width sqrt(hw2), is painted at this place in the order;
+ *                                                    never called: no trail
+ *   - A colour is 0xRRGGBB.  The palette of osa_render_episode is there by name: OSA_COLOUR_OUTSIDE, _FLOOR, _COST,
+ *     _RING, _HAZARD, _GOAL, _VASE, _TRAIL, _POINT, _CAR, _HIT, _HEADING.
+ *   - A scene holds at most OSA_DRAW_MAX = 64 primitives (the trail is one); what is appended past the cap is
+ *     dropped.  osa_custom_render_info reports the cap.
+ *   - The sub-sample positions, the integer mean per channel, the cameras, first / count / trail / hit and the
+ *     argument checks are those of osa_render_episode (omnisafe_amd.h) and are not restated here.  Only the centre
+ *     and the half-width of the view differ: the fixed camera looks at (0, 0) with half-width DRAW_VIEW, the tracking
+ *     camera at position() of the frame's record with half-width DRAW_TRACK.
+ *   - draw() runs in one lane per workgroup, position() in many; both must be deterministic functions of `rec` (and
+ *     `at`): no atomics, no cross-lane operations, no memory but the arguments.
+ *
  * A static_assert with a message that names the member rejects LDS_ROW == true, STATE outside 1 .. 64, ACT outside
  * 1 .. 32, TRACE > STATE, a missing member, and a member named terminal that cannot be called as stated above (it
- * would silently be an env that never ends).
+ * would silently be an env that never ends), and likewise a member named draw that cannot be called as stated above,
+ * draw without position or without DRAW_VIEW, DRAW_VIEW <= 0, and draw with TRACE == 0.
  */
 #ifndef OMNISAFE_AMD_ENV_H
 #define OMNISAFE_AMD_ENV_H
@@ -83,6 +123,18 @@ int osa_custom_eval_episodes(int level, int K, int obs_dim, int act_dim, int hid
                              float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
                              double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
                              void* stream);
+
+/* What the description says about drawing: out_i[0 .. 4) = 1 where it has draw() (else 0), OSA_DRAW_MAX, TRACE, and a
+ * reserved 0; out_f[0 .. 2) = DRAW_VIEW, DRAW_TRACK (both 0 where it does not draw). */
+int osa_custom_render_info(int out_i[4], float out_f[2]);
+
+/* Frames first .. first + count - 1 of one episode, as osa_render_episode (omnisafe_amd.h) with the level in the place
+ * of env_kind and the picture that draw() states: record f has its TRACE floats at state + f * stride.  OSA_EINVAL
+ * before any launch on the conditions of osa_render_episode and for a level outside 0 .. LEVELS; OSA_EUNSUPPORTED for
+ * a description without draw(). */
+int osa_custom_render_episode(int level, const float* state, long stride, int first, int count, int trail,
+                              const uint8_t* hit, int camera, int width, int height, int supersample, uint8_t* rgb,
+                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,10 +2,11 @@
 //   hipcc ... -DOSA_CUSTOM_ENV_HEADER="<absolute path of the header>" -DOSA_CUSTOM_ENV=<struct> custom_env.hip
 // The header is included behind env_device.h and inside a `fp contract(off)` region: its arithmetic is float32 without
 // fused multiply-adds, and it may use everything env_device.h has (osa_philox, osa_u01, osa_nav_*, OsaNavEnv<...>).
-// The description contract and the three entry points are specified in include/omnisafe_amd_env.h.  This file is in a
+// The description contract and the five entry points are specified in include/omnisafe_amd_env.h.  This file is in a
 // directory of its own because every csrc/*.hip goes into libomnisafe_amd.so.
 #include "../env_frame.h"
 #include "../eval_episodes.h"
+#include "../scene_render.h"  // OsaScene, OsaDrawAt and the palette, for a description with draw()
 #include "../../../include/omnisafe_amd_env.h"
 
 #if !defined(OSA_CUSTOM_ENV_HEADER) || !defined(OSA_CUSTOM_ENV)
@@ -90,6 +91,50 @@ template <class E, class = void>
 struct OsaNamesTerminal : std::true_type {};
 template <class E>
 struct OsaNamesTerminal<E, std::void_t<decltype(&OsaTerminalProbe<E>::terminal)>> : std::false_type {};
+
+// draw() is optional in the same way (OsaHasDraw, scene_render.h), and a member of that name which cannot be called as
+// stated must not pass for "does not draw".
+struct OsaDrawName {
+  int draw;
+};
+template <class E>
+struct OsaDrawProbe : E, OsaDrawName {};
+template <class E, class = void>
+struct OsaNamesDraw : std::true_type {};
+template <class E>
+struct OsaNamesDraw<E, std::void_t<decltype(&OsaDrawProbe<E>::draw)>> : std::false_type {};
+
+// What a drawing description needs besides draw(), each asked for only where what it needs is there.
+template <class E, bool = OsaHasDrawView<E>::value>
+struct OsaDrawViewOk : std::true_type {};
+template <class E>
+struct OsaDrawViewOk<E, true> : std::integral_constant<bool, (E::DRAW_VIEW > 0)> {};
+template <class E, bool = OsaHas_TRACE<E>::value>
+struct OsaDrawTraceOk : std::true_type {};
+template <class E>
+struct OsaDrawTraceOk<E, true> : std::integral_constant<bool, (E::TRACE >= 1)> {};
+template <class E, bool = OsaHasDraw<E>::value>
+struct OsaCustomDraw {
+  static constexpr bool callable = !OsaNamesDraw<E>::value, position = true, has_view = true, view = true, trace = true,
+                        draws = false;
+};
+template <class E>
+struct OsaCustomDraw<E, true> {
+  static constexpr bool callable = true, position = OsaHasPosition<E>::value, has_view = OsaHasDrawView<E>::value,
+                        view = OsaDrawViewOk<E>::value, trace = OsaDrawTraceOk<E>::value,
+                        draws = position && has_view && view && trace && OsaHas_TRACE<E>::value;
+};
+static_assert(OsaCustomDraw<OsaCustomEnv>::callable,
+              "custom env: the description has a member draw that cannot be called as draw(const float* rec, const "
+              "OsaDrawAt&, OsaScene&); it would be an env that silently does not draw");
+static_assert(OsaCustomDraw<OsaCustomEnv>::position,
+              "custom env: a description with draw() needs position(const float* rec, float& x, float& y) (what the "
+              "trail and the tracking camera follow)");
+static_assert(OsaCustomDraw<OsaCustomEnv>::has_view,
+              "custom env: a description with draw() needs DRAW_VIEW (half-width of the fixed camera's view)");
+static_assert(OsaCustomDraw<OsaCustomEnv>::view, "custom env: DRAW_VIEW must be greater than 0");
+static_assert(OsaCustomDraw<OsaCustomEnv>::trace,
+              "custom env: a description with draw() needs TRACE >= 1 (draw() sees the TRACE leading state floats)");
 
 template <class E, bool = OsaHas_Regs<E>::value>
 struct OsaCustomFunctions {
@@ -180,7 +225,56 @@ struct OsaCustomLib<E, true> {
   }
 };
 
+// The rasteriser, for a description that draws (and whose contract is whole); every library has both entry points.
+template <class E, bool = OsaCustomDraw<E>::draws && OsaCustomDraw<E>::callable && OsaCustomRanges<E>::complete &&
+                          OsaCustomRanges<E>::trace>
+struct OsaCustomRender {
+  static void info(int* out_i, float* out_f) {
+    out_i[0] = 0;
+    out_f[0] = out_f[1] = 0.f;
+  }
+  template <class... A>
+  static int render(A...) {
+    return OSA_EUNSUPPORTED;
+  }
+};
+template <class E>
+struct OsaCustomRender<E, true> {
+  static void info(int* out_i, float* out_f) {
+    out_i[0] = 1;
+    out_f[0] = E::DRAW_VIEW;
+    out_f[1] = OsaDrawTrack<E>::value;
+  }
+  template <class... A>
+  static int render(A... args) {
+    return osa_scene_render_launch<E>(args...);
+  }
+};
+template <class E, bool = OsaHas_TRACE<E>::value>
+struct OsaCustomTrace : std::integral_constant<int, 0> {};
+template <class E>
+struct OsaCustomTrace<E, true> : std::integral_constant<int, E::TRACE> {};
+
 extern "C" {
+
+int osa_custom_render_info(int* out_i, float* out_f) {
+  OSA_REQUIRE(out_i && out_f);
+  OsaCustomRender<OsaCustomEnv>::info(out_i, out_f);
+  out_i[1] = OSA_DRAW_MAX;
+  out_i[2] = OsaCustomTrace<OsaCustomEnv>::value;
+  out_i[3] = 0;
+  return OSA_OK;
+}
+
+int osa_custom_render_episode(int level, const float* state, long stride, int first, int count, int trail,
+                              const uint8_t* hit, int camera, int width, int height, int supersample, uint8_t* rgb,
+                              void* stream) {
+  const int rc = osa_render_check(state, rgb, first, count, trail, camera, width, height, supersample);
+  if (rc != OSA_OK) return rc;
+  OSA_REQUIRE(level >= 0 && level <= OSA_CUSTOM_LEVELS);
+  return OsaCustomRender<OsaCustomEnv>::render(level, state, stride, first, count, trail, hit, camera, width, height,
+                                               supersample, rgb, stream);
+}
 
 int osa_custom_env_info(int* out) {
   OSA_REQUIRE(out);

@@ -9,20 +9,9 @@
 // workgroup, which stages the frame's scene once in LDS: the state row of the frame's record and, in chunks of
 // OSA_RENDER_CHUNK segments, the trail (start, extent and squared length of every segment, computed once by one lane
 // each).  Workgroups share nothing and write disjoint bytes: no atomics, no flags, no order between workgroups.
-#include "osa_common.h"
+#include "render_common.h"  // the palette, osa_render_disc, osa_render_segment, the argument checks
 
-#define OSA_RENDER_THREADS 256
-#define OSA_RENDER_CHUNK 256  // trail segments staged per round (5 KB of LDS)
 #define OSA_RENDER_ROW 64     // floats of the widest state row
-
-// the palette, 0xRRGGBB (the table of include/omnisafe_amd.h and tests/render_twin.py)
-enum {
-  OSA_PAL_OUTSIDE, OSA_PAL_FLOOR, OSA_PAL_COST, OSA_PAL_RING, OSA_PAL_HAZARD, OSA_PAL_GOAL, OSA_PAL_VASE,
-  OSA_PAL_TRAIL, OSA_PAL_POINT, OSA_PAL_CAR, OSA_PAL_HIT, OSA_PAL_HEADING, OSA_PAL_COUNT
-};
-static __device__ const unsigned OSA_RENDER_PALETTE[OSA_PAL_COUNT] = {
-    0x282C34, 0xECECE4, 0xF4CCC4, 0x60A060, 0x5A64DC, 0x46BE5A, 0x50C8D2,
-    0xFAA028, 0xC82828, 0x8232AA, 0xFF00C8, 0x141414};
 
 struct OsaRenderArgs {
   const float* state;
@@ -45,25 +34,6 @@ struct OsaRenderArgs {
 };
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ bool osa_render_disc(float x, float y, float ox, float oy, float r2) {
-  const float dx = x - ox, dy = y - oy;
-  return dx * dx + dy * dy <= r2;
-}
-
-// The segment from (ax, ay) with extent (ex, ey) and squared length L2, at half-width sqrt(hw2).
-__device__ __forceinline__ bool osa_render_segment(float x, float y, float ax, float ay, float ex, float ey, float L2,
-                                                   float hw2) {
-  const float wx = x - ax, wy = y - ay;
-  float t = 0.f;
-  if (L2 != 0.f) {
-    t = (wx * ex + wy * ey) / L2;
-    t = t < 0.f ? 0.f : t;
-    t = t > 1.f ? 1.f : t;
-  }
-  const float dx = wx - t * ex, dy = wy - t * ey;
-  return dx * dx + dy * dy <= hw2;
-}
-
 template <int S>
 __global__ __launch_bounds__(OSA_RENDER_THREADS) void osa_render_kernel(OsaRenderArgs a) {
   __shared__ float row[OSA_RENDER_ROW];
@@ -181,10 +151,8 @@ extern "C" {
 int osa_render_episode(int env_kind, const float* state, long stride, int first, int count, int trail,
                        const uint8_t* hit, int camera, int width, int height, int supersample, uint8_t* rgb,
                        void* stream) {
-  OSA_REQUIRE(state && rgb && (reinterpret_cast<uintptr_t>(rgb) & 3) == 0);
-  OSA_REQUIRE(count >= 1 && first >= 0 && trail >= 0 && first <= 2147483647 - count);
-  OSA_REQUIRE(width >= 4 && width <= 4096 && width % 4 == 0 && height >= 1 && height <= 4096);
-  OSA_REQUIRE(supersample >= 1 && supersample <= 4 && (camera == 0 || camera == 1));
+  const int rc = osa_render_check(state, rgb, first, count, trail, camera, width, height, supersample);
+  if (rc != OSA_OK) return rc;
   OsaRenderArgs a = {};
   const bool reach = env_kind == OSA_EVAL_ENV_REACH;
   const int families[4] = {OSA_EVAL_ENV_NAV0, OSA_EVAL_ENV_CIRCLE0, OSA_EVAL_ENV_CARGOAL0, OSA_EVAL_ENV_CARCIRCLE0};

@@ -85,7 +85,7 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
     entry_point: str
     eval_entry_point = 'osa_eval_episodes'
     takes_level = False  # the entry point takes a level even while `levels` is empty (a custom class without ids)
-    render_state = True  # whether the rasteriser (csrc/render_kernels.hip) knows the state row
+    render_state = True  # whether a rasteriser knows the state row (csrc/render_kernels.hip, or a description's draw())
     levels: dict[str, int] = {}
     obs_act_dims = (60, 2)
     state_width = 0
@@ -108,6 +108,11 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
     def eval_kind(cls, env_id: str) -> int:
         """env_kind of osa_eval_episodes."""
         return cls.eval_kind_base + cls.levels.get(env_id, 0)
+
+    @classmethod
+    def render_kind(cls, env_id: str):
+        """What ``render.rasterise`` takes in the place of its ``env_kind`` to draw a state row of this id."""
+        return cls.eval_kind(env_id)
 
     @classmethod
     def library(cls):
@@ -210,7 +215,7 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
 
         if not 0 <= lane < self._num_envs:
             raise IndexError(f'lane {lane} of {self._num_envs} envs')
-        frame = render_mod.rasterise(self.eval_kind(self._env_id), self.state, lane * self.state_width,
+        frame = render_mod.rasterise(self.render_kind(self._env_id), self.state, lane * self.state_width,
                                      self.state_width, 0, 1, 0, None, render_mod.camera_index(camera_name),
                                      width, height, 2)
         return frame[0].cpu().numpy()
@@ -349,13 +354,18 @@ class CustomDeviceEnv(DeviceEnvProtocol):
     """A device env whose kernels live in a library of its own.  ``register_device_env`` makes one subclass per
     description; its dimensions are what the compiled library reports (osa_custom_env_info), and so is ``terminates``:
     whether the description has a ``terminal()`` member and ends episodes per env.  ``eval_kind`` is the level: the
-    first argument of the library's osa_custom_eval_episodes."""
+    first argument of the library's osa_custom_eval_episodes.  ``draws`` (and with it ``render_state``) is what
+    osa_custom_render_info reports: whether the description has a ``draw()`` member, which the library's generic scene
+    rasteriser (csrc/scene_render.h) turns into ``render()`` and ``Evaluator.render`` for the class."""
 
     entry_point = 'osa_custom_env_step'
     eval_entry_point = 'osa_custom_eval_episodes'
     takes_level = True
     graph_safe = True
-    render_state = False  # (a state row the rasteriser has never heard of)
+    render_state = False  # (a state row the rasteriser has never heard of, unless the description draws it)
+    draws = False
+    draw_max = 0  # OSA_DRAW_MAX of the library: the primitives a scene holds
+    draw_view = (0.0, 0.0)  # DRAW_VIEW, DRAW_TRACK
     header: str
     struct: str
     lib_path: str
@@ -369,17 +379,30 @@ class CustomDeviceEnv(DeviceEnvProtocol):
         _lib.load(require_gpu=True)  # (no GPU: the same loud failure as the built-in envs; error texts come from there)
         return cls._cdll
 
+    @classmethod
+    def render_kind(cls, env_id: str):
+        from . import render as render_mod
+
+        return render_mod.CustomScene(cls, cls.levels.get(env_id, 0))
+
     def render(self, *args, **kwargs):
+        if self.draws:
+            return super().render(*args, **kwargs)
         # (the ValueError of Evaluator.render for an env without a drawable state row)
         raise ValueError(f'{self._env_id} has no state row to draw: render() takes the geometric device envs '
                          '(SynthReach-v0, SynthNav*-v0)')
 
 
 def _bind_custom(path: str):
-    """dlopen a custom library and declare its three prototypes; returns (CDLL, info[8])."""
+    """dlopen a custom library and declare its five prototypes (include/omnisafe_amd_env.h); returns
+    (CDLL, info[8], (draws, OSA_DRAW_MAX, DRAW_VIEW, DRAW_TRACK))."""
     import ctypes as C
 
     lib = C.CDLL(path)
+    lib.osa_custom_render_info.restype = C.c_int
+    lib.osa_custom_render_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.osa_custom_render_episode.restype, lib.osa_custom_render_episode.argtypes = \
+        _lib.SIGNATURES['osa_render_episode']
     lib.osa_custom_env_info.restype, lib.osa_custom_env_info.argtypes = C.c_int, [C.POINTER(C.c_int)]
     lib.osa_custom_env_step.restype, lib.osa_custom_env_step.argtypes = _lib.SIGNATURES['osa_nav_env_step']
     lib.osa_custom_eval_episodes.restype, lib.osa_custom_eval_episodes.argtypes = _lib.SIGNATURES['osa_eval_episodes']
@@ -387,7 +410,11 @@ def _bind_custom(path: str):
     _lib_code = lib.osa_custom_env_info(info)
     if _lib_code != 0:
         raise _lib.OsaError(f'osa_custom_env_info of {path} failed ({_lib_code})')
-    return lib, list(info)
+    draw_i, draw_f = (C.c_int * 4)(), (C.c_float * 2)()
+    _lib_code = lib.osa_custom_render_info(draw_i, draw_f)
+    if _lib_code != 0:
+        raise _lib.OsaError(f'osa_custom_render_info of {path} failed ({_lib_code})')
+    return lib, list(info), (bool(draw_i[0]), draw_i[1], draw_f[0], draw_f[1])
 
 
 def register_device_env(header: str, struct: str, ids, default_horizon: int = 1000) -> type:
@@ -405,7 +432,8 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
         if env_id in ENV_REGISTRY or env_id in CUSTOM_ENV_REGISTRY:
             raise KeyError(f'{env_id} is registered already')
     path = _build.build_custom_env(header, struct)
-    cdll, (state, obs, _dyn, act, trace, max_level, lanes, terminates) = _bind_custom(path)
+    cdll, (state, obs, _dyn, act, trace, max_level, lanes, terminates), (draws, draw_max, view, track) = \
+        _bind_custom(path)
     for env_id, level in levels.items():
         if not isinstance(level, int) or not 0 <= level <= max_level:
             raise ValueError(f'{env_id}: level {level!r}, but {struct} has levels 0 .. {max_level}')
@@ -424,7 +452,8 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
             '__doc__': f'Device env {struct} of {header} (register_device_env).', '__module__': __name__,
             '_support_envs': list(levels), 'levels': levels, 'obs_act_dims': (obs, act), 'state_width': state,
             'trace_state_floats': trace, 'default_horizon': int(default_horizon), 'max_level': max_level,
-            'lanes': lanes, 'terminates': bool(terminates), 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll})
+            'lanes': lanes, 'terminates': bool(terminates), 'draws': draws, 'render_state': draws, 'draw_max': draw_max,
+            'draw_view': (view, track), 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll})
     for env_id in levels:
         CUSTOM_ENV_REGISTRY[env_id] = cls
     return cls

@@ -5,7 +5,9 @@ omnisafe/evaluator.py:355-629).
 ``torch_save/<model_name>`` with keys ``pi`` and, with ``obs_normalize``, ``obs_normalizer``); ``evaluate()`` plays
 ``num_episodes`` episodes and returns ``(episode_rewards, episode_costs)`` as the reference does; ``render()`` plays them
 the same way and writes one animated PNG per episode, rasterised on the device from the state rows of the trace
-(osa_render_episode, csrc/render_kernels.hip; the picture is specified in include/omnisafe_amd.h).
+(osa_render_episode, csrc/render_kernels.hip; the picture is specified in include/omnisafe_amd.h -- or, for a class of
+register_device_env whose description has a draw(), osa_custom_render_episode of its library with the picture that
+draw() states, include/omnisafe_amd_env.h).
 
 Two paths, one semantics:
   persistent  a fused-family actor on a device env (SynthReach-v0, SynthNavGoal*-v0, SynthNavCircle*-v0,
@@ -314,7 +316,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         tr = self.trace.contiguous()  # [T][K][rec]; a record ends with the state row before its step
         T, K, rec = tr.shape
         state_w = cls.trace_state_floats
-        kind = cls.eval_kind(self._env_id)
+        kind = cls.render_kind(self._env_id)  # (env_kind of the built-in rasteriser, or the custom class and level)
         # hit[f]: record f - 1 had a positive cost (the cost column is two in front of the alive flag and the state)
         hit = torch.zeros(K, T, dtype=torch.uint8, device=tr.device)
         hit[:, 1:] = (tr[:-1, :, rec - state_w - 2] > 0).t()

@@ -1,5 +1,7 @@
 """Host side of osa_render_episode (csrc/render_kernels.hip): frames of the top-down picture that
-include/omnisafe_amd.h specifies, rasterised on the device from the state rows of a trace or of a live env.
+include/omnisafe_amd.h specifies, rasterised on the device from the state rows of a trace or of a live env -- and of
+osa_custom_render_episode (csrc/scene_render.h), the same for a class of ``register_device_env`` whose description has
+a ``draw()``: name it with a :class:`CustomScene` wherever an ``env_kind`` is taken.
 
 ``rasterise`` is one launch into a device tensor; ``stream_frames`` renders an episode in chunks of bounded device
 memory and hands each chunk to the host through one pinned buffer, as numpy views that are valid until the next chunk.
@@ -8,6 +10,7 @@ There is no host rasteriser: without the library or a GPU this raises (omnisafe_
 from __future__ import annotations
 
 import time
+from typing import NamedTuple
 
 import torch
 
@@ -17,9 +20,18 @@ CAMERAS = {'fixed': 0, 'track': 1}
 CHUNK_BYTES = 32 << 20  # device (and pinned host) bytes of a chunk of frames
 
 
-def row_floats(env_kind: int) -> int:
+class CustomScene(NamedTuple):
+    """In the place of an ``env_kind``: a class of ``register_device_env`` that draws (``cls.draws``) and the level
+    that its ``draw()`` is told."""
+    cls: type
+    level: int
+
+
+def row_floats(env_kind) -> int:
     """Leading floats of a state row that the kernel reads: SynthReach 6, the Goal families up to the last vase, the
-    Circle families p and u."""
+    Circle families p and u; a custom class its TRACE."""
+    if isinstance(env_kind, CustomScene):
+        return env_kind.cls.trace_state_floats
     return 6 if env_kind == 1 else (4 if (env_kind // 16) % 2 == 0 else 52)
 
 
@@ -29,13 +41,19 @@ def camera_index(camera_name: str) -> int:
     return CAMERAS[camera_name]
 
 
-def rasterise(env_kind: int, rows: torch.Tensor, offset: int, stride: int, first: int, count: int, trail: int,
-              hit: torch.Tensor | None, camera: int, width: int, height: int, supersample: int,
+def rasterise(env_kind: int | CustomScene, rows: torch.Tensor, offset: int, stride: int, first: int, count: int,
+              trail: int, hit: torch.Tensor | None, camera: int, width: int, height: int, supersample: int,
               out: torch.Tensor | None = None) -> torch.Tensor:
     """Frames first .. first + count - 1 of the episode whose record f has its state row at element
     ``offset + f * stride`` of the float32 device tensor ``rows``; ``hit``: uint8[>= first + count] on the device or
     None.  Returns (a view of ``out`` as) uint8 [count, height, width, 3] on the device."""
     lib = _lib.load(require_gpu=True)
+    if isinstance(env_kind, CustomScene):
+        if not env_kind.cls.draws:
+            raise ValueError(f'{env_kind.cls.struct} has no draw(): nothing to rasterise')
+        entry, what = env_kind.cls.library().osa_custom_render_episode, env_kind.level
+    else:
+        entry, what = lib.osa_render_episode, env_kind
     assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.is_cuda
     assert first >= 0 and count >= 1 and offset >= 0 and stride >= 0
     assert offset + (first + count - 1) * stride + row_floats(env_kind) <= rows.numel()
@@ -44,14 +62,14 @@ def rasterise(env_kind: int, rows: torch.Tensor, offset: int, stride: int, first
     if out is None:
         out = torch.empty(n, dtype=torch.uint8, device=rows.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n
-    _lib.check(lib.osa_render_episode(int(env_kind), rows.data_ptr() + 4 * offset, int(stride), int(first), int(count),
-                                      int(trail), _lib.ptr(hit), int(camera), int(width), int(height),
-                                      int(supersample), out.data_ptr(), _lib.stream_ptr()), 'osa_render_episode')
+    _lib.check(entry(int(what), rows.data_ptr() + 4 * offset, int(stride), int(first), int(count), int(trail),
+                     _lib.ptr(hit), int(camera), int(width), int(height), int(supersample), out.data_ptr(),
+                     _lib.stream_ptr()), entry.__name__)
     return out.reshape(-1)[:n].view(count, height, width, 3)
 
 
-def stream_frames(env_kind: int, rows: torch.Tensor, offset: int, stride: int, frames: int, trail: int,
-                  hit: torch.Tensor | None, camera: int, width: int, height: int, supersample: int,
+def stream_frames(env_kind: int | CustomScene, rows: torch.Tensor, offset: int, stride: int, frames: int,
+                  trail: int, hit: torch.Tensor | None, camera: int, width: int, height: int, supersample: int,
                   frame_skip: int = 1, clock: dict | None = None):
     """Generator over numpy chunks [n, height, width, 3] of frames 0, frame_skip, 2 frame_skip, ... < ``frames``.
     ``clock`` (optional) accumulates the seconds spent in 'raster' (launch to completion) and 'copy' (device to pinned
@@ -77,4 +95,4 @@ def stream_frames(env_kind: int, rows: torch.Tensor, offset: int, stride: int, f
         yield host[:count * per].view(count, height, width, 3).numpy()[keep::frame_skip]
 
 
-__all__ = ['CAMERAS', 'camera_index', 'rasterise', 'stream_frames']
+__all__ = ['CAMERAS', 'CustomScene', 'camera_index', 'rasterise', 'stream_frames']
