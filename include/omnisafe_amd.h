@@ -945,6 +945,39 @@ int osa_eval_episodes(int env_kind, int K, int obs_dim, int act_dim, int hidden,
 /* Floats per trace record of osa_eval_episodes (0 for bad dims). */
 int osa_eval_trace_floats(int env_kind, int obs_dim, int act_dim, int saute);
 
+/* Stochastic data collection with a saved policy (omnisafe/common/offline/data_collector.py:145-190), one agent's block
+ * of total_rows = S dataset rows in ONE launch.  K lanes; lane k plays env index k of a device env from a fresh reset,
+ * at Philox stream positions 0 (reset), 1, 2, ... -- the numbers the per-step env launches of a fresh K-env vector env
+ * seeded `seed` draw for env k -- and owns the rows [k Q, min((k + 1) Q, S)) with Q = rows_per_lane, which it fills
+ * with consecutive episodes; the last one is cut off where the lane's rows end, and a lane with an empty range plays
+ * nothing.  S <= K * Q.  Step t (0-based) of lane k writes row i = k Q + t (data_collector.py:166-189):
+ *   obs[i]      the RAW env observation; the policy sees it normalised with FROZEN statistics (norm_*: as
+ *               osa_eval_episodes; all three NULL: no normaliser);
+ *   action[i]   the actor's sample mean + exp(log_std) * eps BEFORE ActionScale (fused family: hidden as for
+ *               osa_policy_step, act_dim <= 32); eps of dimension d is the first Box-Muller output of the Philox block
+ *               (noise_seed, t + 1, k * act_dim + d): what osa_policy_step draws for row k on the (t + 1)-th step of a
+ *               fresh actor seeded noise_seed.  The env receives the scaled action (old_min / old_max: act_dim floats,
+ *               as osa_action_scale);
+ *   reward[i], cost[i]   of the transition;
+ *   next_obs[i] the raw observation of the post-transition state, whether or not the episode ends;
+ *   done[i]     1.0 where the step terminates (a description with terminal()) or is the `horizon`-th of its episode
+ *               (the time limit is per lane), else 0.0.  After a done row the lane is reset at the SAME stream position
+ *               and obs[i + 1] is the observation of the fresh state; otherwise obs[i + 1] = next_obs[i].
+ * obs, next_obs: float [S][ld_obs >= obs_dim], [S][ld_next >= obs_dim]; action: float [S][ld_act >= act_dim]; reward,
+ * cost, done: float [S].  Only columns [0, obs_dim) / [0, act_dim) of rows [0, S) are written.  ep_ret_sum,
+ * ep_cost_sum: double[K], the sums of reward and cost over the lane's rows in row order; ep_count: int32[K], its done
+ * rows (data_collector.py:178-194 per lane).
+ * env_kind: as osa_eval_episodes, with its least widths; observations up to 304 columns (288 for the kinds with a 64-
+ * float state row) -- wider ones, and what osa_eval_episodes refuses: OSA_EUNSUPPORTED.  Arguments are checked before
+ * any launch. */
+int osa_collect_episodes(int env_kind, int K, int rows_per_lane, long total_rows, int obs_dim, int act_dim, int hidden,
+                         const float* params, const float* norm_mean, const float* norm_std, const long* norm_count,
+                         float norm_clip, const float* old_min, const float* old_max, float min_action,
+                         float max_action, unsigned long long seed, unsigned long long noise_seed, int horizon,
+                         float cost_p, float* obs, int ld_obs, float* action, int ld_act, float* reward, float* cost,
+                         float* next_obs, int ld_next, float* done, double* ep_ret_sum, double* ep_cost_sum,
+                         int* ep_count, void* stream);
+
 /* Rasterised replay of one episode of a geometric device env: frames first .. first + count - 1 of a top-down picture
  * of its state rows, written to rgb as uint8 [count][height][width][3].  The picture is a specification of this
  * package (the reference renders through MuJoCo, third-party CPU code: omnisafe/evaluator.py:511-629 only collects

@@ -1,6 +1,6 @@
 /* omnisafe_amd_env.h -- a device env of your own: the description contract and the C ABI of the library that
  * omnisafe_amd.build.build_custom_env(header, struct) makes of it (csrc/custom/custom_env.hip).  libomnisafe_amd.so
- * exports none of these symbols; every custom library exports all five.  Error codes are omnisafe_amd.h's.
+ * exports none of these symbols; every custom library exports all six.  Error codes are omnisafe_amd.h's.
  *
  * THE DESCRIPTION is a struct of static members in a header of yours.  The header is compiled for gfx950 behind
  * csrc/env_device.h, inside a `#pragma clang fp contract(off)` region: float32, no fused multiply-adds.
@@ -54,6 +54,12 @@
  *   - final_obs is NOT written for a terminating env (only truncated paths are bootstrapped from it);
  *   - a step truncates when steps[n] + 1 >= horizon and it is not terminal; steps[n] returns to 0 on either end.
  * The evaluation kernel ends episode k on the same answer, with ep_len the steps played.
+ *
+ * COLLECTION.  osa_custom_collect_episodes (OfflineDataCollector) plays the description in lanes that run episode after
+ * episode inside one launch.  It calls the same members in the same order as the per-step kernel -- transition(),
+ * terminal(), obs_col() on the post-transition state, then on an ending step fresh() at the step's own OsaEnvAt and
+ * obs_col() on the fresh state -- so a description needs nothing new for it; obs_col() is called for every column of
+ * the row whether or not the episode ends, and the rows it gives are stored raw.
  *
  * DRAWING.  A description with draw() can be looked at: osa_custom_render_episode rasterises frames of its state rows
  * (csrc/scene_render.h), which Evaluator.render, Agent.render, AgentGroup.render and the env's render() call.  Without
@@ -123,6 +129,18 @@ int osa_custom_eval_episodes(int level, int K, int obs_dim, int act_dim, int hid
                              float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
                              double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
                              void* stream);
+
+/* One agent's block of dataset rows in one launch: the argument list and the semantics of osa_collect_episodes
+ * (omnisafe_amd.h) with the level in the place of env_kind.  A description with terminal() ends episodes per lane: the
+ * terminating step's row carries done = 1 and the post-transition observation as next_obs, and the lane is reset by
+ * fresh() at the same stream position (see COLLECTION above). */
+int osa_custom_collect_episodes(int level, int K, int rows_per_lane, long total_rows, int obs_dim, int act_dim,
+                                int hidden, const float* params, const float* norm_mean, const float* norm_std,
+                                const long* norm_count, float norm_clip, const float* old_min, const float* old_max,
+                                float min_action, float max_action, unsigned long long seed,
+                                unsigned long long noise_seed, int horizon, float cost_p, float* obs, int ld_obs,
+                                float* action, int ld_act, float* reward, float* cost, float* next_obs, int ld_next,
+                                float* done, double* ep_ret_sum, double* ep_cost_sum, int* ep_count, void* stream);
 
 /* What the description says about drawing: out_i[0 .. 4) = 1 where it has draw() (else 0), OSA_DRAW_MAX, TRACE, and a
  * reserved 0; out_f[0 .. 2) = DRAW_VIEW, DRAW_TRACK (both 0 where it does not draw). */

@@ -139,6 +139,8 @@ SIGNATURES: dict[str, tuple] = {
     'osa_eval_episodes': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _F, _F, _U, _I, _F, _I, _I, _F, _F,
                                _I, _D, _D, _P, _P, _P, _P, _P]),
     'osa_eval_trace_floats': (_I, [_I, _I, _I, _I]),
+    'osa_collect_episodes': (_I, [_I, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _F, _F, _U, _U, _I, _F,
+                                  _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     'osa_render_episode': (_I, [_I, _P, _L, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
 }
 

@@ -2,10 +2,11 @@
 //   hipcc ... -DOSA_CUSTOM_ENV_HEADER="<absolute path of the header>" -DOSA_CUSTOM_ENV=<struct> custom_env.hip
 // The header is included behind env_device.h and inside a `fp contract(off)` region: its arithmetic is float32 without
 // fused multiply-adds, and it may use everything env_device.h has (osa_philox, osa_u01, osa_nav_*, OsaNavEnv<...>).
-// The description contract and the five entry points are specified in include/omnisafe_amd_env.h.  This file is in a
+// The description contract and the six entry points are specified in include/omnisafe_amd_env.h.  This file is in a
 // directory of its own because every csrc/*.hip goes into libomnisafe_amd.so.
 #include "../env_frame.h"
 #include "../eval_episodes.h"
+#include "../collect_episodes.h"
 #include "../scene_render.h"  // OsaScene, OsaDrawAt and the palette, for a description with draw()
 #include "../../../include/omnisafe_amd_env.h"
 
@@ -205,6 +206,10 @@ struct OsaCustomLib {
   static int eval(A...) {
     return OSA_EUNSUPPORTED;
   }
+  template <class... A>
+  static int collect(A...) {
+    return OSA_EUNSUPPORTED;
+  }
 };
 template <class E>
 struct OsaCustomLib<E, true> {
@@ -222,6 +227,11 @@ struct OsaCustomLib<E, true> {
   static int eval(int level, A... rest) {
     OSA_REQUIRE(level >= 0 && level <= OSA_CUSTOM_LEVELS);
     return osa_eval_launch<E>(level, rest...);
+  }
+  template <class... A>
+  static int collect(int level, A... rest) {
+    OSA_REQUIRE(level >= 0 && level <= OSA_CUSTOM_LEVELS);
+    return osa_collect_launch<E>(level, rest...);
   }
 };
 
@@ -307,6 +317,24 @@ int osa_custom_eval_episodes(int level, int K, int obs_dim, int act_dim, int hid
                                           norm_clip, old_min, old_max, min_action, max_action, seed, horizon, cost_p,
                                           max_steps, saute, saute_budget, saute_gamma, early_terminated, cost_limit,
                                           cost_criteria, ep_ret, ep_cost, ep_len, trace, stream);
+}
+
+int osa_custom_collect_episodes(int level, int K, int rows_per_lane, long total_rows, int obs_dim, int act_dim,
+                                int hidden, const float* params, const float* norm_mean, const float* norm_std,
+                                const long* norm_count, float norm_clip, const float* old_min, const float* old_max,
+                                float min_action, float max_action, unsigned long long seed,
+                                unsigned long long noise_seed, int horizon, float cost_p, float* obs, int ld_obs,
+                                float* action, int ld_act, float* reward, float* cost, float* next_obs, int ld_next,
+                                float* done, double* ep_ret_sum, double* ep_cost_sum, int* ep_count, void* stream) {
+  const int rc = osa_collect_check(K, rows_per_lane, total_rows, obs_dim, act_dim, params, norm_mean, norm_std,
+                                   norm_count, old_min, old_max, min_action, max_action, horizon, obs, ld_obs, action,
+                                   ld_act, reward, cost, next_obs, ld_next, done, ep_ret_sum, ep_cost_sum, ep_count);
+  if (rc != OSA_OK) return rc;
+  return OsaCustomLib<OsaCustomEnv>::collect(level, K, rows_per_lane, total_rows, obs_dim, act_dim, hidden, params,
+                                             norm_mean, norm_std, norm_count, norm_clip, old_min, old_max, min_action,
+                                             max_action, seed, noise_seed, horizon, cost_p, obs, ld_obs, action,
+                                             ld_act, reward, cost, next_obs, ld_next, done, ep_ret_sum, ep_cost_sum,
+                                             ep_count, stream);
 }
 
 }  // extern "C"

@@ -84,6 +84,7 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
 
     entry_point: str
     eval_entry_point = 'osa_eval_episodes'
+    collect_entry_point = 'osa_collect_episodes'  # (OfflineDataCollector's persistent path; env_kind as eval_kind)
     takes_level = False  # the entry point takes a level even while `levels` is empty (a custom class without ids)
     render_state = True  # whether a rasteriser knows the state row (csrc/render_kernels.hip, or a description's draw())
     levels: dict[str, int] = {}
@@ -116,7 +117,8 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
 
     @classmethod
     def library(cls):
-        """The library that exports ``entry_point`` and ``eval_entry_point``, its prototypes declared."""
+        """The library that exports ``entry_point``, ``eval_entry_point`` and ``collect_entry_point``, its prototypes
+        declared."""
         return _lib.load(require_gpu=True)
 
     def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int | None = None,
@@ -360,6 +362,7 @@ class CustomDeviceEnv(DeviceEnvProtocol):
 
     entry_point = 'osa_custom_env_step'
     eval_entry_point = 'osa_custom_eval_episodes'
+    collect_entry_point = 'osa_custom_collect_episodes'
     takes_level = True
     graph_safe = True
     render_state = False  # (a state row the rasteriser has never heard of, unless the description draws it)
@@ -394,7 +397,7 @@ class CustomDeviceEnv(DeviceEnvProtocol):
 
 
 def _bind_custom(path: str):
-    """dlopen a custom library and declare its five prototypes (include/omnisafe_amd_env.h); returns
+    """dlopen a custom library and declare its six prototypes (include/omnisafe_amd_env.h); returns
     (CDLL, info[8], (draws, OSA_DRAW_MAX, DRAW_VIEW, DRAW_TRACK))."""
     import ctypes as C
 
@@ -406,6 +409,8 @@ def _bind_custom(path: str):
     lib.osa_custom_env_info.restype, lib.osa_custom_env_info.argtypes = C.c_int, [C.POINTER(C.c_int)]
     lib.osa_custom_env_step.restype, lib.osa_custom_env_step.argtypes = _lib.SIGNATURES['osa_nav_env_step']
     lib.osa_custom_eval_episodes.restype, lib.osa_custom_eval_episodes.argtypes = _lib.SIGNATURES['osa_eval_episodes']
+    lib.osa_custom_collect_episodes.restype, lib.osa_custom_collect_episodes.argtypes = \
+        _lib.SIGNATURES['osa_collect_episodes']
     info = (C.c_int * 8)()
     _lib_code = lib.osa_custom_env_info(info)
     if _lib_code != 0:
