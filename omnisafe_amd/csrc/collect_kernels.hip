@@ -3,10 +3,10 @@
 // row j = k & 15 of the wave of workgroup k / 16 (the mapping of osa_eval_episodes_kernel) and owns the rows
 // [k Q, min((k + 1) Q, S)), which it fills with consecutive episodes: every step samples the actor (policy_rows.h's
 // expression and noise stream), scales the action, makes the env transition, keeps the RAW observation before and after
-// it, and resets inside the kernel where the episode ends.  Every lane stores the columns it computed; the row-wise
-// store form was measured slower (collect_episodes.h, profiles/collect_timing.json).  Every row has one owner: no
-// atomics, no spins and no barrier between workgroups.  The kernel template, its arguments and its launch are in
-// collect_episodes.h.
+// it, and resets inside the kernel where the episode ends.  Every lane stores the columns it computed; a row-wise store
+// form was measured slower (collect_episodes.h, profiles/collect_row_stores.json).  Every row has one owner: no atomics,
+// no spins and no barrier between workgroups.  The kernel template and its launch are in collect_episodes.h; the entry
+// point fills OsaCollectArgs, and what the kernel shares with the evaluation kernel is in play_episodes.h.
 //
 // Random numbers: lane k replays env index k of the per-step env launches at stream positions 0 (reset), 1, 2, ...
 // and row k of the per-step policy launches of a fresh actor seeded noise_seed, so that this kernel and the per-step
@@ -23,18 +23,23 @@ int osa_collect_episodes(int env_kind, int K, int rows_per_lane, long total_rows
                          float cost_p, float* obs, int ld_obs, float* action, int ld_act, float* reward, float* cost,
                          float* next_obs, int ld_next, float* done, double* ep_ret_sum, double* ep_cost_sum,
                          int* ep_count, void* stream) {
-  const int rc = osa_collect_check(K, rows_per_lane, total_rows, obs_dim, act_dim, params, norm_mean, norm_std,
-                                   norm_count, old_min, old_max, min_action, max_action, horizon, obs, ld_obs, action,
-                                   ld_act, reward, cost, next_obs, ld_next, done, ep_ret_sum, ep_cost_sum, ep_count);
-  if (rc != OSA_OK) return rc;
   const OsaEvalKind kind = osa_eval_kind(env_kind);
+  OsaCollectArgs a = {};
+  a.params = params;
+  a.K = K; a.obs_dim = obs_dim; a.max_steps = rows_per_lane; a.horizon = horizon;
+  a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
+  a.old_min = old_min; a.old_max = old_max; a.min_a = min_action; a.max_a = max_action;
+  a.seed = seed; a.cost_p = cost_p; a.level = kind.level;
+  a.ep_ret = ep_ret_sum; a.ep_cost = ep_cost_sum; a.ep_len = ep_count;
+  a.total_rows = total_rows; a.noise_seed = noise_seed;
+  a.obs = obs; a.action = action; a.reward = reward; a.cost = cost; a.next_obs = next_obs; a.done = done;
+  a.ld_obs = ld_obs; a.ld_act = ld_act; a.ld_next = ld_next;
+  const int rc = osa_collect_check(a, act_dim);
+  if (rc != OSA_OK) return rc;
   switch (kind.family) {
-#define OSA_LAUNCH(FAMILY, LEVELS, E)                                                                               \
-  case FAMILY:                                                                                                      \
-    return osa_collect_launch<E>(kind.level, K, rows_per_lane, total_rows, obs_dim, act_dim, hidden, params,        \
-                                 norm_mean, norm_std, norm_count, norm_clip, old_min, old_max, min_action,          \
-                                 max_action, seed, noise_seed, horizon, cost_p, obs, ld_obs, action, ld_act, reward, \
-                                 cost, next_obs, ld_next, done, ep_ret_sum, ep_cost_sum, ep_count, stream);
+#define OSA_LAUNCH(FAMILY, LEVELS, E) \
+  case FAMILY:                        \
+    return osa_collect_launch<E>(a, act_dim, hidden, stream);
     OSA_EVAL_FAMILIES(OSA_LAUNCH)
 #undef OSA_LAUNCH
   }

@@ -202,14 +202,8 @@ template <class E, bool = OsaCustomRanges<E>::complete && OsaCustomRanges<E>::re
 struct OsaCustomLib {
   static void info(int*) {}
   static int step(const OsaStepArgs&, void*) { return OSA_EUNSUPPORTED; }
-  template <class... A>
-  static int eval(A...) {
-    return OSA_EUNSUPPORTED;
-  }
-  template <class... A>
-  static int collect(A...) {
-    return OSA_EUNSUPPORTED;
-  }
+  static int eval(const OsaEvalArgs&, int, int, void*) { return OSA_EUNSUPPORTED; }
+  static int collect(const OsaCollectArgs&, int, int, void*) { return OSA_EUNSUPPORTED; }
 };
 template <class E>
 struct OsaCustomLib<E, true> {
@@ -223,15 +217,13 @@ struct OsaCustomLib<E, true> {
     return osa_env_step(osa_custom_env_kernel<E, OSA_CUSTOM_LANES>, E::OBS, 64 / OSA_CUSTOM_LANES, true, true, a,
                         stream, E::ACT);
   }
-  template <class... A>
-  static int eval(int level, A... rest) {
-    OSA_REQUIRE(level >= 0 && level <= OSA_CUSTOM_LEVELS);
-    return osa_eval_launch<E>(level, rest...);
+  static int eval(const OsaEvalArgs& a, int act_dim, int hidden, void* stream) {
+    OSA_REQUIRE(a.level >= 0 && a.level <= OSA_CUSTOM_LEVELS);
+    return osa_eval_launch<E>(a, act_dim, hidden, stream);
   }
-  template <class... A>
-  static int collect(int level, A... rest) {
-    OSA_REQUIRE(level >= 0 && level <= OSA_CUSTOM_LEVELS);
-    return osa_collect_launch<E>(level, rest...);
+  static int collect(const OsaCollectArgs& a, int act_dim, int hidden, void* stream) {
+    OSA_REQUIRE(a.level >= 0 && a.level <= OSA_CUSTOM_LEVELS);
+    return osa_collect_launch<E>(a, act_dim, hidden, stream);
   }
 };
 
@@ -309,14 +301,18 @@ int osa_custom_eval_episodes(int level, int K, int obs_dim, int act_dim, int hid
                              float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
                              double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
                              void* stream) {
-  const int rc = osa_eval_check(K, obs_dim, act_dim, params, norm_mean, norm_std, norm_count, old_min, old_max,
-                                min_action, max_action, horizon, max_steps, saute, saute_budget, saute_gamma, ep_ret,
-                                ep_cost, ep_len);
-  if (rc != OSA_OK) return rc;
-  return OsaCustomLib<OsaCustomEnv>::eval(level, K, obs_dim, act_dim, hidden, params, norm_mean, norm_std, norm_count,
-                                          norm_clip, old_min, old_max, min_action, max_action, seed, horizon, cost_p,
-                                          max_steps, saute, saute_budget, saute_gamma, early_terminated, cost_limit,
-                                          cost_criteria, ep_ret, ep_cost, ep_len, trace, stream);
+  OsaEvalArgs a = {};
+  a.params = params;
+  a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
+  a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
+  a.old_min = old_min; a.old_max = old_max; a.min_a = min_action; a.max_a = max_action;
+  a.seed = seed; a.cost_p = cost_p; a.level = level;
+  a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len;
+  a.saute = saute ? 1 : 0; a.budget = saute_budget; a.saute_gamma = saute_gamma;
+  a.early_terminated = early_terminated ? 1 : 0; a.cost_limit = cost_limit; a.cost_criteria = cost_criteria;
+  a.trace = trace;
+  const int rc = osa_eval_check(a, act_dim);
+  return rc != OSA_OK ? rc : OsaCustomLib<OsaCustomEnv>::eval(a, act_dim, hidden, stream);
 }
 
 int osa_custom_collect_episodes(int level, int K, int rows_per_lane, long total_rows, int obs_dim, int act_dim,
@@ -326,15 +322,18 @@ int osa_custom_collect_episodes(int level, int K, int rows_per_lane, long total_
                                 unsigned long long noise_seed, int horizon, float cost_p, float* obs, int ld_obs,
                                 float* action, int ld_act, float* reward, float* cost, float* next_obs, int ld_next,
                                 float* done, double* ep_ret_sum, double* ep_cost_sum, int* ep_count, void* stream) {
-  const int rc = osa_collect_check(K, rows_per_lane, total_rows, obs_dim, act_dim, params, norm_mean, norm_std,
-                                   norm_count, old_min, old_max, min_action, max_action, horizon, obs, ld_obs, action,
-                                   ld_act, reward, cost, next_obs, ld_next, done, ep_ret_sum, ep_cost_sum, ep_count);
-  if (rc != OSA_OK) return rc;
-  return OsaCustomLib<OsaCustomEnv>::collect(level, K, rows_per_lane, total_rows, obs_dim, act_dim, hidden, params,
-                                             norm_mean, norm_std, norm_count, norm_clip, old_min, old_max, min_action,
-                                             max_action, seed, noise_seed, horizon, cost_p, obs, ld_obs, action,
-                                             ld_act, reward, cost, next_obs, ld_next, done, ep_ret_sum, ep_cost_sum,
-                                             ep_count, stream);
+  OsaCollectArgs a = {};
+  a.params = params;
+  a.K = K; a.obs_dim = obs_dim; a.max_steps = rows_per_lane; a.horizon = horizon;
+  a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
+  a.old_min = old_min; a.old_max = old_max; a.min_a = min_action; a.max_a = max_action;
+  a.seed = seed; a.cost_p = cost_p; a.level = level;
+  a.ep_ret = ep_ret_sum; a.ep_cost = ep_cost_sum; a.ep_len = ep_count;
+  a.total_rows = total_rows; a.noise_seed = noise_seed;
+  a.obs = obs; a.action = action; a.reward = reward; a.cost = cost; a.next_obs = next_obs; a.done = done;
+  a.ld_obs = ld_obs; a.ld_act = ld_act; a.ld_next = ld_next;
+  const int rc = osa_collect_check(a, act_dim);
+  return rc != OSA_OK ? rc : OsaCustomLib<OsaCustomEnv>::collect(a, act_dim, hidden, stream);
 }
 
 }  // extern "C"

@@ -2,64 +2,18 @@
 // launch: eval_kernels.hip instantiates it for the built-in families, csrc/custom/custom_env.hip for one description
 // that is not in this tree.
 #pragma once
-#include "env_device.h"
+#include "play_episodes.h"
 
-struct OsaEvalArgs {
-  OsaNet nd;  // actor shape; nd.obs_dim = policy input width = obs_dim + saute
-  const float* params;
-  int K, obs_dim, max_steps, horizon;
-  const float *mean, *std_;
-  const long* count;
-  float clip;
-  const float *old_min, *old_max;
-  float min_a, max_a;
-  unsigned long long seed;
-  float cost_p;
+struct OsaEvalArgs : OsaPlayArgs {  // nd.obs_dim = obs_dim + saute
   int saute;
   float budget, saute_gamma;
   int early_terminated;
   double cost_limit, cost_criteria;
-  double *ep_ret, *ep_cost;
-  int* ep_len;
   float* trace;
   int rec;  // floats per trace record
-  int level;  // level of the env (a built-in one: env_kind - its family's OSA_EVAL_ENV_* constant)
 };
 
-#define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
-
 #pragma clang fp contract(off)
-// normalizer.py:104-107 with frozen statistics (osa_normalize_kernel without the mask)
-__device__ __forceinline__ float osa_eval_norm(const OsaEvalArgs& a, bool on, float v, int col) {
-  if (on) {
-    v = (v - a.mean[col]) / a.std_[col];
-    v = v < -a.clip ? -a.clip : v;  // (NaN-preserving, as osa_normalize_kernel)
-    v = v > a.clip ? a.clip : v;
-  }
-  return v;
-}
-
-// The env observation of episode k (at) into its LDS input row, lane group g taking a quarter of the columns.
-template <class E>
-__device__ __forceinline__ void osa_eval_obs(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow, int g,
-                                             const typename E::Regs& s, const float* __restrict__ srow,
-                                             const OsaEnvAt&) {
-  for (int c = g; c < a.obs_dim; c += 4) xrow[c] = osa_eval_norm(a, norm_on, E::obs_col(s, srow, a.level, c), c);
-}
-// The noise env draws its observation pair-wise: the non-truncating draw (v0, v1) of every feature pair.
-template <>
-__device__ __forceinline__ void osa_eval_obs<OsaSynthEnv>(const OsaEvalArgs& a, bool norm_on, float* __restrict__ xrow,
-                                                          int g, const OsaSynthEnv::Regs&, const float* __restrict__,
-                                                          const OsaEnvAt& at) {
-  const int D = a.obs_dim;
-  for (int pair = g; 2 * pair < D; pair += 4) {
-    float v0, v1, c2, d2;
-    osa_synth_obs_pair(at.seed, at.pos, at.n, pair, v0, v1, c2, d2);
-    xrow[2 * pair] = osa_eval_norm(a, norm_on, v0, 2 * pair);
-    if (2 * pair + 1 < D) xrow[2 * pair + 1] = osa_eval_norm(a, norm_on, v1, 2 * pair + 1);
-  }
-}
-
 // E: the family's description (env_device.h).
 template <int HT, int OT, class E>
 __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
@@ -77,12 +31,12 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
   OsaEnvAt at = {a.seed, 0, k, a.level, a.cost_p};
   float* __restrict__ srow = reinterpret_cast<float*>(osa_eval_lds) + 16 * (INP + OSA_EVAL_ACT_LD) + j * E::STATE;
   typename E::Regs s = {};
-  if constexpr (E::LDS_ROW) {
-    for (int c = OSA_NAV_DYN + g; c < E::STATE; c += 4) srow[c] = valid ? E::fresh_obj(at, c) : 0.f;
-    __syncthreads();  // the row's hazards are in LDS (the reset places the goal away from them)
-  }
+  osa_play_fresh_objects<E>(srow, g, at, valid);
+  if constexpr (E::LDS_ROW) __syncthreads();
   E::fresh(s, at, srow);
-  if (valid) osa_eval_obs<E>(a, norm_on, xrow, g, s, srow, at);
+  // the env observation of episode k, normalised, into its LDS input row
+  const auto put = [&](int c, float v) { xrow[c] = osa_play_norm(a, norm_on, v, c); };
+  if (valid) osa_play_obs<E>(a, g, s, srow, at, false, put);
   float z = 1.f;  // Saute / Simmer safety budget left (evaluator.py:415)
   if (a.saute && g == 0) xrow[a.obs_dim] = z;
   double ret = 0.0, cost = 0.0;
@@ -143,7 +97,7 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
           a.ep_len[k] = len;
         }
       } else {
-        osa_eval_obs<E>(a, norm_on, xrow, g, s, srow, at);
+        osa_play_obs<E>(a, g, s, srow, at, false, put);
         if (a.saute && g == 0) xrow[a.obs_dim] = z;
       }
     }
@@ -157,47 +111,26 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
 #pragma clang fp contract(fast)
 
 // The argument checks every entry point makes before it looks at the env.
-static inline int osa_eval_check(int K, int obs_dim, int act_dim, const float* params, const float* norm_mean,
-                                 const float* norm_std, const long* norm_count, const float* old_min,
-                                 const float* old_max, float min_action, float max_action, int horizon, int max_steps,
-                                 int saute, float saute_budget, float saute_gamma, const double* ep_ret,
-                                 const double* ep_cost, const int* ep_len) {
-  OSA_REQUIRE(K >= 1 && obs_dim >= 1 && act_dim >= 1 && max_steps >= 1 && horizon >= 1);
-  OSA_REQUIRE(params && old_min && old_max && max_action != min_action && ep_ret && ep_cost && ep_len);
-  OSA_REQUIRE((norm_mean == nullptr) == (norm_std == nullptr) && (norm_mean == nullptr) == (norm_count == nullptr));
-  OSA_REQUIRE(!saute || (saute_budget != 0.f && saute_gamma != 0.f));
+static inline int osa_eval_check(const OsaEvalArgs& a, int act_dim) {
+  const int rc = osa_play_check(a, act_dim);
+  if (rc != OSA_OK) return rc;
+  OSA_REQUIRE(!a.saute || (a.budget != 0.f && a.saute_gamma != 0.f));
   return OSA_OK;
 }
 
-// K episodes of description E at `level`, after osa_eval_check: the remaining checks, the arguments and the launch.
-// A trace record holds obs_dim (+ 1 with saute) + act_dim + 3 + E::TRACE floats.
+// K episodes of description E at a.level, after osa_eval_check: the remaining checks, the rest of the arguments (nd,
+// rec) and the launch.  A trace record holds obs_dim (+ 1 with saute) + act_dim + 3 + E::TRACE floats.
 template <class E>
-static int osa_eval_launch(int level, int K, int obs_dim, int act_dim, int hidden, const float* params,
-                           const float* norm_mean, const float* norm_std, const long* norm_count, float norm_clip,
-                           const float* old_min, const float* old_max, float min_action, float max_action,
-                           unsigned long long seed, int horizon, float cost_p, int max_steps, int saute,
-                           float saute_budget, float saute_gamma, int early_terminated, double cost_limit,
-                           double cost_criteria, double* ep_ret, double* ep_cost, int* ep_len, float* trace,
-                           void* stream) {
-  OSA_REQUIRE(obs_dim >= E::OBS && act_dim >= E::ACT);
-  const int in_w = obs_dim + (saute ? 1 : 0);
+static int osa_eval_launch(OsaEvalArgs a, int act_dim, int hidden, void* stream) {
+  OSA_REQUIRE(a.obs_dim >= E::OBS && act_dim >= E::ACT);
+  const int in_w = a.obs_dim + a.saute;
   const int rc = osa_check_dims(in_w, act_dim, hidden);
   if (rc != OSA_OK) return rc;
-  OsaEvalArgs a;
   a.nd = osa_make_net(in_w, act_dim, hidden);
   const size_t lds = (size_t)16 * (a.nd.INP + OSA_EVAL_ACT_LD + (E::LDS_ROW ? E::STATE : 0)) * sizeof(float);
   if (lds > 65536) return OSA_EUNSUPPORTED;  // policy input wider than 992 columns (928 with a 64-float state row)
-  a.params = params;
-  a.K = K; a.obs_dim = obs_dim; a.max_steps = max_steps; a.horizon = horizon;
-  a.mean = norm_mean; a.std_ = norm_std; a.count = norm_count; a.clip = norm_clip;
-  a.old_min = old_min; a.old_max = old_max; a.min_a = min_action; a.max_a = max_action;
-  a.seed = seed; a.cost_p = cost_p;
-  a.saute = saute ? 1 : 0; a.budget = saute_budget; a.saute_gamma = saute_gamma;
-  a.early_terminated = early_terminated ? 1 : 0; a.cost_limit = cost_limit; a.cost_criteria = cost_criteria;
-  a.ep_ret = ep_ret; a.ep_cost = ep_cost; a.ep_len = ep_len; a.trace = trace;
   a.rec = in_w + act_dim + 3 + E::TRACE;
-  a.level = level;
-  const dim3 grid((unsigned)((K + 15) / 16));
+  const dim3 grid((unsigned)((a.K + 15) / 16));
 #define OSA_CALL(HT, OT, NSB) \
   hipLaunchKernelGGL((osa_eval_episodes_kernel<HT, OT, E>), grid, dim3(64), lds, osa_stream(stream), a)
   OSA_DISPATCH_OT(a.nd, OSA_CALL);

@@ -29,7 +29,6 @@ Deviations from the reference, decided for parallel episodes:
 """
 from __future__ import annotations
 
-import json
 import os
 import time
 
@@ -42,18 +41,10 @@ from . import render as render_mod
 from .config import Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
-from .spaces import Box
+from .saved_policy import (DEVICE_ENVS, build_policy, choose_path, device_env_class, load_checkpoint, policy_args,
+                           scale_bounds)
 
 TIME_LIMIT = 1000  # evaluator.py:179-180
-DEVICE_ENVS = tuple(envs_mod.DeviceVectorEnv.__subclasses__())
-
-
-def _device_env_class(env_id: str):
-    """The class of a device env id -- a built-in family or one of register_device_env -- or None: what decides whether
-    the evaluator knows the env's dimensions without building it, may play it in the persistent kernel, lets its own
-    horizon end the episodes and can ask it for its state rows."""
-    cls = envs_mod.ENV_REGISTRY.get(env_id)
-    return cls if cls in DEVICE_ENVS else envs_mod.CUSTOM_ENV_REGISTRY.get(env_id)
 
 
 def _is_device_env(env) -> bool:
@@ -91,10 +82,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             render_mod.camera_index(camera_name)
         self._render_defaults = {'camera_name': camera_name or 'fixed', 'width': int(width), 'height': int(height)}
         self._save_dir, self._model_name = save_dir, model_name
-        with open(os.path.join(save_dir, 'config.json'), encoding='utf-8') as f:
-            self._dict_cfgs = json.load(f)
-        self._cfgs = Config.dict2config(self._dict_cfgs)
-        ck = torch.load(os.path.join(save_dir, 'torch_save', model_name), weights_only=False)
+        self._dict_cfgs, self._cfgs, ck = load_checkpoint(save_dir, model_name)
         self._env_id = self._cfgs.env_id
         self._env_cfgs = dict(self._dict_cfgs.get('env_cfgs') or {})
         algo = str(self._cfgs.algo)
@@ -107,19 +95,13 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         self._early_terminated = 'EarlyTerminated' in algo
         self._cost_limit = float(a.cost_limit) if self._early_terminated else 0.0
         obs_dim, act_dim = self._env_dims()
-        in_dim = obs_dim + (1 if self._saute else 0)
-        self._actor = ConstraintActorCritic(Box(-np.inf, np.inf, (in_dim,)), Box(-1.0, 1.0, (act_dim,)),
-                                            self._cfgs.model_cfgs, epochs=1, device=self._device)
-        self._actor.actor.load_state_dict(ck['pi'])
-        self._normalizer = None
-        if a.obs_normalize:  # evaluator.py:174-177
-            self._normalizer = Normalizer((obs_dim,), clip=5, device=self._device)
-            self._normalizer.load_state_dict(ck['obs_normalizer'])
+        self._actor, self._normalizer = build_policy(self._cfgs, ck, obs_dim, act_dim, self._device,
+                                                     extra_inputs=int(self._saute))
 
     def _env_dims(self) -> tuple[int, int]:
         if self._user_env is not None:
             return (int(self._user_env.observation_space.shape[0]), int(self._user_env.action_space.shape[0]))
-        cls = _device_env_class(self._env_id)
+        cls = device_env_class(self._env_id)
         if cls is not None:
             return cls.dims(self._env_id)
         env = envs_mod.make(self._env_id, num_envs=1, device=self._device, **self._env_cfgs)
@@ -130,7 +112,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     # ------------------------------------------------------------------ evaluation
     def _persistent_ok(self) -> bool:
         return (self._user_env is None and not self._actor.general
-                and _device_env_class(self._env_id) is not None)
+                and device_env_class(self._env_id) is not None)
 
     def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, trace: bool = False):
         """evaluator.py:399-490: ``(episode_rewards, episode_costs)``; ``episode_lengths`` is kept as an attribute.
@@ -139,15 +121,10 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             raise ValueError('The policy must be loaded (load_saved) before evaluating the agent.')
         num_episodes = int(num_episodes)
         assert num_episodes >= 1
-        want = os.environ.get('OSA_EVAL_PATH', '')
-        if want not in ('', 'per-step', 'persistent'):
-            raise ValueError(f'OSA_EVAL_PATH={want!r}: per-step or persistent')
-        persistent = self._persistent_ok() if want == '' else want == 'persistent'
-        if persistent and not self._persistent_ok():
-            raise _lib.OsaError('OSA_EVAL_PATH=persistent: the persistent kernel takes a fused-family actor on a '
+        self.path = choose_path('OSA_EVAL_PATH', self._persistent_ok(),
+                                'the persistent kernel takes a fused-family actor on a '
                                 f'device env (here {self._env_id}, general network: {self._actor.general})')
-        self.path = 'persistent' if persistent else 'per-step'
-        run = self._run_persistent if persistent else self._run_per_step
+        run = self._run_persistent if self.path == 'persistent' else self._run_per_step
         ret, cost, length = run(num_episodes, float(cost_criteria), trace)
         rewards, costs = ret.cpu().tolist(), cost.cpu().tolist()
         self.episode_lengths = [float(x) for x in length.cpu().tolist()]
@@ -169,12 +146,6 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         env.set_seed(self._seed)
         return env
 
-    def _scale_bounds(self, env) -> tuple[torch.Tensor, torch.Tensor]:
-        f32 = dict(dtype=torch.float32, device=self._device)
-        lo = torch.as_tensor(env.action_space.low, **f32).reshape(-1).contiguous()
-        hi = torch.as_tensor(env.action_space.high, **f32).reshape(-1).contiguous()
-        return lo, hi
-
     def _trace_floats(self, env, obs_dim: int, act_dim: int) -> int:
         if isinstance(env, envs_mod.CustomDeviceEnv):  # (include/omnisafe_amd_env.h: osa_custom_eval_episodes)
             return obs_dim + int(self._saute) + act_dim + 3 + env.trace_state_floats
@@ -186,7 +157,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         entry = env.eval_entry_point
         play = getattr(env.library(), entry)
         obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
-        lo, hi = self._scale_bounds(env)
+        lo, hi = scale_bounds(env, self._device)
         horizon = int(env.max_episode_steps)
         dev = self._device
         ret = torch.zeros(K, dtype=torch.float64, device=dev)
@@ -195,12 +166,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         tr = None
         if trace:
             tr = torch.zeros(horizon, K, self._trace_floats(env, obs_dim, act_dim), dtype=torch.float32, device=dev)
-        nm = self._normalizer
-        ac = self._actor
         _lib.check(play(
-            kind, K, obs_dim, act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(nm._mean) if nm else None,
-            _lib.ptr(nm._std) if nm else None, _lib.ptr(nm._count) if nm else None,
-            float(nm._clip_value) if nm else 0.0, _lib.ptr(lo), _lib.ptr(hi), -1.0, 1.0,
+            kind, K, *policy_args(self._actor, self._normalizer, obs_dim, act_dim, lo, hi),
             env._seed & 0xFFFFFFFFFFFFFFFF, horizon, env._cost_p, horizon,
             int(self._saute), self._budget if self._saute else 0.0, self._saute_gamma if self._saute else 0.0,
             int(self._early_terminated), self._cost_limit, cost_criteria, _lib.ptr(ret), _lib.ptr(cost),
@@ -230,8 +197,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         dev = self._device
         K = int(env.num_envs)
         obs_dim, act_dim = int(env.observation_space.shape[0]), int(env.action_space.shape[0])
-        lo, hi = self._scale_bounds(env)
-        device_env = self._user_env is None and _device_env_class(self._env_id) is not None
+        lo, hi = scale_bounds(env, self._device)
+        device_env = self._user_env is None and device_env_class(self._env_id) is not None
         max_steps = int(env.max_episode_steps) if device_env else TIME_LIMIT
         state_w = getattr(env, 'trace_state_floats', 0)  # state floats of a trace record
         f64 = dict(dtype=torch.float64, device=dev)
@@ -295,7 +262,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         opts = self._render_defaults
         width, height = int(width or opts['width']), int(height or opts['height'])
         camera = render_mod.camera_index(camera_name or opts['camera_name'])
-        cls = _device_env_class(self._env_id)
+        cls = device_env_class(self._env_id)
         if self._user_env is not None or cls is None or not (cls.trace_state_floats and cls.render_state):
             what = 'an env object given as env=' if self._user_env is not None else self._env_id
             raise ValueError(f'{what} has no state row to draw: render() takes the geometric device envs '

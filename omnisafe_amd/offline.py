@@ -39,7 +39,6 @@ an agent that finishes no episode prints nan averages where the reference divide
 """
 from __future__ import annotations
 
-import json
 import math
 import os
 import zipfile
@@ -51,8 +50,8 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import Config
-from .evaluator import TIME_LIMIT, _device_env_class
+from .evaluator import TIME_LIMIT
+from .saved_policy import build_policy, choose_path, device_env_class, load_checkpoint, policy_args, scale_bounds
 
 NOISE_KEY = 0x6A09E667F3BCC908
 AGENT_STRIDE = 0x9E3779B1  # (odd and far above any seed a user counts up from: agents of neighbouring seeds differ too)
@@ -121,7 +120,7 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
         self._num_envs = None if num_envs is None else int(num_envs)
         assert self._num_envs is None or self._num_envs >= 1
         self._env_cfgs = dict(env_cfgs or {})
-        self._cls = _device_env_class(env_name)
+        self._cls = device_env_class(env_name)
         if self._cls is not None:  # (a device env: its dimensions need neither the library nor a GPU)
             self._obs_dim, self._act_dim = self._cls.dims(env_name)
         else:
@@ -141,33 +140,17 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
     # ------------------------------------------------------------------ agents
     def register_agent(self, save_dir: str, model_name: str, size: int) -> None:
         """data_collector.py:93-143."""
-        cfg_path = os.path.join(save_dir, 'config.json')
         try:
-            with open(cfg_path, encoding='utf-8') as file:
-                kwargs = json.load(file)
+            kwargs, cfgs, model_params = load_checkpoint(save_dir, model_name)
         except FileNotFoundError as error:
-            raise FileNotFoundError('The config file is not found in the save directory.') from error
-        cfgs = Config.dict2config(kwargs)
-        model_path = os.path.join(save_dir, 'torch_save', model_name)
-        try:
-            model_params = torch.load(model_path, weights_only=False)
-        except FileNotFoundError as error:
+            if os.path.basename(str(error.filename)) == 'config.json':
+                raise FileNotFoundError('The config file is not found in the save directory.') from error
             raise FileNotFoundError(f'Model {model_name} not found in {save_dir}') from error
         algo = str(kwargs.get('algo', ''))
         if 'Saute' in algo or 'Simmer' in algo:
             raise NotImplementedError(f'{algo}: the actor of a Saute / Simmer checkpoint takes the safety column beside '
                                       'the observation; the collector plays plain policies (as the reference\'s)')
-        from .models import ConstraintActorCritic
-        from .normalizer import Normalizer
-        from .spaces import Box
-
-        actor = ConstraintActorCritic(Box(-np.inf, np.inf, (self._obs_dim,)), Box(-1.0, 1.0, (self._act_dim,)),
-                                      cfgs.model_cfgs, epochs=1, device=self._device)
-        actor.actor.load_state_dict(model_params['pi'])
-        normalizer = None
-        if cfgs.algo_cfgs.obs_normalize:
-            normalizer = Normalizer((self._obs_dim,), clip=5, device=self._device)
-            normalizer.load_state_dict(model_params['obs_normalizer'])
+        actor, normalizer = build_policy(cfgs, model_params, self._obs_dim, self._act_dim, self._device)
 
         def agent_step(obs: torch.Tensor) -> torch.Tensor:
             x = normalizer.apply(obs) if normalizer is not None else obs
@@ -191,9 +174,6 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
             assert agent.size <= self._size, f'Agent {agent} size is larger than collector size.'
             total_size += agent.size
         assert total_size == self._size, 'Sum of agent size is not equal to collector size.'
-        want = os.environ.get('OSA_COLLECT_PATH', '')
-        if want not in ('', 'per-step', 'persistent'):
-            raise ValueError(f'OSA_COLLECT_PATH={want!r}: per-step or persistent')
         S, dev = self._size, self._device
         f32 = dict(dtype=torch.float32, device=dev)
         data = {'obs': torch.zeros(S, self._obs_dim, **f32), 'action': torch.zeros(S, self._act_dim, **f32),
@@ -204,15 +184,13 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
         for i, agent in enumerate(self.agents):
             if agent.size == 0:
                 continue
-            persistent = self._persistent_ok(agent) if want == '' else want == 'persistent'
-            if persistent and not self._persistent_ok(agent):
-                raise _lib.OsaError('OSA_COLLECT_PATH=persistent: the persistent kernel takes a fused-family actor on '
+            self.path = choose_path('OSA_COLLECT_PATH', self._persistent_ok(agent),
+                                    'the persistent kernel takes a fused-family actor on '
                                     f'a device env with at most {PERSISTENT_MAX_OBS} observation columns (here '
                                     f'{self._env_name}, general network: {agent.actor.general})')
-            self.path = 'persistent' if persistent else 'per-step'
             K = self._num_envs or default_num_envs(agent.size, self._horizon())
             block = {k: v[ptx:ptx + agent.size] for k, v in data.items()}
-            run = self._run_persistent if persistent else self._run_per_step
+            run = self._run_persistent if self.path == 'persistent' else self._run_per_step
             ret, cost, count = run(agent, K, block, *agent_seeds(self._seed, i))
             # data_collector.py:178-194 with the lanes' float64 sums added up exactly
             ep_ret, ep_cost = math.fsum(ret.cpu().tolist()), math.fsum(cost.cpu().tolist())
@@ -235,31 +213,23 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
         env.set_seed(env_seed)
         return env
 
-    def _scale_bounds(self, env) -> tuple[torch.Tensor, torch.Tensor]:
-        f32 = dict(dtype=torch.float32, device=self._device)
-        lo = torch.as_tensor(env.action_space.low, **f32).reshape(-1).contiguous()
-        hi = torch.as_tensor(env.action_space.high, **f32).reshape(-1).contiguous()
-        return lo, hi
-
     def _run_persistent(self, agent: OfflineAgent, K: int, block: dict, env_seed: int, noise_seed: int):
         env = self._make_env(K, env_seed)
         entry = env.collect_entry_point
         play = getattr(env.library(), entry)
         S = agent.size
         Q, _ = lane_layout(S, K)
-        lo, hi = self._scale_bounds(env)
+        lo, hi = scale_bounds(env, self._device)
         dev = self._device
         ret = torch.zeros(K, dtype=torch.float64, device=dev)
         cost = torch.zeros(K, dtype=torch.float64, device=dev)
         count = torch.zeros(K, dtype=torch.int32, device=dev)
-        nm, ac = agent.normalizer, agent.actor
         for name in FIELDS:
             assert block[name].stride(-1) == 1
         _lib.check(play(
-            env.eval_kind(self._env_name), K, Q, S, self._obs_dim, self._act_dim, ac.hidden, _lib.ptr(ac.params),
-            _lib.ptr(nm._mean) if nm else None, _lib.ptr(nm._std) if nm else None,
-            _lib.ptr(nm._count) if nm else None, float(nm._clip_value) if nm else 0.0, _lib.ptr(lo), _lib.ptr(hi),
-            -1.0, 1.0, env_seed, noise_seed, int(env.max_episode_steps), env._cost_p,
+            env.eval_kind(self._env_name), K, Q, S,
+            *policy_args(agent.actor, agent.normalizer, self._obs_dim, self._act_dim, lo, hi), env_seed,
+            noise_seed, int(env.max_episode_steps), env._cost_p,
             _lib.ptr(block['obs']), block['obs'].stride(0), _lib.ptr(block['action']), block['action'].stride(0),
             _lib.ptr(block['reward']), _lib.ptr(block['cost']), _lib.ptr(block['next_obs']),
             block['next_obs'].stride(0), _lib.ptr(block['done']), _lib.ptr(ret), _lib.ptr(cost), _lib.ptr(count),
@@ -280,7 +250,7 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
         S = agent.size
         Q, ranges = lane_layout(S, K)
         env = self._make_env(K, env_seed)
-        lo, hi = self._scale_bounds(env)
+        lo, hi = scale_bounds(env, self._device)
         ac, nm = agent.actor, agent.normalizer
         ac.set_seed(noise_seed)  # a fresh noise stream: the (t + 1)-th step draws at position t + 1
         ac._rng_offset = 0

@@ -244,11 +244,11 @@ def test_further_ids_of_a_struct_join_its_class(glider_ids):
 
 
 def test_the_evaluator_learns_the_dimensions_from_the_class(glider_ids):
-    from omnisafe_amd import evaluator
+    from omnisafe_amd import saved_policy
 
-    assert evaluator._device_env_class('Glider1-v0') is glider_ids
-    assert evaluator._device_env_class('SynthReach-v0').__name__ == 'ReachVectorEnv'
-    assert evaluator._device_env_class('NoSuchEnv-v0') is None
+    assert saved_policy.device_env_class('Glider1-v0') is glider_ids
+    assert saved_policy.device_env_class('SynthReach-v0').__name__ == 'ReachVectorEnv'
+    assert saved_policy.device_env_class('NoSuchEnv-v0') is None
 
 
 def test_plugin_registers_the_custom_class_under_its_own_key(monkeypatch, glider_ids):

@@ -124,6 +124,8 @@ def test_library_exports_the_entry_point_and_checks_before_a_launch():
 
     lib = _lib.load()
     assert 'osa_collect_episodes' in _lib.SIGNATURES and hasattr(lib, 'osa_collect_episodes')
+    # obs_dim .. max_action: the slice saved_policy.policy_args packs for both players
+    assert _lib.SIGNATURES['osa_eval_episodes'][1][2:14] == _lib.SIGNATURES['osa_collect_episodes'][1][4:16]
     circle1 = 32 + 1
     for bad in BAD_ARGUMENTS:
         assert lib.osa_collect_episodes(circle1, *collect_args(**bad)) == -1, bad

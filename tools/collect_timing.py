@@ -1,7 +1,7 @@
 """Device time of OfflineDataCollector's persistent kernel next to the two things it can be measured against, for a
 randomly initialised PPOLag checkpoint with an active observation normaliser:
 
-    python tools/collect_timing.py [--k 4096] [--q 200] [--horizon 100] [--reps 5] [--variant-lib PATH]
+    python tools/collect_timing.py [--k 4096] [--q 200] [--horizon 100] [--reps 5] [--variant-lib PATH] [--out PATH]
 
 Per env (SynthReach-v0 and SynthNavGoal1-v0) and in ONE process, K lanes of Q rows each:
   collect    osa_collect_episodes: the whole block in one launch (rows/s, us per step of the K lanes, ns per lane-step)
@@ -10,11 +10,10 @@ Per env (SynthReach-v0 and SynthNavGoal1-v0) and in ONE process, K lanes of Q ro
              collection kernel extends, which stores nothing per step
 and collect / eval per step, beside the bytes a row adds: (2 obs_dim + act_dim + 3) * 4.
 HIP events round each call; one warm-up call, then the median of --reps.
---variant-lib: a build of the library with the row-wise store form (rows leave LDS with the wave walking along one
-    slot's row at a time) in the place of the kernel's column-strided stores
-    (tools/build_variant_lib.sh rowstores collect_kernels.hip -DOSA_COLLECT_ROW_STORES); `collect` is repeated on it in a
-    child process (OSA_LIB_PATH) and reported as `collect_row_stores`.
-Writes profiles/collect_timing.json and prints the same JSON line."""
+--variant-lib: another build of the library (a parent commit's, or one of tools/build_variant_lib.sh); `collect` is
+    repeated on it in a child process (OSA_LIB_PATH) and reported as `collect_variant` and `variant_over_collect`.
+    (profiles/collect_row_stores.json: the row-wise store form of commit 9b8c2dd measured this way.)
+Writes --out (default profiles/collect_timing.json) and prints the same JSON line."""
 from __future__ import annotations
 
 import argparse
@@ -36,6 +35,7 @@ from omnisafe_amd.config import Config, get_default_kwargs  # noqa: E402
 from omnisafe_amd.models import ConstraintActorCritic  # noqa: E402
 from omnisafe_amd.normalizer import Normalizer  # noqa: E402
 from omnisafe_amd.offline import OfflineDataCollector, agent_seeds  # noqa: E402
+from omnisafe_amd.saved_policy import policy_args, scale_bounds  # noqa: E402
 from omnisafe_amd.spaces import Box  # noqa: E402
 
 DEV = 'cuda:0'
@@ -99,18 +99,16 @@ def measure(env_id: str, obs_dim: int, act_dim: int, K: int, Q: int, horizon: in
     row['paths_equal'] = all(bool(torch.equal(kept[k], block[k])) for k in kept)
     # the deterministic kernel on the same env and K: one episode of Q steps per lane, nothing stored per step
     env = col._make_env(K, seeds[0])
-    lo, hi = col._scale_bounds(env)
-    nm, ac = agent.normalizer, agent.actor
+    lo, hi = scale_bounds(env, DEV)
     ret = torch.zeros(K, dtype=torch.float64, device=DEV)
     cost = torch.zeros(K, dtype=torch.float64, device=DEV)
     length = torch.zeros(K, dtype=torch.int32, device=DEV)
     play = getattr(env.library(), env.eval_entry_point)
 
     def evaluate():
-        _lib.check(play(env.eval_kind(env_id), K, obs_dim, act_dim, ac.hidden, _lib.ptr(ac.params), _lib.ptr(nm._mean),
-                        _lib.ptr(nm._std), _lib.ptr(nm._count), float(nm._clip_value), _lib.ptr(lo), _lib.ptr(hi), -1.0,
-                        1.0, seeds[0], Q, 0.0, Q, 0, 0.0, 0.0, 0, 0.0, 1.0, _lib.ptr(ret), _lib.ptr(cost),
-                        _lib.ptr(length), None, _lib.stream_ptr()))
+        _lib.check(play(env.eval_kind(env_id), K, *policy_args(agent.actor, agent.normalizer, obs_dim, act_dim, lo, hi),
+                        seeds[0], Q, 0.0, Q, 0, 0.0, 0.0, 0, 0.0, 1.0, _lib.ptr(ret), _lib.ptr(cost), _lib.ptr(length),
+                        None, _lib.stream_ptr()))
 
     row['eval'] = figures(median_ms(evaluate, reps), K, Q)
     assert int(length.min()) == Q
@@ -127,6 +125,7 @@ def main() -> None:
     ap.add_argument('--horizon', type=int, default=100)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--variant-lib', default='')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'collect_timing.json'))
     ap.add_argument('--only-collect', action='store_true')
     args = ap.parse_args()
     rows = [measure(env_id, D, A, args.k, args.q, args.horizon, args.reps, args.only_collect) for env_id, D, A in CASES]
@@ -142,11 +141,11 @@ def main() -> None:
             text=True, timeout=300)
         variant = json.loads(child.stdout.strip().splitlines()[-1])
         for row, other in zip(rows, variant['rows']):
-            row['collect_row_stores'] = other['collect']
-            row['row_stores_over_collect'] = round(other['collect']['ms'] / row['collect']['ms'], 3)
+            row['collect_variant'] = other['collect']
+            row['variant_over_collect'] = round(other['collect']['ms'] / row['collect']['ms'], 3)
         out['variant_lib'] = os.path.basename(args.variant_lib)
-    os.makedirs(os.path.join(ROOT, 'profiles'), exist_ok=True)
-    with open(os.path.join(ROOT, 'profiles', 'collect_timing.json'), 'w', encoding='utf-8') as f:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w', encoding='utf-8') as f:
         json.dump(out, f, indent=1)
         f.write('\n')
     print(json.dumps(out))
