@@ -1,6 +1,6 @@
 /* omnisafe_amd_env.h -- a device env of your own: the description contract and the C ABI of the library that
  * omnisafe_amd.build.build_custom_env(header, struct) makes of it (csrc/custom/custom_env.hip).  libomnisafe_amd.so
- * exports none of these symbols; every custom library exports all six.  Error codes are omnisafe_amd.h's.
+ * exports none of these symbols; every custom library exports all of them.  Error codes are omnisafe_amd.h's.
  *
  * THE DESCRIPTION is a struct of static members in a header of yours.  The header is compiled for gfx950 behind
  * csrc/env_device.h, inside a `#pragma clang fp contract(off)` region: float32, no fused multiply-adds.
@@ -33,6 +33,10 @@
  *                                                                     // the tracking camera follow
  *     static __device__ void draw(const float* rec, const OsaDrawAt&, OsaScene&);           // optional: the picture
  *                                                                     // of a state row (see DRAWING below)
+ *     static constexpr int PARAMS = P;                        // optional: P runtime parameters, 1 .. 16, and with it
+ *     static constexpr float PARAM_DEFAULT[P] = {..};         //   their values where the caller names none,
+ *     static constexpr const char* PARAM_NAMES[P] = {..};     //   their names (env_cfgs keys), and
+ *     static __device__ void bind(Regs&, const float* par);   //   what puts them into Regs (see PARAMETERS below)
  *   };
  *
  * `row` is never a pointer the description may read (nullptr in the per-step kernel): it exists for the built-in
@@ -61,6 +65,31 @@
  * obs_col() on the fresh state -- so a description needs nothing new for it; obs_col() is called for every column of
  * the row whether or not the episode ends, and the rows it gives are stored raw.
  *
+ * PARAMETERS.  A description with PARAMS computes with P floats that are no compile-time constants: every env has a
+ * row of them, drawn anew for each of its episodes.
+ *   - The caller gives every parameter a range (lo, hi), both float32, in a (2, P) device array `range` (lo = range[k],
+ *     hi = range[P + k]); lo == hi fixes the parameter.  The kernels read the array through its pointer at every reset,
+ *     so a change takes effect at each env's next reset -- also under a captured graph that keeps replaying.
+ *   - The rows live in a matrix par[N][ld_par] (ld_par >= P) of their own, not in the state: STATE, store() and trace
+ *     records are what they are without PARAMS.
+ *   - At every reset of env n at stream position pos -- the common reset, a truncation, a terminal() end -- the row is
+ *     redrawn before fresh(): parameter k from word k & 3 of osa_philox(seed ^ OSA_PARAM_KEY, pos, (n << 20) + (k >> 2))
+ *     with OSA_PARAM_KEY = 0x8CB92BA72F3D8DD7 (csrc/env_params.h), u = osa_u01(word), and without fused multiply-adds
+ *         span = hi - lo;  add = span * u;  v = fminf(lo + add, hi)
+ *     so lo == hi gives exactly lo and no value leaves [lo, hi].
+ *   - bind(s, par) copies what the description needs of par[0 .. P) into members of its Regs; every other member then
+ *     sees the parameters through Regs, its signature unchanged.  A kernel calls it after load() and again after a
+ *     redraw; load() and fresh() must leave alone the members that bind() sets.
+ *   - The order inside a step: load, bind; transition, terminal; on a truncating step final_obs (still under the ended
+ *     episode's parameters); on a reset the redraw, bind, fresh; the observation; one lane writes the redrawn row.
+ *   - The two persistent players keep the row in registers and redraw it at every in-kernel reset, at the ending
+ *     step's position like fresh(); the evaluation kernel also leaves each episode's row in a (K, P) output.
+ *   - PARAM_NAMES are the keys a caller names the parameters by (make(env_id, wind=0.3, band=(0.4, 0.8)), env_cfgs,
+ *     set_param): identifiers, distinct, and neither `horizon` nor `seed`.
+ *   - draw() gets the row of the episode it draws as OsaDrawAt::par (nullptr without PARAMS).
+ * The plain entry points of a library with PARAMS return OSA_EUNSUPPORTED (they would run with unbound parameters), and
+ * so do the parameter-taking ones of a library without; every library has both sets.
+ *
  * DRAWING.  A description with draw() can be looked at: osa_custom_render_episode rasterises frames of its state rows
  * (csrc/scene_render.h), which Evaluator.render, Agent.render, AgentGroup.render and the env's render() call.  Without
  * the member the description "does not draw": osa_custom_render_episode returns OSA_EUNSUPPORTED, and nothing else
@@ -69,8 +98,9 @@
  *     leading floats of the env's row of the state matrix.  These are the same floats (state_col(col) of a traced
  *     state is srow[col] of the stored one for col < TRACE); the per-step evaluator path relies on that already.
  *     draw() and position() may read rec[0 .. TRACE) and nothing else.
- *   - OsaDrawAt {int level; int hit; int frame;}: the level the caller names, the caller's hit[f] != 0 (the evaluator:
- *     the step into this record had a positive cost), and the record's index f.
+ *   - OsaDrawAt {int level; int hit; int frame; const float* par;}: the level the caller names, the caller's
+ *     hit[f] != 0 (the evaluator: the step into this record had a positive cost), the record's index f, and the P
+ *     parameters of the episode the record is of (PARAMETERS above; nullptr for a description without PARAMS).
  *   - draw() paints by appending primitives to the scene in painter's order (a later primitive wins); a frame starts
  *     as the background everywhere (OSA_COLOUR_OUTSIDE).  Each test is float32 without fused multiply-adds, on the
  *     sub-sample (x, y) with dx = x - ox, dy = y - oy:
@@ -97,7 +127,10 @@
  * A static_assert with a message that names the member rejects LDS_ROW == true, STATE outside 1 .. 64, ACT outside
  * 1 .. 32, TRACE > STATE, a missing member, and a member named terminal that cannot be called as stated above (it
  * would silently be an env that never ends), and likewise a member named draw that cannot be called as stated above,
- * draw without position or without DRAW_VIEW, DRAW_VIEW <= 0, and draw with TRACE == 0.
+ * draw without position or without DRAW_VIEW, DRAW_VIEW <= 0, and draw with TRACE == 0; PARAMS outside 1 .. 16, PARAMS
+ * without bind, PARAM_DEFAULT or PARAM_NAMES, either array with another length than PARAMS, a member named bind that
+ * cannot be called as stated above, and names that are no identifiers, repeat, or are `horizon` or `seed`.  A
+ * description without PARAMS is compiled as if none of this existed.
  */
 #ifndef OMNISAFE_AMD_ENV_H
 #define OMNISAFE_AMD_ENV_H
@@ -153,6 +186,45 @@ int osa_custom_render_info(int out_i[4], float out_f[2]);
 int osa_custom_render_episode(int level, const float* state, long stride, int first, int count, int trail,
                               const uint8_t* hit, int camera, int width, int height, int supersample, uint8_t* rgb,
                               void* stream);
+
+/* The runtime parameters of the description: *count = PARAMS (0 without the member); defaults (may be NULL): PARAMS
+ * floats, room for 16; names (may be NULL): PARAM_NAMES with one space between two of them and a terminating 0, in at
+ * most cap bytes -- OSA_EINVAL where they do not fit. */
+int osa_custom_param_info(int* count, float* defaults, char* names, int cap);
+
+/* The parameter-taking forms: the plain form's arguments, and in front of the stream `range` (the (2, P) ranges),
+ * `par` and `ld_par` (rows of P floats at stride ld_par >= P).  OSA_EUNSUPPORTED in a library without PARAMS (as the
+ * plain forms in a library with PARAMS), before any other check; OSA_EINVAL for a null range or par or ld_par < P.
+ *   step     par is the (N, ld_par) matrix of the envs' current rows, read and (at a reset) rewritten
+ *   eval     par receives row k of episode k: the (K, P) record of what every episode was played under
+ *   collect  par receives the row lane k holds when the launch ends
+ *   render   one row `par` of P floats (no ld_par): the parameters of the episode drawn, OsaDrawAt::par of every frame;
+ *            OSA_EINVAL for a null par */
+int osa_custom_env_step_params(unsigned long long seed, unsigned long long step, const unsigned long long* step_base,
+                               int N, int obs_dim, int horizon, int level, float* state, int* steps,
+                               const float* action, int ld_action, float* obs, int ld_obs, float* reward, float* cost,
+                               uint8_t* terminated, uint8_t* truncated, float* final_obs, int ld_final, int reset_only,
+                               const float* range, float* par, int ld_par, void* stream);
+int osa_custom_eval_episodes_params(int level, int K, int obs_dim, int act_dim, int hidden, const float* params,
+                                    const float* norm_mean, const float* norm_std, const long* norm_count,
+                                    float norm_clip, const float* old_min, const float* old_max, float min_action,
+                                    float max_action, unsigned long long seed, int horizon, float cost_p,
+                                    int max_steps, int saute, float saute_budget, float saute_gamma,
+                                    int early_terminated, double cost_limit, double cost_criteria, double* ep_ret,
+                                    double* ep_cost, int* ep_len, float* trace, const float* range, float* par,
+                                    int ld_par, void* stream);
+int osa_custom_collect_episodes_params(int level, int K, int rows_per_lane, long total_rows, int obs_dim, int act_dim,
+                                       int hidden, const float* params, const float* norm_mean, const float* norm_std,
+                                       const long* norm_count, float norm_clip, const float* old_min,
+                                       const float* old_max, float min_action, float max_action,
+                                       unsigned long long seed, unsigned long long noise_seed, int horizon,
+                                       float cost_p, float* obs, int ld_obs, float* action, int ld_act, float* reward,
+                                       float* cost, float* next_obs, int ld_next, float* done, double* ep_ret_sum,
+                                       double* ep_cost_sum, int* ep_count, const float* range, float* par, int ld_par,
+                                       void* stream);
+int osa_custom_render_episode_params(int level, const float* state, long stride, int first, int count, int trail,
+                                     const uint8_t* hit, int camera, int width, int height, int supersample,
+                                     uint8_t* rgb, const float* par, void* stream);
 
 #ifdef __cplusplus
 }

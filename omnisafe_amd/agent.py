@@ -68,21 +68,22 @@ class Agent:  # the reference exposes AlgoWrapper under this name (omnisafe/__in
         """algo_wrapper.py:172-184."""
         return self.agent.learn()
 
-    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0) -> dict:
+    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, env_params: dict | None = None) -> dict:
         """algo_wrapper.py:215-229: every ``torch_save/*.pt`` of this run, in epoch order, through
         :class:`omnisafe_amd.evaluator.Evaluator`; ``{model_name: (episode_rewards, episode_costs)}``.  Under a world
-        size > 1 only rank 0 evaluates (no collective is entered); the other ranks return ``{}``."""
+        size > 1 only rank 0 evaluates (no collective is entered); the other ranks return ``{}``.  ``env_params``:
+        ``Evaluator.evaluate``'s overlay of the run's ``env_cfgs``."""
         if dist.world_size() > 1 and dist.rank() != 0:
             return {}
         ev, log_dir = self._evaluator()
         out = {}
         for name in self._saved_models():
             ev.load_saved(save_dir=log_dir, model_name=name)
-            out[name] = ev.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria)
+            out[name] = ev.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria, env_params=env_params)
         return out
 
     def render(self, num_episodes: int = 10, render_mode: str = 'rgb_array', camera_name: str = 'track',
-               width: int = 256, height: int = 256) -> dict:
+               width: int = 256, height: int = 256, env_params: dict | None = None) -> dict:
         """algo_wrapper.py:234-269: every ``torch_save/*.pt`` of this run, in epoch order, through
         :meth:`omnisafe_amd.evaluator.Evaluator.render`; ``{model_name: save_replay_path}`` with the replays under
         ``<log_dir>/video/<model name without .pt>``.  Rank 0 only, like ``evaluate``."""
@@ -94,7 +95,7 @@ class Agent:  # the reference exposes AlgoWrapper under this name (omnisafe/__in
             ev.load_saved(save_dir=log_dir, model_name=name, render_mode=render_mode, camera_name=camera_name,
                           width=width, height=height)
             out[name] = os.path.join(log_dir, 'video', name.split('.')[0])
-            ev.render(num_episodes=num_episodes, save_replay_path=out[name])
+            ev.render(num_episodes=num_episodes, save_replay_path=out[name], env_params=env_params)
         return out
 
     def _evaluator(self):

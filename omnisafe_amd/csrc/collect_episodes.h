@@ -58,6 +58,8 @@ __global__ __launch_bounds__(64) void osa_collect_episodes_kernel(OsaCollectArgs
   typename E::Regs s = {};
   osa_play_fresh_objects<E>(srow, g, at, rows > 0);
   if constexpr (E::LDS_ROW) __syncthreads();
+  OsaParamRow<E> par;  // the running episode's parameters (a description with PARAMS), redrawn at every reset
+  osa_play_params<E>(a, s, at, par);
   E::fresh(s, at, srow);
   // the RAW env observation into the lane's LDS row being written: the reset's, then every step's next one
   float* nrow = raw + j * RW;
@@ -133,6 +135,7 @@ __global__ __launch_bounds__(64) void osa_collect_episodes_kernel(OsaCollectArgs
     }
     __syncthreads();  // the stores have read the next rows; the fresh objects are in LDS
     if (end) {
+      osa_play_params<E>(a, s, at, par);
       E::fresh(s, at, srow);
       if (live) osa_play_obs<E>(a, g, s, srow, at, true, put);  // obs of the following row: the fresh reset
     }
@@ -144,6 +147,7 @@ __global__ __launch_bounds__(64) void osa_collect_episodes_kernel(OsaCollectArgs
     a.ep_ret[k] = ret;
     a.ep_cost[k] = cost;
     a.ep_len[k] = episodes;
+    osa_play_params_out<E>(a, k, par);
   }
 }
 #pragma clang fp contract(fast)

@@ -7,6 +7,7 @@
 // instantiates for a description that is not in this tree.
 #pragma once
 #include "env_device.h"
+#include "env_params.h"
 
 struct OsaStepArgs {
   unsigned long long seed, step;
@@ -24,6 +25,15 @@ struct OsaStepArgs {
   float* final_obs;
   int ld_f, reset_only;
 };
+// The arguments of the per-step kernel of a description with runtime parameters (env_params.h): the (2, P) ranges, read
+// through the pointer at every reset, and the (N, ld_par) matrix of the envs' rows.
+struct OsaParamStepArgs : OsaStepArgs {
+  const float* range;
+  float* par;
+  int ld_par;
+};
+template <class E>
+using OsaCustomStepArgs = std::conditional_t<(OsaEnvParams<E>::value > 0), OsaParamStepArgs, OsaStepArgs>;
 
 // The stream position of the launch: the host's part and the device-resident one.
 __device__ __forceinline__ unsigned long long osa_step_pos(const OsaStepArgs& a) {
@@ -53,8 +63,9 @@ __device__ __forceinline__ void osa_step_end(const OsaStepArgs& a, int n, float 
 // The argument checks and the launch of every env entry point: `envs` envs per 64-lane workgroup, at least min_obs
 // observation columns; has_state: the env has a state matrix and takes actions, at least min_act columns of them (the
 // built-in families: two); has_level: it takes a level.
-template <class Kernel>
-static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bool has_level, const OsaStepArgs& a,
+// (Args: OsaStepArgs, or what derives from it for a kernel that takes more.)
+template <class Kernel, class Args = OsaStepArgs>
+static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bool has_level, const Args& a,
                         void* stream, int min_act = 2) {
   OSA_REQUIRE(a.N > 0 && a.D >= min_obs && (a.state || !has_state) && a.steps && a.obs && a.ld >= a.D);
   if (has_level) OSA_REQUIRE(a.level >= 0 && a.level <= 2 && (!a.final_obs || a.ld_f >= a.D));
@@ -82,6 +93,9 @@ static int osa_env_step(Kernel kernel, int min_obs, int envs, bool has_state, bo
 // the exec mask and every lane of an env takes the same side.
 // The description gets no row pointer (`row` == nullptr: its state is what load() put into Regs) and the unclamped
 // action row of the env in global memory.
+// A description with PARAMS (env_params.h) has a row of P floats per env beside the state matrix: loaded and handed to
+// bind() after load(), redrawn and bound again before fresh() at every reset -- after final_obs, which therefore shows
+// the ended episode under its own parameters -- and written back by lane 0 where it was redrawn.
 // LANES: E::LANES where the description declares it (16, 32 or 64), else 32 -- the value measured for the Circle
 // kernels (28 and 40 columns: 3.75 us against 4.55 us with 64 lanes, profiles/circle_env_timing.json) and for no other
 // shape; profiles/custom_env_timing.json has 16 / 32 / 64 for OsaReachEnv.
@@ -106,7 +120,7 @@ struct OsaEnvLevels<E, std::void_t<decltype(E::LEVELS)>> {
 
 #pragma clang fp contract(off)
 template <class E, int LANES>
-__global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaStepArgs a) {
+__global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaCustomStepArgs<E> a) {
   static_assert(!E::LDS_ROW, "osa_custom_env_kernel: the description keeps its state row in registers");
   static_assert(LANES == 16 || LANES == 32 || LANES == 64, "osa_custom_env_kernel: 16, 32 or 64 lanes per env");
   const int n = (64 / LANES) * blockIdx.x + threadIdx.x / LANES, lane = threadIdx.x % LANES;
@@ -115,6 +129,13 @@ __global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaStepArgs a) {
   float* __restrict__ srow = a.state + (long)n * E::STATE;
   typename E::Regs s;
   E::load(s, srow);
+  constexpr int P = OsaEnvParams<E>::value;
+  OsaParamRow<E> par;
+  if constexpr (P > 0) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) par.v[k] = a.par[(long)n * a.ld_par + k];
+    E::bind(s, par.v);
+  }
   uint8_t trunc = 0, term = 0;
   int count = 0;
   float r = 0.f, c = 0.f;
@@ -127,11 +148,21 @@ __global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaStepArgs a) {
       for (int k = lane; k < a.D; k += LANES)
         a.final_obs[(long)n * a.ld_f + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
   }
-  if (a.reset_only || trunc || term) E::fresh(s, at, nullptr);
+  const bool reset = a.reset_only || trunc || term;
+  if (reset) {
+    if constexpr (P > 0) osa_param_reset<E>(s, at, a.range, par);
+    E::fresh(s, at, nullptr);
+  }
   for (int k = lane; k < a.D; k += LANES)
     a.obs[(long)n * a.ld + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
   if (lane == 0) {
     E::store(s, srow);
+    if constexpr (P > 0) {
+      if (reset) {
+#pragma unroll
+        for (int k = 0; k < P; ++k) a.par[(long)n * a.ld_par + k] = par.v[k];
+      }
+    }
     osa_step_end(a, n, r, c, trunc, count, term);
   }
 }

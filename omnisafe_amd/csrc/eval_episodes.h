@@ -33,6 +33,9 @@ __global__ __launch_bounds__(64) void osa_eval_episodes_kernel(OsaEvalArgs a) {
   typename E::Regs s = {};
   osa_play_fresh_objects<E>(srow, g, at, valid);
   if constexpr (E::LDS_ROW) __syncthreads();
+  OsaParamRow<E> par;  // the episode's parameters (a description with PARAMS): drawn once, an episode keeps them
+  osa_play_params<E>(a, s, at, par);
+  if (valid && g == 0) osa_play_params_out<E>(a, k, par);
   E::fresh(s, at, srow);
   // the env observation of episode k, normalised, into its LDS input row
   const auto put = [&](int c, float v) { xrow[c] = osa_play_norm(a, norm_on, v, c); };

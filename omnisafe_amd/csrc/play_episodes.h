@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "env_device.h"
+#include "env_params.h"
 
 // An entry point fills its player's struct from its parameters; the launch completes it (nd, and what it adds itself).
 struct OsaPlayArgs {
@@ -20,6 +21,11 @@ struct OsaPlayArgs {
   double *ep_ret, *ep_cost;  // per lane
   int* ep_len;
   int level;  // level of the env (a built-in one: env_kind - its family's OSA_EVAL_ENV_* constant)
+  // a custom description with PARAMS (env_params.h), else unused: the (2, P) ranges, and where a player leaves rows of
+  // P floats at stride ld_par (the evaluation: each episode's row; the collection: each lane's last one)
+  const float* range;
+  float* par;
+  int ld_par;
 };
 
 #define OSA_EVAL_ACT_LD 32  // LDS row of the env actions (act_dim <= 32: osa_check_dims)
@@ -61,6 +67,23 @@ __device__ __forceinline__ void osa_play_obs(const OsaPlayArgs& a, int g, const 
     }
   } else {
     for (int c = g; c < a.obs_dim; c += 4) put(c, E::obs_col(s, srow, a.level, c));
+  }
+}
+
+// The parameter half of a reset at `at` (the reset at position 0, or an in-kernel one at the ending step's position),
+// before E::fresh: the episode's row is redrawn into the registers of its lanes -- the same row in the four lane groups
+// -- and bound.  Nothing without PARAMS.
+template <class E>
+__device__ __forceinline__ void osa_play_params(const OsaPlayArgs& a, typename E::Regs& s, const OsaEnvAt& at,
+                                                OsaParamRow<E>& row) {
+  if constexpr (OsaEnvParams<E>::value > 0) osa_param_reset<E>(s, at, a.range, row);
+}
+// Lane k's row to a.par (one lane per episode calls it).
+template <class E>
+__device__ __forceinline__ void osa_play_params_out(const OsaPlayArgs& a, int k, const OsaParamRow<E>& row) {
+  if constexpr (OsaEnvParams<E>::value > 0) {
+#pragma unroll
+    for (int q = 0; q < OsaEnvParams<E>::value; ++q) a.par[(long)k * a.ld_par + q] = row.v[q];
   }
 }
 

@@ -5,7 +5,7 @@
 // Mapping (render_kernels.hip's): a workgroup of 256 lanes draws 1024 consecutive row-major pixels of ONE frame, lane l
 // the 4 horizontally adjacent pixels 4 l .. 4 l + 3, one 12-byte store per lane.  Workgroups share nothing and write
 // disjoint bytes: no atomics, no flags.
-// Staging: the frame's record goes to LDS; ONE lane runs E::draw on it, which appends primitives to the OsaScene in LDS
+// Staging: the frame's record goes to LDS, and with it the episode's parameter row (a description with PARAMS); ONE lane runs E::draw on it, which appends primitives to the OsaScene in LDS
 // (kind, colour, geometry; a segment's extent and squared length computed there, once); barrier; where the scene has a
 // trail, its segments are staged in chunks of OSA_RENDER_CHUNK and collected into a per-lane bit mask; then every lane
 // walks the primitive list once, testing its 4 S^2 sub-samples against each primitive.  At every step of the walk all
@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "env_params.h"
 #include "render_common.h"
 
 #define OSA_DRAW_MAX 64  // primitives of a scene; 2 KB of LDS.  The widest built-in picture (Goal2) has 25.
@@ -23,6 +24,7 @@ struct OsaDrawAt {
   int level;  // the level the caller named
   int hit;    // the caller's hit[f] != 0 (the evaluator: the step into this record cost something)
   int frame;  // f, the index of the record
+  const float* par;  // the P parameters of the episode the record is of; nullptr for a description without PARAMS
 };
 
 enum { OSA_PRIM_DISC, OSA_PRIM_RING, OSA_PRIM_BOX, OSA_PRIM_SEGMENT, OSA_PRIM_TRAIL };
@@ -108,6 +110,7 @@ struct OsaSceneArgs {
   int level;
   int quads;  // width * height / 4
   int blocks_per_frame;
+  const float* par;  // the episode's parameter row (a description with PARAMS: P floats), else nullptr
 };
 
 #pragma clang fp contract(off)
@@ -129,10 +132,15 @@ __global__ __launch_bounds__(OSA_RENDER_THREADS) void osa_scene_render_kernel(Os
   const bool active = quad < a.quads;
   const float* __restrict__ rec = a.state + (long)f * a.stride;
   if ((int)threadIdx.x < E::TRACE) rec_s[threadIdx.x] = rec[threadIdx.x];
+  constexpr int P = OsaEnvParams<E>::value;
+  __shared__ float par_s[P > 0 ? P : 1];
+  if constexpr (P > 0) {
+    if ((int)threadIdx.x < P) par_s[threadIdx.x] = a.par[threadIdx.x];
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     scene.clear();
-    const OsaDrawAt at = {a.level, a.hit != nullptr && a.hit[f] != 0 ? 1 : 0, f};
+    const OsaDrawAt at = {a.level, a.hit != nullptr && a.hit[f] != 0 ? 1 : 0, f, P > 0 ? par_s : nullptr};
     E::draw(rec_s, at, scene);
   }
   __syncthreads();
@@ -256,12 +264,14 @@ __global__ __launch_bounds__(OSA_RENDER_THREADS) void osa_scene_render_kernel(Os
 }
 #pragma clang fp contract(fast)
 
-// osa_custom_render_episode behind its level check: osa_render_episode's argument checks, then one launch.
+// osa_custom_render_episode behind its level check: osa_render_episode's argument checks, then one launch.  par: the
+// episode's parameter row for a description with PARAMS (the caller has checked it), else nullptr.
 template <class E>
 static int osa_scene_render_launch(int level, const float* state, long stride, int first, int count, int trail,
                                    const uint8_t* hit, int camera, int width, int height, int supersample,
-                                   uint8_t* rgb, void* stream) {
-  OsaSceneArgs a = {state, stride, first, count, trail, hit, camera, width, height, rgb, level, width * height / 4, 0};
+                                   uint8_t* rgb, const float* par, void* stream) {
+  OsaSceneArgs a = {state, stride, first, count, trail, hit, camera, width, height, rgb, level, width * height / 4, 0,
+                    par};
   a.blocks_per_frame = (a.quads + OSA_RENDER_THREADS - 1) / OSA_RENDER_THREADS;
   if ((long)count * a.blocks_per_frame > 2147483647L) return OSA_EUNSUPPORTED;  // render in chunks of frames
   const dim3 grid((unsigned)((long)count * a.blocks_per_frame)), block(OSA_RENDER_THREADS);

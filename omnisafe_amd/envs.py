@@ -175,9 +175,22 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
             self._seed & 0xFFFFFFFFFFFFFFFF, self._t, _lib.ptr(self._t_base), self._num_envs, self._obs_dim,
             self._horizon, *middle, _lib.ptr(obs), self._obs_dim, _lib.ptr(self._reward), _lib.ptr(self._cost),
             _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._final), self._obs_dim, reset_only,
-            _lib.stream_ptr()), self.entry_point)
+            *self._param_args(), _lib.stream_ptr()), self.entry_point)
         self._t += 1
         return obs
+
+    def _param_args(self) -> tuple:
+        """What the entry point takes between ``reset_only`` and the stream: nothing, but for a custom class with
+        runtime parameters (range, par, ld_par)."""
+        return ()
+
+    def player_param_args(self, rows: int) -> tuple[tuple, torch.Tensor | None]:
+        """What ``eval_entry_point`` / ``collect_entry_point`` take in front of the stream, and the (rows, P) tensor the
+        player leaves parameter rows in: ``((), None)`` but for a custom class with runtime parameters."""
+        return (), None
+
+    def _render_kind(self, lane: int):
+        return self.render_kind(self._env_id)
 
     def reset(self, seed: int | None = None, options: dict | None = None):
         if seed is not None:
@@ -217,7 +230,7 @@ class DeviceEnvProtocol:  # pylint: disable=too-many-instance-attributes
 
         if not 0 <= lane < self._num_envs:
             raise IndexError(f'lane {lane} of {self._num_envs} envs')
-        frame = render_mod.rasterise(self.render_kind(self._env_id), self.state, lane * self.state_width,
+        frame = render_mod.rasterise(self._render_kind(lane), self.state, lane * self.state_width,
                                      self.state_width, 0, 1, 0, None, render_mod.camera_index(camera_name),
                                      width, height, 2)
         return frame[0].cpu().numpy()
@@ -358,7 +371,14 @@ class CustomDeviceEnv(DeviceEnvProtocol):
     whether the description has a ``terminal()`` member and ends episodes per env.  ``eval_kind`` is the level: the
     first argument of the library's osa_custom_eval_episodes.  ``draws`` (and with it ``render_state``) is what
     osa_custom_render_info reports: whether the description has a ``draw()`` member, which the library's generic scene
-    rasteriser (csrc/scene_render.h) turns into ``render()`` and ``Evaluator.render`` for the class."""
+    rasteriser (csrc/scene_render.h) turns into ``render()`` and ``Evaluator.render`` for the class.
+
+    A description with ``PARAMS`` has runtime parameters: ``param_names`` / ``param_defaults`` are the library's
+    (empty tuples otherwise), ``make(env_id, ..., wind=0.3, band=(0.4, 0.8))`` -- or the same keys in ``env_cfgs`` --
+    fixes a parameter (a number) or gives the range each env draws it from at every reset (a pair); see
+    :func:`param_ranges`.  On the env, ``params`` is the (N, P) device tensor of the envs' current rows, ``param_ranges``
+    the (2, P) device tensor of the ranges, which the kernels read through its pointer, and ``set_param`` rewrites a
+    range in place."""
 
     entry_point = 'osa_custom_env_step'
     eval_entry_point = 'osa_custom_eval_episodes'
@@ -374,8 +394,43 @@ class CustomDeviceEnv(DeviceEnvProtocol):
     lib_path: str
     lanes = 32
     max_level = 0
+    param_names: tuple = ()
+    param_defaults: tuple = ()
     _support_envs: list[str] = []
     _cdll = None
+
+    def __init__(self, env_id: str, num_envs: int = 1, device='cuda:0', horizon: int | None = None,
+                 seed: int = 0, **env_cfgs) -> None:
+        ranges = param_ranges(type(self), env_cfgs)  # (refuses before anything is allocated)
+        super().__init__(env_id, num_envs, device, horizon, seed)
+        if self.param_names:
+            self.param_ranges = torch.from_numpy(ranges).to(self._device)
+            self.params = torch.zeros(self._num_envs, len(self.param_names), dtype=torch.float32, device=self._device)
+
+    def _param_args(self) -> tuple:
+        if not self.param_names:
+            return ()
+        return _lib.ptr(self.param_ranges), _lib.ptr(self.params), self.params.stride(0)
+
+    def player_param_args(self, rows: int):
+        if not self.param_names:
+            return (), None
+        par = torch.zeros(int(rows), len(self.param_names), dtype=torch.float32, device=self._device)
+        return (_lib.ptr(self.param_ranges), _lib.ptr(par), par.stride(0)), par
+
+    def set_param(self, name: str, value) -> None:
+        """Fix parameter ``name`` (a number) or give it a range (a pair): written into ``param_ranges`` in place, on
+        the current stream, so every env takes it at its next reset -- also the envs of a rollout graph that keeps
+        replaying, whose launches read the ranges through the tensor's pointer."""
+        if name not in self.param_names:
+            raise TypeError(f'{self._env_id} has no parameter {name!r} (its parameters: {list(self.param_names)})')
+        k = self.param_names.index(name)
+        pair = param_ranges(type(self), {name: value})[:, k]
+        self.param_ranges[:, k].copy_(torch.from_numpy(pair.copy()))
+
+    def _render_kind(self, lane: int):
+        kind = self.render_kind(self._env_id)
+        return kind._replace(par=self.params[lane]) if self.param_names else kind
 
     @classmethod
     def library(cls):
@@ -396,8 +451,39 @@ class CustomDeviceEnv(DeviceEnvProtocol):
                          '(SynthReach-v0, SynthNav*-v0)')
 
 
+def param_ranges(cls, env_cfgs: dict) -> np.ndarray:
+    """The (2, P) float32 ranges ``[lo; hi]`` of a custom class's runtime parameters from the keys of ``env_cfgs``: a
+    number fixes the parameter (``lo == hi``), a pair is the range each env draws it from at every reset, an absent
+    key takes the description's default.  TypeError: a key that is neither a parameter nor ``horizon`` / ``seed``;
+    ValueError: ``lo > hi`` or a value that is not finite.  A class without parameters ignores every key, as it always
+    did, and gives a (2, 0) array.  Needs no GPU."""
+    names = tuple(getattr(cls, 'param_names', ()))
+    out = np.zeros((2, len(names)), np.float32)
+    if not names:
+        return out
+    unknown = sorted(k for k in env_cfgs if k not in names and k not in ('horizon', 'seed'))
+    if unknown:
+        raise TypeError(f'{cls.__name__} takes no env_cfgs {unknown}: its parameters are {list(names)} (besides '
+                        'horizon and seed)')
+    out[:] = np.asarray(cls.param_defaults, np.float32)
+    for k, name in enumerate(names):
+        if name not in env_cfgs:
+            continue
+        value = env_cfgs[name]
+        pair = tuple(value) if isinstance(value, (tuple, list, np.ndarray)) else (value, value)
+        if len(pair) != 2:
+            raise ValueError(f'{name}={value!r}: a number, or a pair (lo, hi)')
+        lo, hi = (np.float32(v) for v in pair)
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError(f'{name}={value!r} is not finite')
+        if lo > hi:
+            raise ValueError(f'{name}={value!r}: lo > hi')
+        out[:, k] = lo, hi
+    return out
+
+
 def _bind_custom(path: str):
-    """dlopen a custom library and declare its six prototypes (include/omnisafe_amd_env.h); returns
+    """dlopen a custom library and declare its prototypes (include/omnisafe_amd_env.h); returns
     (CDLL, info[8], (draws, OSA_DRAW_MAX, DRAW_VIEW, DRAW_TRACK))."""
     import ctypes as C
 
@@ -411,6 +497,14 @@ def _bind_custom(path: str):
     lib.osa_custom_eval_episodes.restype, lib.osa_custom_eval_episodes.argtypes = _lib.SIGNATURES['osa_eval_episodes']
     lib.osa_custom_collect_episodes.restype, lib.osa_custom_collect_episodes.argtypes = \
         _lib.SIGNATURES['osa_collect_episodes']
+    # the parameter-taking forms: range, par, ld_par (render: the episode's row) in front of the stream
+    for plain, extra in (('osa_custom_env_step', 3), ('osa_custom_eval_episodes', 3),
+                         ('osa_custom_collect_episodes', 3), ('osa_custom_render_episode', 1)):
+        fn, old = getattr(lib, plain + '_params'), getattr(lib, plain)
+        fn.restype = old.restype
+        fn.argtypes = list(old.argtypes[:-1]) + [C.c_void_p, C.c_void_p, C.c_int][:extra] + [old.argtypes[-1]]
+    lib.osa_custom_param_info.restype = C.c_int
+    lib.osa_custom_param_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_char_p, C.c_int]
     info = (C.c_int * 8)()
     _lib_code = lib.osa_custom_env_info(info)
     if _lib_code != 0:
@@ -420,6 +514,17 @@ def _bind_custom(path: str):
     if _lib_code != 0:
         raise _lib.OsaError(f'osa_custom_render_info of {path} failed ({_lib_code})')
     return lib, list(info), (bool(draw_i[0]), draw_i[1], draw_f[0], draw_f[1])
+
+
+def _custom_params(lib, path: str) -> tuple[tuple, tuple]:
+    """(names, defaults) of the runtime parameters of a bound custom library: empty tuples without PARAMS."""
+    import ctypes as C
+
+    count, defaults, names = C.c_int(), (C.c_float * 16)(), C.create_string_buffer(1024)
+    _lib_code = lib.osa_custom_param_info(C.byref(count), defaults, names, len(names))
+    if _lib_code != 0:
+        raise _lib.OsaError(f'osa_custom_param_info of {path} failed ({_lib_code})')
+    return tuple(names.value.decode().split()), tuple(float(v) for v in defaults[:count.value])
 
 
 def register_device_env(header: str, struct: str, ids, default_horizon: int = 1000) -> type:
@@ -439,6 +544,7 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
     path = _build.build_custom_env(header, struct)
     cdll, (state, obs, _dyn, act, trace, max_level, lanes, terminates), (draws, draw_max, view, track) = \
         _bind_custom(path)
+    param_names, param_defaults = _custom_params(cdll, path)
     for env_id, level in levels.items():
         if not isinstance(level, int) or not 0 <= level <= max_level:
             raise ValueError(f'{env_id}: level {level!r}, but {struct} has levels 0 .. {max_level}')
@@ -458,7 +564,11 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
             '_support_envs': list(levels), 'levels': levels, 'obs_act_dims': (obs, act), 'state_width': state,
             'trace_state_floats': trace, 'default_horizon': int(default_horizon), 'max_level': max_level,
             'lanes': lanes, 'terminates': bool(terminates), 'draws': draws, 'render_state': draws, 'draw_max': draw_max,
-            'draw_view': (view, track), 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll})
+            'draw_view': (view, track), 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll,
+            'param_names': param_names, 'param_defaults': param_defaults})
+        if param_names:  # (the plain forms of such a library refuse: they would run with unbound parameters)
+            for attr in ('entry_point', 'eval_entry_point', 'collect_entry_point'):
+                setattr(cls, attr, getattr(CustomDeviceEnv, attr) + '_params')
     for env_id in levels:
         CUSTOM_ENV_REGISTRY[env_id] = cls
     return cls

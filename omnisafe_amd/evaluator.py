@@ -68,6 +68,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         self._actor: ConstraintActorCritic | None = None
         self._normalizer: Normalizer | None = None
         self.episode_lengths: list[float] = []
+        self.episode_params = np.zeros((0, 0), np.float32)  # (K, P) of the last evaluate(): each episode's parameters
         self.path: str | None = None  # path of the last evaluate(): 'persistent' or 'per-step'
         self.render_clock: dict[str, float] = {}  # seconds of the last render(): play, raster, copy, encode
 
@@ -114,9 +115,13 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         return (self._user_env is None and not self._actor.general
                 and device_env_class(self._env_id) is not None)
 
-    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, trace: bool = False):
+    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0, trace: bool = False,
+                 env_params: dict | None = None):
         """evaluator.py:399-490: ``(episode_rewards, episode_costs)``; ``episode_lengths`` is kept as an attribute.
-        ``trace=True`` also keeps the per-step record of osa_eval_episodes as ``self.trace`` (tests)."""
+        ``trace=True`` also keeps the per-step record of osa_eval_episodes as ``self.trace`` (tests).
+        ``env_params`` overlays the run's ``env_cfgs`` for this call: the runtime parameters of a custom device env
+        (``{'wind': 0.4}``, or a pair for a range) at values the policy was not trained on.  ``episode_params`` is then
+        the (K, P) array of the parameters every episode was played under (P = 0 for an env without any)."""
         if self._actor is None:
             raise ValueError('The policy must be loaded (load_saved) before evaluating the agent.')
         num_episodes = int(num_episodes)
@@ -125,7 +130,12 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
                                 'the persistent kernel takes a fused-family actor on a '
                                 f'device env (here {self._env_id}, general network: {self._actor.general})')
         run = self._run_persistent if self.path == 'persistent' else self._run_per_step
+        self._env_overlay = dict(env_params or {})
+        self._episode_par = None  # the device rows behind episode_params
         ret, cost, length = run(num_episodes, float(cost_criteria), trace)
+        par = self._episode_par
+        self.episode_params = (np.zeros((num_episodes, 0), np.float32) if par is None
+                               else par[:num_episodes].cpu().numpy())
         rewards, costs = ret.cpu().tolist(), cost.cpu().tolist()
         self.episode_lengths = [float(x) for x in length.cpu().tolist()]
         if self._verbose:
@@ -142,7 +152,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         return rewards, costs
 
     def _make_env(self, K: int):
-        env = envs_mod.make(self._env_id, num_envs=K, device=self._device, **self._env_cfgs)
+        cfgs = dict(self._env_cfgs, **getattr(self, '_env_overlay', {}))
+        env = envs_mod.make(self._env_id, num_envs=K, device=self._device, **cfgs)
         env.set_seed(self._seed)
         return env
 
@@ -166,12 +177,13 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         tr = None
         if trace:
             tr = torch.zeros(horizon, K, self._trace_floats(env, obs_dim, act_dim), dtype=torch.float32, device=dev)
+        par_args, self._episode_par = env.player_param_args(K)
         _lib.check(play(
             kind, K, *policy_args(self._actor, self._normalizer, obs_dim, act_dim, lo, hi),
             env._seed & 0xFFFFFFFFFFFFFFFF, horizon, env._cost_p, horizon,
             int(self._saute), self._budget if self._saute else 0.0, self._saute_gamma if self._saute else 0.0,
             int(self._early_terminated), self._cost_limit, cost_criteria, _lib.ptr(ret), _lib.ptr(cost),
-            _lib.ptr(length), _lib.ptr(tr), _lib.stream_ptr()), entry)
+            _lib.ptr(length), _lib.ptr(tr), *par_args, _lib.stream_ptr()), entry)
         self.trace = tr
         env.close()
         return ret, cost, length
@@ -215,6 +227,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             tr = torch.zeros(max_steps, K, self._trace_floats(env, obs_dim, act_dim), dtype=torch.float32,
                              device=dev)
         obs, _ = env.reset()
+        if self._user_env is None and getattr(env, 'param_names', ()):  # an episode keeps the row of its reset
+            self._episode_par = env.params.clone()
         for t in range(max_steps):
             x = obs.reshape(K, obs_dim).to(dev, torch.float32)
             if self._normalizer is not None:
@@ -249,13 +263,14 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
     def render(self, num_episodes: int = 1, save_replay_path: str | None = None,  # pylint: disable=too-many-locals
                max_render_steps: int = 2000, cost_criteria: float = 1.0, *, width: int | None = None,
                height: int | None = None, camera_name: str | None = None, trail: int = 50, supersample: int = 2,
-               fps: float = 30, frame_skip: int = 1):
+               fps: float = 30, frame_skip: int = 1, env_params: dict | None = None):
         """evaluator.py:511-629: plays ``num_episodes`` episodes as ``evaluate`` does and writes, per episode k,
         ``<save_replay_path>/eval-episode-<k>.png`` (animated PNG of records 0 .. min(length, max_render_steps) - 1,
         every ``frame_skip``-th frame, 1 / fps seconds each) and ``eval-episode-<k>-path.png`` (the last of those
         records with the whole path behind it), and appends ``result.txt`` in the reference's wording.
         ``save_replay_path`` defaults to ``<save_dir>/video/<model name without .pt>``; ``width``, ``height`` and
-        ``camera_name`` ('fixed' or 'track') default to what ``load_saved`` was given.  Returns
+        ``camera_name`` ('fixed' or 'track') default to what ``load_saved`` was given; ``env_params`` is
+        ``evaluate``'s, and a description's draw() is told the parameters of the episode it draws.  Returns
         ``(episode_rewards, episode_costs)``."""
         if self._actor is None:
             raise ValueError('The policy must be loaded (load_saved) before rendering the agent.')
@@ -277,7 +292,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             print(f'Saving the replay video to {save_replay_path},\n and the result to {result_path}.')
         clock = {'play': 0.0, 'raster': 0.0, 'copy': 0.0, 'encode': 0.0}
         t0 = time.perf_counter()
-        rewards, costs = self.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria, trace=True)
+        rewards, costs = self.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria, trace=True,
+                                       env_params=env_params)
         torch.cuda.synchronize(self._device)
         clock['play'] = time.perf_counter() - t0
         tr = self.trace.contiguous()  # [T][K][rec]; a record ends with the state row before its step
@@ -289,6 +305,8 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         hit[:, 1:] = (tr[:-1, :, rec - state_w - 2] > 0).t()
         for k in range(int(num_episodes)):
             frames = int(min(self.episode_lengths[k], max_render_steps, T))
+            if self._episode_par is not None:  # (a custom class with runtime parameters: this episode's row)
+                kind = kind._replace(par=self._episode_par[k])
             at = (kind, tr, k * rec + rec - state_w, K * rec)
             chunks = render_mod.stream_frames(*at, frames, trail, hit[k], camera, width, height, supersample,
                                               frame_skip, clock)

@@ -205,12 +205,14 @@ class AgentGroup:
         self.env_steps_per_second = steps / self.wall_time
         return [m.result for m in self._members]
 
-    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0) -> list[dict]:
+    def evaluate(self, num_episodes: int = 10, cost_criteria: float = 1.0,
+                 env_params: dict | None = None) -> list[dict]:
         """``Agent.evaluate`` of every member, in member order."""
-        return [a.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria) for a in self.agents]
+        return [a.evaluate(num_episodes=num_episodes, cost_criteria=cost_criteria, env_params=env_params)
+                for a in self.agents]
 
     def render(self, num_episodes: int = 10, render_mode: str = 'rgb_array', camera_name: str = 'track',
-               width: int = 256, height: int = 256) -> list[dict]:
+               width: int = 256, height: int = 256, env_params: dict | None = None) -> list[dict]:
         """``Agent.render`` of every member, in member order."""
         return [a.render(num_episodes=num_episodes, render_mode=render_mode, camera_name=camera_name, width=width,
-                         height=height) for a in self.agents]
+                         height=height, env_params=env_params) for a in self.agents]

@@ -226,6 +226,7 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
         count = torch.zeros(K, dtype=torch.int32, device=dev)
         for name in FIELDS:
             assert block[name].stride(-1) == 1
+        par_args, _ = env.player_param_args(K)  # (a custom class with runtime parameters: its ranges)
         _lib.check(play(
             env.eval_kind(self._env_name), K, Q, S,
             *policy_args(agent.actor, agent.normalizer, self._obs_dim, self._act_dim, lo, hi), env_seed,
@@ -233,7 +234,7 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
             _lib.ptr(block['obs']), block['obs'].stride(0), _lib.ptr(block['action']), block['action'].stride(0),
             _lib.ptr(block['reward']), _lib.ptr(block['cost']), _lib.ptr(block['next_obs']),
             block['next_obs'].stride(0), _lib.ptr(block['done']), _lib.ptr(ret), _lib.ptr(cost), _lib.ptr(count),
-            _lib.stream_ptr()), entry)
+            *par_args, _lib.stream_ptr()), entry)
         env.close()
         return ret, cost, count
 

@@ -22,9 +22,11 @@ CHUNK_BYTES = 32 << 20  # device (and pinned host) bytes of a chunk of frames
 
 class CustomScene(NamedTuple):
     """In the place of an ``env_kind``: a class of ``register_device_env`` that draws (``cls.draws``) and the level
-    that its ``draw()`` is told."""
+    that its ``draw()`` is told; for a class with runtime parameters also ``par``, the float32 device row of the P
+    parameters of the episode (or the env) that is drawn, which ``draw()`` sees as ``OsaDrawAt::par``."""
     cls: type
     level: int
+    par: torch.Tensor | None = None
 
 
 def row_floats(env_kind) -> int:
@@ -43,15 +45,24 @@ def camera_index(camera_name: str) -> int:
 
 def rasterise(env_kind: int | CustomScene, rows: torch.Tensor, offset: int, stride: int, first: int, count: int,
               trail: int, hit: torch.Tensor | None, camera: int, width: int, height: int, supersample: int,
-              out: torch.Tensor | None = None) -> torch.Tensor:
+              out: torch.Tensor | None = None) -> torch.Tensor:  # pylint: disable=too-many-locals
     """Frames first .. first + count - 1 of the episode whose record f has its state row at element
     ``offset + f * stride`` of the float32 device tensor ``rows``; ``hit``: uint8[>= first + count] on the device or
     None.  Returns (a view of ``out`` as) uint8 [count, height, width, 3] on the device."""
     lib = _lib.load(require_gpu=True)
+    extra: tuple = ()
     if isinstance(env_kind, CustomScene):
         if not env_kind.cls.draws:
             raise ValueError(f'{env_kind.cls.struct} has no draw(): nothing to rasterise')
         entry, what = env_kind.cls.library().osa_custom_render_episode, env_kind.level
+        if env_kind.cls.param_names:
+            par = env_kind.par
+            if par is None:
+                raise ValueError(f'{env_kind.cls.struct} has runtime parameters: name the row to draw with '
+                                 '(CustomScene.par)')
+            assert par.dtype == torch.float32 and par.is_cuda and par.is_contiguous() \
+                and par.numel() >= len(env_kind.cls.param_names)
+            entry, extra = env_kind.cls.library().osa_custom_render_episode_params, (par.data_ptr(),)
     else:
         entry, what = lib.osa_render_episode, env_kind
     assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.is_cuda
@@ -63,7 +74,7 @@ def rasterise(env_kind: int | CustomScene, rows: torch.Tensor, offset: int, stri
         out = torch.empty(n, dtype=torch.uint8, device=rows.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n
     _lib.check(entry(int(what), rows.data_ptr() + 4 * offset, int(stride), int(first), int(count), int(trail),
-                     _lib.ptr(hit), int(camera), int(width), int(height), int(supersample), out.data_ptr(),
+                     _lib.ptr(hit), int(camera), int(width), int(height), int(supersample), out.data_ptr(), *extra,
                      _lib.stream_ptr()), entry.__name__)
     return out.reshape(-1)[:n].view(count, height, width, 3)
 
