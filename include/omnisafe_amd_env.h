@@ -6,14 +6,18 @@
  * csrc/env_device.h, inside a `#pragma clang fp contract(off)` region: float32, no fused multiply-adds.
  *
  *   struct MyEnv {
- *     static constexpr int STATE = ..;     // floats per row of the (N, STATE) state matrix, 1 .. 64
+ *     static constexpr int STATE = ..;     // floats per row of the (N, STATE) state matrix, 1 .. 64 (1 .. 256 with
+ *                                          // LDS_ROW = true)
  *     static constexpr int OBS = ..;       // observation columns, >= 1
- *     static constexpr int DYN = ..;       // leading state floats a transition changes (documentation; <= STATE)
+ *     static constexpr int DYN = ..;       // leading state floats a transition changes (<= STATE; with LDS_ROW the
+ *                                          // columns [DYN, STATE) are the objects, see OBJECT ROWS below)
  *     static constexpr int ACT = ..;       // action columns, 1 .. 32
  *     static constexpr int TRACE = ..;     // leading state floats in an evaluator trace record, <= STATE
- *     static constexpr bool LDS_ROW = false;  // must be false: the state of an env is what load() puts into Regs
+ *     static constexpr bool LDS_ROW = false;  // false: the state of an env is what load() puts into Regs; true: the
+ *                                          // row also holds objects, kept in LDS (OBJECT ROWS below)
  *     static constexpr int LEVELS = ..;    // optional: the highest level, 0 .. 2 (default 2)
  *     static constexpr int LANES = ..;     // optional: lanes per env in the per-step kernel, 16 / 32 / 64 (default 32)
+ *     static __device__ float fresh_obj(const OsaEnvAt&, int col);    // with LDS_ROW: object column col of a fresh row
  *     struct Regs { ... };                 // an aggregate: the registers that hold a state row
  *     static __device__ void load(Regs&, const float* srow);          // from the env's row of the state matrix
  *     static __device__ void store(const Regs&, float* srow);         // and back (one lane per env calls it)
@@ -39,14 +43,41 @@
  *     static __device__ void bind(Regs&, const float* par);   //   what puts them into Regs (see PARAMETERS below)
  *   };
  *
- * `row` is never a pointer the description may read (nullptr in the per-step kernel): it exists for the built-in
- * families that keep objects in LDS.  Actions arrive unclamped.  OsaEnvAt {seed, pos, n, level, cost_p} says where
+ * `row` is nullptr for a description with LDS_ROW = false, in every kernel: its state is its Regs.  With LDS_ROW = true
+ * it is the env's row in LDS, never nullptr (OBJECT ROWS below).  Actions arrive unclamped.  OsaEnvAt {seed, pos, n, level, cost_p} says where
  * the call stands: env index n at position pos of the Philox stream `seed`; draw with
  * osa_philox(seed ^ MY_KEY, pos, ((unsigned long long)n << 20) + block, w) and osa_u01(w[i]) so that the per-step
  * launches (pos = 0 for the reset, then 1, 2, ...) and the evaluation kernel (episode k = env index k) play the same
  * episodes.  fresh() of a truncating step and the transition of the same step see the same pos.  Every lane of an
  * env runs load / transition / terminal / fresh with the same inputs, so they must be deterministic functions of their
  * arguments: no atomics, no cross-lane operations, no memory but the arguments.
+ *
+ * OBJECT ROWS.  A description with LDS_ROW = true has a field of objects that a lidar and a cost loop walk: hazards,
+ * buttons, obstacles.  Its state row has up to 256 floats, of which the leading DYN are what a transition changes --
+ * what load() and store() move between the row and Regs -- and the columns [DYN, STATE) are the objects.
+ *   - The objects are written only at a reset, one call fresh_obj(at, col) per column col in [DYN, STATE), by many lanes
+ *     at once; between resets they are read-only.  fresh_obj is a function of (at, col) alone: it does not see the
+ *     runtime parameters of a description with PARAMS (they are bound into Regs, and fresh_obj gets none).
+ *   - fresh() is called after the fresh objects are in `row` and may read them (the Goal family places its goal away
+ *     from the fresh hazards this way).
+ *   - Every member that takes `const float* row` (load, fresh, transition, terminal, obs_col, state_col) gets the env's
+ *     row in LDS.  Only its columns [DYN, STATE) mean anything outside load(): the leading DYN floats are the Regs, and
+ *     the row's copy of them is stale or unwritten.  load() alone is handed a row whose leading floats are the stored
+ *     state (the per-step kernel stages the whole row first; the persistent players never call load()).
+ *   - An object may move between resets only as a closed form of the Regs (an episode step count kept in a DYN column
+ *     and a phase in the object's read-only columns, say): the cost, the lidar and draw() compute where it stands.
+ *   - state_col(col) must give what store() and fresh_obj() leave in column col of the state matrix for col < TRACE, as
+ *     for any description; read the object columns from `row`.
+ *   - terminal(), draw() with position() and DRAW_VIEW, and PARAMS with bind() combine with LDS_ROW = true exactly as
+ *     they do with register state; draw() reads the objects from `rec` (TRACE must reach them).
+ *   - The per-step kernel is osa_custom_row_env_kernel (csrc/env_frame.h): LANES lanes per env and 64 / LANES envs per
+ *     workgroup, each with a slice of STATE floats in LDS; the order inside a step is that of PARAMETERS below with
+ *     "the fresh objects" between the redraw and fresh().  OsaNavEnv<OsaPoint, OsaGoal> and OsaNavEnv<OsaCar, OsaGoal>
+ *     (csrc/env_device.h) are valid descriptions of this kind as they stand; tests/custom_envs/button.h is a task
+ *     written from scratch on the same robots.
+ *   - The persistent players keep 16 rows per workgroup in LDS behind their own buffers and return OSA_EUNSUPPORTED
+ *     where that passes 64 KB: with STATE = 256 the evaluation takes policy inputs up to 736 columns, the collection
+ *     observations up to 234.
  *
  * TERMINATION.  Every env counts the steps of its episode (steps[n]) and truncates when the count reaches `horizon`.
  * A description without terminal() never ends an episode otherwise, so its envs truncate together every `horizon`
@@ -124,8 +155,9 @@
  *   - draw() runs in one lane per workgroup, position() in many; both must be deterministic functions of `rec` (and
  *     `at`): no atomics, no cross-lane operations, no memory but the arguments.
  *
- * A static_assert with a message that names the member rejects LDS_ROW == true, STATE outside 1 .. 64, ACT outside
- * 1 .. 32, TRACE > STATE, a missing member, and a member named terminal that cannot be called as stated above (it
+ * A static_assert with a message that names the member rejects LDS_ROW == true without fresh_obj, a member named
+ * fresh_obj that cannot be called as stated above (with LDS_ROW == true), STATE outside 1 .. 64 (outside 1 .. 256 with
+ * LDS_ROW == true), DYN > STATE, ACT outside 1 .. 32, TRACE > STATE, a missing member, and a member named terminal that cannot be called as stated above (it
  * would silently be an env that never ends), and likewise a member named draw that cannot be called as stated above,
  * draw without position or without DRAW_VIEW, DRAW_VIEW <= 0, and draw with TRACE == 0; PARAMS outside 1 .. 16, PARAMS
  * without bind, PARAM_DEFAULT or PARAM_NAMES, either array with another length than PARAMS, a member named bind that
@@ -144,6 +176,10 @@ extern "C" {
 /* out[0 .. 8) = STATE, OBS, DYN, ACT, TRACE, LEVELS (the highest level), LANES, and 1 where the description has
  * terminal() (else 0).  The Python side reads every dimension from here. */
 int osa_custom_env_info(int out[8]);
+
+/* The row kind: out[0 .. 4) = 1 where the description has LDS_ROW = true (else 0), the widest STATE of that kind (256 or
+ * 64), and two reserved 0. */
+int osa_custom_row_info(int out[4]);
 
 /* One reset (reset_only != 0) or one step of N envs: the argument list and the semantics of osa_nav_env_step
  * (omnisafe_amd.h).  state is (N, STATE) float32, action (N, >= ACT) with row stride ld_action, obs (N, obs_dim >= OBS)

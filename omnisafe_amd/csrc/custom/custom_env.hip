@@ -45,7 +45,7 @@ static_assert(OsaHas_OBS<OsaCustomEnv>::value, "custom env: the description has 
 static_assert(OsaHas_DYN<OsaCustomEnv>::value, "custom env: the description has no member DYN (state floats a transition changes)");
 static_assert(OsaHas_ACT<OsaCustomEnv>::value, "custom env: the description has no member ACT (action columns)");
 static_assert(OsaHas_TRACE<OsaCustomEnv>::value, "custom env: the description has no member TRACE (state floats of a trace record)");
-static_assert(OsaHas_LDS_ROW<OsaCustomEnv>::value, "custom env: the description has no member LDS_ROW (must be false)");
+static_assert(OsaHas_LDS_ROW<OsaCustomEnv>::value, "custom env: the description has no member LDS_ROW (false: the state is the Regs; true: an object row in LDS)");
 static_assert(OsaHas_Regs<OsaCustomEnv>::value, "custom env: the description has no member struct Regs");
 
 // The functions, asked for only where what they need is there (one message per missing member, not a cascade).
@@ -94,6 +94,23 @@ template <class E, class = void>
 struct OsaNamesTerminal : std::true_type {};
 template <class E>
 struct OsaNamesTerminal<E, std::void_t<decltype(&OsaTerminalProbe<E>::terminal)>> : std::false_type {};
+
+// fresh_obj(const OsaEnvAt&, int col) -> float is what a description with LDS_ROW = true writes its object columns with;
+// a member of that name which cannot be called that way is told so (the name alone, as for terminal).
+template <class E, class = void>
+struct OsaHasFreshObj : std::false_type {};
+template <class E>
+struct OsaHasFreshObj<E, std::void_t<decltype(static_cast<float>(E::fresh_obj(std::declval<const OsaEnvAt&>(), 0)))>>
+    : std::true_type {};
+struct OsaFreshObjName {
+  int fresh_obj;
+};
+template <class E>
+struct OsaFreshObjProbe : E, OsaFreshObjName {};
+template <class E, class = void>
+struct OsaNamesFreshObj : std::true_type {};
+template <class E>
+struct OsaNamesFreshObj<E, std::void_t<decltype(&OsaFreshObjProbe<E>::fresh_obj)>> : std::false_type {};
 
 // draw() is optional in the same way (OsaHasDraw, scene_render.h), and a member of that name which cannot be called as
 // stated must not pass for "does not draw".
@@ -270,19 +287,30 @@ static_assert(OsaCustomFunctions<OsaCustomEnv>::terminal,
 template <class E, bool = OsaHas_STATE<E>::value && OsaHas_OBS<E>::value && OsaHas_DYN<E>::value &&
                           OsaHas_ACT<E>::value && OsaHas_TRACE<E>::value && OsaHas_LDS_ROW<E>::value>
 struct OsaCustomRanges {
-  static constexpr bool registers = true, state = true, obs = true, dyn = true, act = true, trace = true,
-                        complete = false;
+  static constexpr bool registers = true, fresh_obj = true, state = true, row_state = true, obs = true, dyn = true,
+                        act = true, trace = true, complete = false;
 };
 template <class E>
 struct OsaCustomRanges<E, true> {
-  static constexpr bool registers = !E::LDS_ROW, state = E::STATE >= 1 && E::STATE <= 64, obs = E::OBS >= 1,
+  // A row in LDS needs fresh_obj; a member of that name with another signature gets the message of its own alone.
+  static constexpr bool fresh_obj = !E::LDS_ROW || OsaHasFreshObj<E>::value || !OsaNamesFreshObj<E>::value,
+                        registers = !E::LDS_ROW || OsaNamesFreshObj<E>::value,
+                        state = E::LDS_ROW || (E::STATE >= 1 && E::STATE <= 64),
+                        row_state = !E::LDS_ROW || (E::STATE >= 1 && E::STATE <= OSA_ROW_STATE_MAX), obs = E::OBS >= 1,
                         dyn = E::DYN >= 0 && E::DYN <= E::STATE, act = E::ACT >= 1 && E::ACT <= 32,
                         trace = E::TRACE >= 0 && E::TRACE <= E::STATE, complete = true;
 };
 static_assert(OsaCustomRanges<OsaCustomEnv>::registers,
-              "custom env: LDS_ROW must be false (a description with an object row in LDS needs a kernel of its own, "
-              "like osa_goal_env_kernel; out-of-tree descriptions keep their state in registers)");
-static_assert(OsaCustomRanges<OsaCustomEnv>::state, "custom env: STATE must be 1 .. 64 floats");
+              "custom env: LDS_ROW must be false for a description without fresh_obj(const OsaEnvAt&, int col) (the "
+              "object columns [DYN, STATE) of a row in LDS are written by it at every reset; a description without "
+              "objects keeps its state in registers)");
+static_assert(OsaCustomRanges<OsaCustomEnv>::fresh_obj,
+              "custom env: the description has a member fresh_obj that cannot be called as float fresh_obj(const "
+              "OsaEnvAt&, int col); its object columns would never be written");
+static_assert(OsaCustomRanges<OsaCustomEnv>::state,
+              "custom env: STATE must be 1 .. 64 floats (a description with LDS_ROW = true may have up to 256)");
+static_assert(OsaCustomRanges<OsaCustomEnv>::row_state,
+              "custom env: with LDS_ROW = true STATE must be 1 .. 256 floats");
 static_assert(OsaCustomRanges<OsaCustomEnv>::obs, "custom env: OBS must be at least 1");
 static_assert(OsaCustomRanges<OsaCustomEnv>::dyn, "custom env: DYN must be 0 .. STATE");
 static_assert(OsaCustomRanges<OsaCustomEnv>::act, "custom env: ACT must be 1 .. 32 action columns");
@@ -302,8 +330,9 @@ struct OsaParamArgs {
   float* par;
   int ld_par;
 };
-template <class E, bool = OsaCustomRanges<E>::complete && OsaCustomRanges<E>::registers && OsaCustomRanges<E>::state &&
-                          OsaCustomRanges<E>::obs && OsaCustomRanges<E>::act && OsaCustomRanges<E>::trace &&
+template <class E, bool = OsaCustomRanges<E>::complete && OsaCustomRanges<E>::registers &&
+                          OsaCustomRanges<E>::fresh_obj && OsaCustomRanges<E>::state && OsaCustomRanges<E>::row_state &&
+                          OsaCustomRanges<E>::dyn && OsaCustomRanges<E>::obs && OsaCustomRanges<E>::act && OsaCustomRanges<E>::trace &&
                           OsaCustomFunctions<E>::load && OsaCustomFunctions<E>::store && OsaCustomFunctions<E>::fresh &&
                           OsaCustomFunctions<E>::obs_col && OsaCustomFunctions<E>::state_col &&
                           OsaCustomFunctions<E>::transition && OsaCustomFunctions<E>::terminal &&
@@ -311,6 +340,7 @@ template <class E, bool = OsaCustomRanges<E>::complete && OsaCustomRanges<E>::re
 struct OsaCustomLib {
   static constexpr int P = 0;
   static void info(int*) {}
+  static constexpr bool lds_row = false;
   static void param_info(float*, const char**) {}
   static int params(const OsaParamArgs*) { return OSA_EUNSUPPORTED; }
   static int step(const OsaStepArgs&, const OsaParamArgs*, void*) { return OSA_EUNSUPPORTED; }
@@ -320,6 +350,7 @@ struct OsaCustomLib {
 template <class E>
 struct OsaCustomLib<E, true> {
   static constexpr int P = OsaEnvParams<E>::value;
+  static constexpr bool lds_row = E::LDS_ROW;
   static void info(int* out) {
     const int v[8] = {E::STATE,          E::OBS,           E::DYN, E::ACT, E::TRACE,
                       OSA_CUSTOM_LEVELS, OSA_CUSTOM_LANES, OsaCustomFunctions<E>::terminates ? 1 : 0};
@@ -347,8 +378,12 @@ struct OsaCustomLib<E, true> {
       args.par = p->par;
       args.ld_par = p->ld_par;
     }
-    return osa_env_step(osa_custom_env_kernel<E, OSA_CUSTOM_LANES>, E::OBS, 64 / OSA_CUSTOM_LANES, true, true, args,
-                        stream, E::ACT);
+    if constexpr (E::LDS_ROW)
+      return osa_env_step(osa_custom_row_env_kernel<E, OSA_CUSTOM_LANES>, E::OBS, 64 / OSA_CUSTOM_LANES, true, true,
+                          args, stream, E::ACT);
+    else
+      return osa_env_step(osa_custom_env_kernel<E, OSA_CUSTOM_LANES>, E::OBS, 64 / OSA_CUSTOM_LANES, true, true, args,
+                          stream, E::ACT);
   }
   template <class Args>
   static int player(Args& a, const OsaParamArgs* p) {
@@ -498,6 +533,14 @@ int osa_custom_render_episode_params(int level, const float* state, long stride,
 int osa_custom_env_info(int* out) {
   OSA_REQUIRE(out);
   OsaCustomLib<OsaCustomEnv>::info(out);
+  return OSA_OK;
+}
+
+int osa_custom_row_info(int* out) {
+  OSA_REQUIRE(out);
+  out[0] = OsaCustomLib<OsaCustomEnv>::lds_row ? 1 : 0;
+  out[1] = OsaCustomLib<OsaCustomEnv>::lds_row ? OSA_ROW_STATE_MAX : 64;
+  out[2] = out[3] = 0;
   return OSA_OK;
 }
 

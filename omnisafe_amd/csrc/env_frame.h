@@ -3,8 +3,9 @@
 // gymnasium vector auto-reset convention (the returned obs is the post-reset obs, the pre-reset obs is handed back as
 // final_observation where the caller asks for it), what an env's first lane writes at the end, and the argument checks
 // and the launch of every entry point.  rollout_kernels.hip builds the kernels of the built-in families on it;
-// osa_custom_env_kernel below is the kernel of any register-state description, which csrc/custom/custom_env.hip
-// instantiates for a description that is not in this tree.
+// osa_custom_env_kernel below is the kernel of any register-state description and osa_custom_row_env_kernel the one of
+// any description with an object row in LDS; csrc/custom/custom_env.hip instantiates one of the two for a description
+// that is not in this tree.
 #pragma once
 #include "env_device.h"
 #include "env_params.h"
@@ -156,6 +157,97 @@ __global__ __launch_bounds__(64) void osa_custom_env_kernel(OsaCustomStepArgs<E>
   for (int k = lane; k < a.D; k += LANES)
     a.obs[(long)n * a.ld + k] = k < E::OBS ? E::obs_col(s, nullptr, a.level, k) : 0.f;
   if (lane == 0) {
+    E::store(s, srow);
+    if constexpr (P > 0) {
+      if (reset) {
+#pragma unroll
+        for (int k = 0; k < P; ++k) a.par[(long)n * a.ld_par + k] = par.v[k];
+      }
+    }
+    osa_step_end(a, n, r, c, trunc, count, term);
+  }
+}
+#pragma clang fp contract(fast)
+
+// ------------------------------------------------------------------------------------------------
+// The per-step kernel of ANY description with an object row in LDS (E::LDS_ROW == true): what osa_goal_env_kernel
+// (rollout_kernels.hip) is for OsaNavEnv<robot, OsaGoal>, with the family a template parameter.  LANES lanes per env,
+// 64 / LANES envs per 64-lane workgroup, each env with a slice of E::STATE floats of one __shared__ array:
+//   - the env's lanes stage its row from the state matrix (a strided loop), barrier;
+//   - load, bind (PARAMS); transition, terminal, the time limit; final_obs on a truncating step (never on a terminating
+//     one), by the strided column loop over E::obs_col; barrier (the columns' reads of the objects are done);
+//   - on a reset the parameters are redrawn and the env's lanes write E::fresh_obj(at, col) for col = DYN + lane,
+//     DYN + lane + LANES, ... into the LDS row and the state matrix; barrier; fresh (which may read the fresh objects);
+//   - the observation row by the same column loop, zeros past E::OBS; lane 0 stores the Regs, the redrawn parameter
+//     row, reward, cost, flags and the step counter.
+// The objects are walked per column through obs_col, as the evaluation kernel walks them, not by a lane-per-object
+// pass as in osa_goal_env_kernel: any description fits, at the price of each lane repeating the walk.
+// Every barrier stands in workgroup-uniform flow.  The envs of a workgroup may disagree about resetting (terminal(), or
+// step counters that differ) and the last workgroup of an odd N has slots without an env: both are predication around
+// the stores and the fresh_obj loop, and no lane returns early.  The lanes of a slot without an env shadow env N - 1 --
+// they read its rows and compute what its own lanes compute -- and store nothing (`live`).
+// `row` is the env's slice: columns [DYN, STATE) are the objects; [0, DYN) hold what was staged and go stale with the
+// transition (the state is the Regs).  Arithmetic: float32 without fused multiply-adds, as the description's.
+// LANES: OsaEnvLanes<E> as above -- E::LANES, else 32, which is also what was measured fastest here
+// (profiles/custom_row_env_timing.json: the Goal rows at 16 / 32 / 64 lanes, fastest at 32 in four of six cases and
+// within 5 % of the fastest in the other two; the 150-float Field 25.8 us at 32 lanes against 37 us at 16 and at 64).
+// ------------------------------------------------------------------------------------------------
+#define OSA_ROW_STATE_MAX 256  // floats of a row in LDS
+
+#pragma clang fp contract(off)
+template <class E, int LANES>
+__global__ __launch_bounds__(64) void osa_custom_row_env_kernel(OsaCustomStepArgs<E> a) {
+  static_assert(E::LDS_ROW, "osa_custom_row_env_kernel: the description keeps an object row in LDS");
+  static_assert(LANES == 16 || LANES == 32 || LANES == 64, "osa_custom_row_env_kernel: 16, 32 or 64 lanes per env");
+  static_assert(E::STATE >= 1 && E::STATE <= OSA_ROW_STATE_MAX && E::DYN >= 0 && E::DYN <= E::STATE, "row widths");
+  constexpr int ENVS = 64 / LANES;
+  __shared__ float rows[ENVS * E::STATE];
+  const int slot = threadIdx.x / LANES, lane = threadIdx.x % LANES;
+  const int n = ENVS * blockIdx.x + slot;
+  const bool live = n < a.N;
+  const int m = live ? n : a.N - 1;  // (the env whose rows this slot reads)
+  float* __restrict__ row = rows + slot * E::STATE;
+  float* __restrict__ srow = a.state + (long)m * E::STATE;
+  for (int c = lane; c < E::STATE; c += LANES) row[c] = srow[c];
+  __syncthreads();
+  const OsaEnvAt at = {a.seed, osa_step_pos(a), m, a.level, 0.f};
+  typename E::Regs s;
+  E::load(s, row);
+  constexpr int P = OsaEnvParams<E>::value;
+  OsaParamRow<E> par;
+  if constexpr (P > 0) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) par.v[k] = a.par[(long)m * a.ld_par + k];
+    E::bind(s, par.v);
+  }
+  uint8_t trunc = 0, term = 0;
+  int count = 0;
+  float r = 0.f, c = 0.f;
+  if (!a.reset_only) {  // (a kernel argument: uniform)
+    osa_env_transition<E>(s, row, at, a.action + (long)m * a.ld_a, r, c);
+    term = osa_env_terminal<E>(s, row, at) ? 1 : 0;  // (a compile-time 0 without E::terminal)
+    trunc = osa_step_trunc(a, m, count);
+    if (term) trunc = 0;  // termination wins over a time limit reached on the same step
+    if (live && trunc && a.final_obs)
+      for (int k = lane; k < a.D; k += LANES)
+        a.final_obs[(long)n * a.ld_f + k] = k < E::OBS ? E::obs_col(s, row, a.level, k) : 0.f;
+  }
+  __syncthreads();  // every read of the old objects is done
+  const bool reset = a.reset_only || trunc || term;
+  if (reset) {  // (per env: predication, no barrier inside)
+    if constexpr (P > 0) osa_param_reset<E>(s, at, a.range, par);
+    for (int col = E::DYN + lane; col < E::STATE; col += LANES) {
+      const float o = E::fresh_obj(at, col);
+      row[col] = o;
+      if (live) srow[col] = o;
+    }
+  }
+  __syncthreads();  // the fresh objects are in LDS
+  if (reset) E::fresh(s, at, row);
+  if (live)
+    for (int k = lane; k < a.D; k += LANES)
+      a.obs[(long)n * a.ld + k] = k < E::OBS ? E::obs_col(s, row, a.level, k) : 0.f;
+  if (live && lane == 0) {
     E::store(s, srow);
     if constexpr (P > 0) {
       if (reset) {

@@ -88,11 +88,13 @@ __device__ __forceinline__ void osa_play_params_out(const OsaPlayArgs& a, int k,
 }
 
 // The first half of a reset at `at` for a family with objects (LDS_ROW), which keeps the state row of its lane in LDS:
-// the fresh objects into the row (zeros for a lane that plays nothing), lane group g writing a quarter of them.  The
-// caller's barrier and E::fresh follow (the row's hazards are in LDS: the reset places the goal away from them).
+// the fresh objects into the row (zeros for a lane that plays nothing), lane group g writing a quarter of them: the
+// columns [E::DYN, E::STATE), one E::fresh_obj call each.  The caller's barrier and E::fresh follow (the row's hazards
+// are in LDS: the reset places the goal away from them).  Columns [0, E::DYN) of the LDS row are never written here:
+// they are the Regs.
 template <class E>
 __device__ __forceinline__ void osa_play_fresh_objects(float* __restrict__ srow, int g, const OsaEnvAt& at, bool on) {
   if constexpr (E::LDS_ROW)
-    for (int c = OSA_NAV_DYN + g; c < E::STATE; c += 4) srow[c] = on ? E::fresh_obj(at, c) : 0.f;
+    for (int c = E::DYN + g; c < E::STATE; c += 4) srow[c] = on ? E::fresh_obj(at, c) : 0.f;
 }
 #pragma clang fp contract(fast)

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(OSA_RENDER_THREADS) void osa_scene_render_kernel(Os
   const int quad = (blockIdx.x - local * a.blocks_per_frame) * OSA_RENDER_THREADS + threadIdx.x;
   const bool active = quad < a.quads;
   const float* __restrict__ rec = a.state + (long)f * a.stride;
-  if ((int)threadIdx.x < E::TRACE) rec_s[threadIdx.x] = rec[threadIdx.x];
+  for (int c = threadIdx.x; c < E::TRACE; c += OSA_RENDER_THREADS) rec_s[c] = rec[c];  // (TRACE reaches 256)
   constexpr int P = OsaEnvParams<E>::value;
   __shared__ float par_s[P > 0 ? P : 1];
   if constexpr (P > 0) {

@@ -371,7 +371,10 @@ class CustomDeviceEnv(DeviceEnvProtocol):
     whether the description has a ``terminal()`` member and ends episodes per env.  ``eval_kind`` is the level: the
     first argument of the library's osa_custom_eval_episodes.  ``draws`` (and with it ``render_state``) is what
     osa_custom_render_info reports: whether the description has a ``draw()`` member, which the library's generic scene
-    rasteriser (csrc/scene_render.h) turns into ``render()`` and ``Evaluator.render`` for the class.
+    rasteriser (csrc/scene_render.h) turns into ``render()`` and ``Evaluator.render`` for the class.  ``lds_row``
+    (osa_custom_row_info) is the row kind: True for a description with ``LDS_ROW = true``, whose state row (up to 256
+    floats) holds objects that the kernels keep in LDS and whose per-step kernel is the generic row kernel
+    (csrc/env_frame.h: osa_custom_row_env_kernel); nothing else about the class differs.
 
     A description with ``PARAMS`` has runtime parameters: ``param_names`` / ``param_defaults`` are the library's
     (empty tuples otherwise), ``make(env_id, ..., wind=0.3, band=(0.4, 0.8))`` -- or the same keys in ``env_cfgs`` --
@@ -387,6 +390,7 @@ class CustomDeviceEnv(DeviceEnvProtocol):
     graph_safe = True
     render_state = False  # (a state row the rasteriser has never heard of, unless the description draws it)
     draws = False
+    lds_row = False
     draw_max = 0  # OSA_DRAW_MAX of the library: the primitives a scene holds
     draw_view = (0.0, 0.0)  # DRAW_VIEW, DRAW_TRACK
     header: str
@@ -513,7 +517,19 @@ def _bind_custom(path: str):
     _lib_code = lib.osa_custom_render_info(draw_i, draw_f)
     if _lib_code != 0:
         raise _lib.OsaError(f'osa_custom_render_info of {path} failed ({_lib_code})')
+    lib.osa_custom_row_info.restype, lib.osa_custom_row_info.argtypes = C.c_int, [C.POINTER(C.c_int)]
     return lib, list(info), (bool(draw_i[0]), draw_i[1], draw_f[0], draw_f[1])
+
+
+def _custom_row(lib, path: str) -> bool:
+    """The row kind of a bound custom library (osa_custom_row_info): True for an object row in LDS."""
+    import ctypes as C
+
+    row_i = (C.c_int * 4)()
+    _lib_code = lib.osa_custom_row_info(row_i)
+    if _lib_code != 0:
+        raise _lib.OsaError(f'osa_custom_row_info of {path} failed ({_lib_code})')
+    return bool(row_i[0])
 
 
 def _custom_params(lib, path: str) -> tuple[tuple, tuple]:
@@ -544,6 +560,7 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
     path = _build.build_custom_env(header, struct)
     cdll, (state, obs, _dyn, act, trace, max_level, lanes, terminates), (draws, draw_max, view, track) = \
         _bind_custom(path)
+    lds_row = _custom_row(cdll, path)
     param_names, param_defaults = _custom_params(cdll, path)
     for env_id, level in levels.items():
         if not isinstance(level, int) or not 0 <= level <= max_level:
@@ -565,7 +582,7 @@ def register_device_env(header: str, struct: str, ids, default_horizon: int = 10
             'trace_state_floats': trace, 'default_horizon': int(default_horizon), 'max_level': max_level,
             'lanes': lanes, 'terminates': bool(terminates), 'draws': draws, 'render_state': draws, 'draw_max': draw_max,
             'draw_view': (view, track), 'header': header, 'struct': struct, 'lib_path': path, '_cdll': cdll,
-            'param_names': param_names, 'param_defaults': param_defaults})
+            'param_names': param_names, 'param_defaults': param_defaults, 'lds_row': lds_row})
         if param_names:  # (the plain forms of such a library refuse: they would run with unbound parameters)
             for attr in ('entry_point', 'eval_entry_point', 'collect_entry_point'):
                 setattr(cls, attr, getattr(CustomDeviceEnv, attr) + '_params')
