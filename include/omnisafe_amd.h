@@ -1026,6 +1026,74 @@ int osa_render_episode(int env_kind, const float* state, long stride, int first,
                        const uint8_t* hit, int camera, int width, int height, int supersample, uint8_t* rgb,
                        void* stream);
 
+/* ---- offline CRR / CCRR (csrc/crr_kernels.hip) ---------------------------------------------------------------------
+ * Critic Regularized Regression and its constrained form trained from a device-resident dataset
+ * (omnisafe/algorithms/offline/crr.py, c_crr.py).  Networks: a gaussian_learning actor (obs -> act, log_std behind the
+ * layers) and `pairs` pairs of Q critics (obs || act -> 1) with a target copy each; every network is one padded float32
+ * block in the layout of osa_gmlp_layout (W_l [out][in rounded to 4], b_l rounded to 4, ...), block strides Pa and Pc.
+ * Critic blocks in order: reward critic 0, 1, then (pairs == 2) cost critic 0, 1.  At least one hidden layer. */
+#define OSA_CRR_NSTAT 12
+/* a step's statistics row: 0 Loss_reward_critic, 1 data_Qr, 2 target_Qr, 3 Loss_cost_critic, 4 data_Qc, 5 target_Qc,
+ * 6 Loss_actor, 7 current_Qr, 8 current_Qc, 9 PolicyStd, 10 LagrangeMultiplier, 11 unused; the Q entries are FIRST-ROW
+ * values (crr.py:152-153, 187), not batch means. */
+typedef struct osa_crr_desc {
+  int obs_dim, act_dim;
+  int n_layers[2];                    /* linear layers of the actor / of a critic (hidden layers + 1) */
+  int width[2][OSA_GMLP_MAX_LAYERS];  /* output widths; the last one = act_dim / 1 */
+  int activation[2];                  /* OSA_ACT_* of the hidden layers */
+  int batch, samples, pairs;          /* B, sampled_action_num S, 1 (CRR) or 2 (CCRR) */
+} osa_crr_desc;
+typedef struct osa_crr_hparams {
+  float gamma, beta, polyak, one_minus_polyak; /* the two Polyak factors as float32 roundings of tau and 1 - tau */
+  float lr_actor, lr_critic;
+  double beta1, beta2, adam_eps; /* double: torch rounds 1 - beta to float32 from the double difference */
+  float cost_limit, lambda_lr;
+  int lagrange_open;    /* c_crr.py:181-185: epoch * steps_per_epoch > lagrange_start_step, constant over a block */
+  int reference_wiring; /* CCRR: 1 = c_crr.py as written (the reward pair takes both critic updates and values the
+                           sampled rows of the cost advantage); 0 = the cost pair has its own update */
+} osa_crr_hparams;
+typedef struct osa_crr_state {                /* device memory, 16-byte aligned blocks */
+  float *actor, *actor_m, *actor_v;           /* [Pa] */
+  float *critic, *critic_m, *critic_v;        /* [2 pairs][Pc] */
+  float* target;                              /* [2 pairs][Pc] */
+  int* adam_step;                             /* [1 + pairs]: actor, reward pair, cost pair */
+  float* lagrange;                            /* [4]: lambda, its Adam m, v and step count (CCRR) */
+  long* step;                                 /* [1] steps taken: advanced by every step on the device */
+} osa_crr_state;
+typedef struct osa_crr_data {                 /* the dataset: N rows of float32, never written */
+  const float *obs, *act, *reward, *cost, *next_obs, *done;
+  int ld_obs, ld_act, ld_next;
+  long n_rows;
+} osa_crr_data;
+typedef struct osa_crr_draw_buffers {         /* step t reads slot t % nslots */
+  const long* idx;                            /* [nslots][B] in [0, N) */
+  const float *eps_next, *eps_next_c;         /* [nslots][B][act_dim]; the second draw of c_crr.py:112 (CCRR) */
+  const float* eps_samp;                      /* [nslots][B S][act_dim] */
+  int nslots;
+} osa_crr_draw_buffers;
+/* out[0..3] = Pa, Pc, offset of log_std in the actor block, OSA_CRR_NSTAT; then (oW, ob, ld) of layers
+ * 0..OSA_GMLP_MAX_LAYERS-1 of the actor and of a critic (-1, -1, 0 for absent layers): 4 + 48 ints.  Host only. */
+int osa_crr_layout(const osa_crr_desc* desc, int* out);
+/* floats of the step's workspace; 0 for a description osa_crr_layout refuses.  Host only. */
+size_t osa_crr_ws_floats(const osa_crr_desc* desc);
+/* The draws of steps first_step .. first_step + nsteps - 1 into their slots (dataset.py:237-247's randint and the noise
+ * of actor.predict, crr.py:134, 166, c_crr.py:112), one launch per buffer: Philox4x32-10 with key seed ^ K (K: one
+ * constant per buffer), counter (step, element); idx = multiply-high of the first 64 bits into [0, n_rows); eps = the
+ * first Box-Muller normal, element = row * act_dim + d.  OSA_EINVAL before any launch for a null buffer (eps_next_c may
+ * be NULL with pairs == 1), nsteps < 1 or > nslots, n_rows < 1. */
+int osa_crr_draws(const osa_crr_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                  long n_rows, long* idx, float* eps_next, float* eps_next_c, float* eps_samp, void* stream);
+/* nsteps train steps enqueued on `stream` (crr.py:114-200 / c_crr.py:91-206 per step): gather by index, reward (and
+ * cost) critic update on TD targets from the target pair, actor update on the advantage-weighted log-likelihood with
+ * the UPDATED critics, the Lagrange step (when lagrange_open) and the Polyak updates.  No host synchronisation and no
+ * allocation; the draws' slot and the row of stats [nslots][OSA_CRR_NSTAT] follow *state->step, so a captured step
+ * advances on replay.  ws: osa_crr_ws_floats floats, 16-byte aligned.  Arguments are checked before any launch:
+ * OSA_EINVAL for null pointers, a short workspace, misaligned blocks, beta <= 0; OSA_EUNSUPPORTED for shapes
+ * osa_crr_layout refuses (no hidden layer, more than OSA_GMLP_MAX_LAYERS linear layers, B (1 + S) > 2^20). */
+int osa_crr_step(const osa_crr_desc* desc, const osa_crr_hparams* hp, const osa_crr_state* state,
+                 const osa_crr_data* data, const osa_crr_draw_buffers* draws, float* stats, float* ws, size_t ws_floats,
+                 int nsteps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

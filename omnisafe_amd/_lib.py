@@ -142,6 +142,11 @@ SIGNATURES: dict[str, tuple] = {
     'osa_collect_episodes': (_I, [_I, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _F, _F, _U, _U, _I, _F,
                                   _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     'osa_render_episode': (_I, [_I, _P, _L, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    # offline CRR / CCRR (csrc/crr_kernels.hip): structs of crr_step.py, passed by reference
+    'osa_crr_layout': (_I, [_P, _P]),
+    'osa_crr_ws_floats': (C.c_size_t, [_P]),
+    'osa_crr_draws': (_I, [_P, _U, _L, _I, _I, _L, _P, _P, _P, _P, _P]),
+    'osa_crr_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
 }
 
 

@@ -6,6 +6,9 @@ from .siblings import (CPPOPID, CUP, FOCOPS, IPO, P3O, PCPO, PDO, RCPO, TRPOPID,
                        PPOSimmerPID, TRPOSaute, TRPOSimmerPID)
 
 ALGORITHMS = {'on-policy': tuple(sorted(registry.REGISTRY._module_dict))}  # noqa: SLF001
-__all__ = ['PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
+from .offline import CCRR, CRR  # noqa: E402  (after the on-policy tuple: the registry holds both families)
+
+ALGORITHMS['offline'] = ('CCRR', 'CRR')
+__all__ = ['CRR', 'CCRR','PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
            'OnCRPO', 'CPPOPID', 'TRPOPID', 'PCPO', 'FOCOPS', 'CUP', 'P3O', 'PPOSaute', 'TRPOSaute',
            'PPOSimmerPID', 'TRPOSimmerPID', 'registry', 'ALGORITHMS']

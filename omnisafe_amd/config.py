@@ -165,10 +165,39 @@ DEFAULTS = {'PPOLag': _PPOLAG, 'TRPOLag': _TRPOLAG, 'CPO': _CPO, 'PPO': _PPO, 'T
             'PPOEarlyTerminated': _PPOET, 'TRPOEarlyTerminated': _TRPOET}
 
 
+# ---- offline family (configs/offline/CRR.yaml, CCRR.yaml `defaults` blocks).  A table of its own: DEFAULTS is the
+# on-policy family, whose entries all carry the on-policy keys.  Deviations as above: device cuda:0, use_tensorboard
+# off, the `verbose` extension.  `dataset` is a path to an .npz file here (the reference takes a name to download).
+_OFFLINE_MODEL = {
+    'weight_initialization_mode': 'kaiming_uniform',
+    'actor': {'hidden_sizes': [256, 256, 256], 'activation': 'relu', 'lr': 0.001},
+    'critic': {'hidden_sizes': [256, 256, 256], 'activation': 'relu', 'lr': 0.001},
+}
+_CRR = {
+    'seed': 0,
+    'train_cfgs': {'device': 'cuda:0', 'torch_threads': 16, 'total_steps': 1000000,
+                   'dataset': 'SafetyPointCircle1-v0_mixed_0.5', 'evaluate_epoisodes': 10, 'parallel': 1,
+                   'vector_env_nums': 1},
+    'algo_cfgs': {'gamma': 0.99, 'beta': 1, 'batch_size': 256, 'steps_per_epoch': 1000, 'phi': 0.05,
+                  'sampled_action_num': 10, 'polyak': 0.005},
+    'logger_cfgs': {'use_wandb': False, 'wandb_project': 'omnisafe', 'use_tensorboard': False,
+                    'save_model_freq': 100, 'log_dir': './runs', 'verbose': True},
+    'model_cfgs': _OFFLINE_MODEL,
+    'env_cfgs': {},
+}
+_CCRR = copy.deepcopy(_CRR)
+_CCRR['algo_cfgs']['lagrange_start_step'] = 150000
+_CCRR['lagrange_cfgs'] = {'cost_limit': 25.0, 'lagrangian_multiplier_init': 1.0, 'lambda_lr': 0.001,
+                          'lambda_optimizer': 'Adam'}
+OFFLINE_DEFAULTS = {'CRR': _CRR, 'CCRR': _CCRR}
+
+
 def get_default_kwargs(algo: str) -> dict:
     """get_default_kwargs_yaml (config.py:235-262) for the accelerated algorithms."""
+    if algo in OFFLINE_DEFAULTS:
+        return copy.deepcopy(OFFLINE_DEFAULTS[algo])
     if algo not in DEFAULTS:
-        raise KeyError(f'{algo} is not an omnisafe_amd algorithm (have {sorted(DEFAULTS)})')
+        raise KeyError(f'{algo} is not an omnisafe_amd algorithm (have {sorted(DEFAULTS) + sorted(OFFLINE_DEFAULTS)})')
     return copy.deepcopy(DEFAULTS[algo])
 
 
@@ -185,6 +214,16 @@ def recursive_check_config(config: dict, default: dict, exclude_keys=()) -> None
 def check_all_configs(cfgs: Config) -> None:
     """Subset of config.py:265-409 that guards this path."""
     a = cfgs.algo_cfgs
+    if getattr(cfgs, 'algo', None) in OFFLINE_DEFAULTS:  # the offline family has none of the on-policy keys
+        t = cfgs.train_cfgs
+        assert isinstance(a.steps_per_epoch, int) and a.steps_per_epoch > 0
+        assert isinstance(a.batch_size, int) and a.batch_size > 0
+        assert isinstance(a.sampled_action_num, int) and a.sampled_action_num > 0
+        assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0 and a.beta > 0
+        assert isinstance(t.total_steps, int) and t.total_steps > 0
+        assert isinstance(t.evaluate_epoisodes, int) and t.evaluate_epoisodes > 0
+        assert t.parallel == 1 and t.vector_env_nums == 1, 'offline only supports parallel 1 and vector_env_nums 1'
+        return
     assert isinstance(a.update_iters, int) and a.update_iters > 0, 'update_iters must be positive int'
     assert isinstance(a.steps_per_epoch, int) and a.steps_per_epoch > 0
     assert isinstance(a.batch_size, int) and a.batch_size > 0

@@ -83,7 +83,14 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
             render_mod.camera_index(camera_name)
         self._render_defaults = {'camera_name': camera_name or 'fixed', 'width': int(width), 'height': int(height)}
         self._save_dir, self._model_name = save_dir, model_name
-        self._dict_cfgs, self._cfgs, ck = load_checkpoint(save_dir, model_name)
+        self.load_policy(*load_checkpoint(save_dir, model_name)[::2])
+
+    def load_policy(self, dict_cfgs: dict, ck: dict) -> None:
+        """A policy that is not on disk (yet): a run's settings as config.json holds them and its checkpoint dict (the
+        offline algorithms' evaluation at each epoch)."""
+        if not hasattr(self, '_render_defaults'):
+            self._render_defaults = {'camera_name': 'fixed', 'width': 256, 'height': 256}
+        self._dict_cfgs, self._cfgs = dict_cfgs, Config.dict2config(dict_cfgs)
         self._env_id = self._cfgs.env_id
         self._env_cfgs = dict(self._dict_cfgs.get('env_cfgs') or {})
         algo = str(self._cfgs.algo)

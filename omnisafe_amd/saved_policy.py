@@ -43,7 +43,7 @@ def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: 
                                   cfgs.model_cfgs, epochs=1, device=device)
     actor.actor.load_state_dict(state['pi'])
     normalizer = None
-    if cfgs.algo_cfgs.obs_normalize:
+    if getattr(cfgs.algo_cfgs, 'obs_normalize', False):  # (absent in an offline run: that family has no normaliser)
         normalizer = Normalizer((obs_dim,), clip=5, device=device)
         normalizer.load_state_dict(state['obs_normalizer'])
     return actor, normalizer
