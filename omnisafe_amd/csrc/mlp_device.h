@@ -200,6 +200,25 @@ __device__ __forceinline__ float osa_adam_update(float g, float& m, float& v, fl
   return fmaf(-step_size * m, __builtin_amdgcn_rcpf(denom), w);
 }
 
+// s * inv as ONE float32 number: the average of the ranks' gradients, inv = 1 / world.  Where the clip factor between
+// the average and Adam is the compile-time constant 1 (the data-parallel chunked and split passes: clipped per rank
+// before the average) the compiler otherwise contracts the product into the first moment's difference,
+// fma(s, inv, -m), while the second moment squares the rounded product: at a world that is no power of two the two
+// moments of one step then see gradients half an ulp apart, and a step from zero moments (m = 0: the rounded product)
+// another gradient than the same step from seeded moments.  A power-of-two world is exact either way: same bits.
+__device__ __forceinline__ f32x4 osa_scale_rounded(f32x4 s, float inv) {
+#pragma clang fp contract(off)
+  f32x4 p = s * inv;
+  asm("" : "+v"(p));  // (the product is materialised here: nothing downstream can fuse into it)
+  return p;
+}
+__device__ __forceinline__ float osa_scale_rounded(float s, float inv) {
+#pragma clang fp contract(off)
+  float p = s * inv;
+  asm("" : "+v"(p));
+  return p;
+}
+
 // Four parameters at once (packed float32 math on the vector; sqrt / rcp per element).
 __device__ __forceinline__ f32x4 osa_adam_update4(f32x4 g, f32x4& m, f32x4& v, f32x4 w, float beta1,
                                                   float beta2, float step_size, float inv_bc2_sqrt,

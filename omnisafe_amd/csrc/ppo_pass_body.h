@@ -1596,12 +1596,12 @@ __device__ __forceinline__ void osa_ppo_pass_body(const OsaPassArgs& a, const in
         }
         const float invR = 1.f / (float)nranks;
 #pragma unroll
-        for (int ti = 0; ti < HT; ++ti) g2[ti] = s2[ti] * invR;
+        for (int ti = 0; ti < HT; ++ti) g2[ti] = osa_scale_rounded(s2[ti], invR);
 #pragma unroll
-        for (int kb = 0; kb < KB; ++kb) g1[kb] = s1[kb] * invR;
+        for (int kb = 0; kb < KB; ++kb) g1[kb] = osa_scale_rounded(s1[kb], invR);
 #pragma unroll
-        for (int o = 0; o < OT; ++o) g3[o] = s3[o] * invR;
-        gb = sb_ * invR;
+        for (int o = 0; o < OT; ++o) g3[o] = osa_scale_rounded(s3[o], invR);
+        gb = osa_scale_rounded(sb_, invR);
         apply_clip = false;  // clipped per rank above (clip-then-average)
         if (leader && rk == 0) {
           float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};

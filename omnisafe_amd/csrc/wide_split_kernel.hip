@@ -263,8 +263,8 @@ __device__ __forceinline__ void osa_split_dp_average(f32x4 (&g)[NT], float& gb, 
   }
   const float invW = 1.f / (float)W;
 #pragma unroll
-  for (int q = 0; q < NT; ++q) g[q] = s[q] * invW;
-  gb = sb * invW;
+  for (int q = 0; q < NT; ++q) g[q] = osa_scale_rounded(s[q], invW);
+  gb = osa_scale_rounded(sb, invW);
   DTICK(2);
 #undef DTICK
 }

@@ -33,6 +33,8 @@ twin and the kernels see the same numbers.
 `case_table()` is the table of the 64-row step (tests/test_step_oracle_gpu.py); `form_table()` that of the other forms
 of the same step -- several blocks + slab reduce, the chunked, wide and split passes, the large-batch partial
 gradients (tests/test_step_forms_gpu.py).  The twin itself is the same for all: a step of n rows is a step of n rows.
+`dp_step` (end of the file) states the data-parallel step of W ranks on top of `step` -- clip per rank, average, one
+Adam step -- and `dp_table()` is the table of its forms (tests/test_dp_twin.py, tests/test_dp_forms_gpu.py).
 
 General networks.  A case may carry `actor_hidden` / `critic_hidden` (0 to 7 hidden widths; None: [64, 64]) and
 `actor_act` / `critic_act` (ACTIVATIONS: tanh, relu, sigmoid, softplus, identity -- computed as the reference's torch
@@ -998,3 +1000,373 @@ def plan_features(plan: dict) -> set:
 def plan_kernels(plan: dict) -> set:
     """The instantiations (TM, TN, BK, AT, BT) of gm_gemm_kernel a step of this plan launches."""
     return {(q['TM'], q['TN'], q['BK'], q['AT'], q['BT']) for q in plan['launches']}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# data parallelism: the step of W ranks (tests/test_dp_twin.py on the CPU, tests/test_dp_forms_gpu.py on the device)
+# ---------------------------------------------------------------------------------------------------------------------
+# What makes W ranks different from one minibatch of W n rows (reference: every rank runs _update on ITS rows,
+# algorithms/on_policy/base/policy_gradient.py:428-445 / 468-485 / 514-524; clip_grad_norm_ comes BEFORE
+# distributed.avg_grads, policy_gradient.py:437-443; avg_grads is all_reduce(SUM) / world_size, utils/distributed.py:167-198):
+#
+#   gradient   for rank r = 0 .. W - 1 the gradient g_r of the rank's loss on ITS n rows -- every mean over n, the critics'
+#              L2 term once per rank -- exactly step()'s `grads`; its norm gives coef_r = min(1, max_grad_norm / (|g_r| + 1e-6))
+#   average    g = (1 / W) sum_r coef_r g_r, summed in rank order
+#   update     ONE Adam step on g (adam(), the step count advances by one whatever W)
+#   chunked    a rank whose minibatch is spread over 64-row chunk workgroups: g_r is the SUM of its chunks' shares (each
+#              scaled by 1 / n, the L2 and entropy terms from chunk 0 alone), THEN its norm, THEN the rank's factor
+#              (csrc/ppo_pass_body.h, `chunk_norm`) -- the same formula: a mean over n rows is a mean over n rows
+#   statistics every logged scalar is the mean over the ranks of the rank's own value (what Logger.get_stats averages):
+#              loss, mean ratio, entropy, sum p^2, the UNCLIPPED gradient norm |g_r|, MSE.  osa_dp_apply_kernel writes them
+#              to columns 0..9 and nothing to columns 10..15; the cooperative forms (osa_ppo_dp_pass_placed,
+#              osa_ppo_dp_chunked_pass -- whose chunk-0 leader forms the rank's loss and ratio as the sum of its chunks'
+#              shares and takes sum p^2 and the entropy from chunk 0 -- and osa_ppo_split_dp_pass) write the same ten
+#              columns and, per step of the launch, Adam's bias corrections float32(lr / (1 - b1^t)), float32(1 / sqrt(1 - b2^t))
+#              to columns 10 + 2 net, 11 + 2 net, as the single-rank passes do.
+#   layout     a case is make_case's data for W M rows; rank r owns rows r M .. r M + M - 1 and minibatch k of rank r is
+#              perm[r, k B:(k + 1) B] + r M (PPOUpdater.run_pass_replicated).  Extended surrogates have no DP form.
+
+
+def dp_step(state: dict, batches: list, hp: dict, lam: float, loss_kind: int, dtype=torch.float64, nets=NETS,
+            acts: dict | None = None) -> dict:
+    """One data-parallel optimiser step: `batches` holds the W ranks' minibatches (rank order).
+
+    Returns {net: {...}}: `g` the averaged clipped gradient per reference tensor, p' / m' / v' / t / step_size /
+    inv_bc2_sqrt of the ONE Adam step on it, every scalar of SCALARS (and the critics' `loss`) as the mean over the ranks,
+    `coefs` / `gnorms` the ranks' factors and unclipped norms, `ranks` the W results of step()."""
+    W = len(batches)
+    ranks = [step(state, b, hp, lam, loss_kind, None, dtype, nets, acts) for b in batches]
+    full = dict(DEFAULT_HP, **hp)
+    f = {k: _f32(full[k]) for k in ('lr_actor', 'lr_critic', 'beta1', 'beta2', 'adam_eps')}
+    as_t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)  # noqa: E731
+    out = {}
+    for net in nets:
+        g = OrderedDict()
+        for k in ranks[0][net]['grads']:
+            acc = None
+            for r in ranks:
+                term = r[net]['grads'][k] * r[net]['coef']
+                acc = term if acc is None else acc + term
+            g[k] = acc / W
+        lr = f['lr_actor' if net == 'actor' else 'lr_critic']
+        t = int(state['t'][net]) + 1
+        new_p, new_m, new_v = OrderedDict(), OrderedDict(), OrderedDict()
+        for k, gk in g.items():
+            new_p[k], new_m[k], new_v[k] = adam(as_t(state['params'][net][k]), as_t(state['m'][net][k]),
+                                                as_t(state['v'][net][k]), gk, lr, f['beta1'], f['beta2'], f['adam_eps'], t)
+        ss, ib = bias_corrections(lr, f['beta1'], f['beta2'], t)
+        res = dict(g=g, p=new_p, m=new_m, v=new_v, t=t, step_size=ss, inv_bc2_sqrt=ib, ranks=[r[net] for r in ranks],
+                   coefs=[float(r[net]['coef']) for r in ranks], gnorms=[float(r[net]['gnorm']) for r in ranks])
+        for sc in SCALARS[net] + (() if net == 'actor' else ('loss',)):
+            acc = None
+            for r in ranks:
+                acc = r[net][sc] if acc is None else acc + r[net][sc]
+            res[sc] = acc / W
+        out[net] = res
+    return out
+
+
+def dp_minibatch(case: dict, k: int, orders=None) -> list:
+    """The W ranks' row indices of minibatch k (`orders`: per rank another order of its rows -- the same step)."""
+    s, n = minibatches(case['M'], case['B'])[k]
+    idx = [case['perm'][r, s:s + n] + r * case['M'] for r in range(case['W'])]
+    return idx if orders is None else [i[o] for i, o in zip(idx, orders)]
+
+
+def dp_case_step(case: dict, state: dict, k: int, dtype=torch.float64, orders=None) -> dict:
+    """Minibatch k of the case's data-parallel pass, taken from `state`."""
+    return dp_step(state, [rows(case['data'], i) for i in dp_minibatch(case, k, orders)], case['hp'], case['lam'],
+                   case['loss_kind'], dtype, case_nets(case), case_acts(case))
+
+
+def dp_run_pass(case: dict, dtype=torch.float64, state: dict | None = None) -> tuple:
+    """The whole data-parallel pass: ceil(M / B) dependent steps -> ([step results], final state)."""
+    state = case['state'] if state is None else state
+    res = []
+    for k in range(len(minibatches(case['M'], case['B']))):
+        res.append(dp_case_step(case, state, k, dtype))
+        state = advance(state, res[-1])
+    return res, state
+
+
+def make_dp_case(obs_dim: int, act_dim: int, W: int, B: int, M: int, *, norm_clip=None, **kw) -> dict:
+    """A data-parallel case: make_case's inputs for W M rows (every stream of make_case as it is), laid out rank by rank.
+
+    layout     position j of rank r's pass takes the row make_case put at position r M + j of ITS pass, so a minibatch of
+               a rank is a run of consecutive positions and holds the six clip cells as make_case arranged them; inside
+               the rank's M rows the rows sit in a seeded random order (`perm`, (W, M), drawn from a stream of its own)
+    ranks      rank r's targets and advantages are multiplied by float32(1 + r / W) after everything is drawn: the
+               ranks' gradient norms differ by tens of percent, so a factor taken from another rank, from the mean of
+               the ranks or from the averaged gradient is a visible error (tests/test_dp_twin.py computes each)
+    norm_clip  None: max_grad_norm = 1000 bites on no rank;  ('straddle', net): the geometric mean of the two middle
+               per-rank float64 norms of that network on the first minibatch -- half the ranks clip, half do not (an
+               odd world has a middle pair on either side of its median rank: the pair that lies further apart);
+               ('all', 0.5): half the smallest norm of any rank and network on the first minibatch -- every rank clips
+    """
+    assert kw.get('ext') is None and W >= 1
+    case = make_case(obs_dim, act_dim, B, W * M, norm_clip=None, **kw)
+    rs = np.random.RandomState(770077 + 131 * obs_dim + 17 * act_dim + 7 * B + M + 1009 * W + kw.get('seed', 0))
+    perm = np.stack([rs.permutation(M) for _ in range(W)]).astype(np.int64)
+    src = np.empty(W * M, np.int64)
+    for r in range(W):
+        src[r * M + perm[r]] = case['perm'][r * M:(r + 1) * M]
+    data = {k: np.ascontiguousarray(np.asarray(v)[src]) for k, v in case['data'].items()}
+    for r in range(W):
+        fac = F32(1.0 + r / W)
+        for k in ('target_value_r', 'target_value_c', 'adv_r', 'adv_c'):
+            data[k][r * M:(r + 1) * M] *= fac
+    case.update(W=int(W), M=int(M), perm=perm, data=data, norm_clip=norm_clip)
+    if norm_clip is not None:
+        which, arg = norm_clip
+        r0 = dp_case_step(dict(case, update_actor=True, update_critics=True, use_cost=True), case['state'], 0)
+        if which == 'straddle':
+            assert W >= 2
+            norms = sorted(r0[arg]['gnorms'])
+            # (an odd world has two middle pairs, below and above the median rank: the one with the wider gap)
+            lo, hi = max(((norms[i], norms[i + 1]) for i in {(W - 2) // 2, (W - 1) // 2}), key=lambda p: p[1] / p[0])
+            case['hp']['max_grad_norm'] = _f32(math.sqrt(lo * hi))
+        else:
+            assert which == 'all'
+            case['hp']['max_grad_norm'] = _f32(arg * min(min(r0[net]['gnorms']) for net in NETS))
+        case['norms0'] = {net: r0[net]['gnorms'] for net in NETS}
+    return case
+
+
+def dp_check_coverage(case: dict) -> dict:
+    """Asserts that the case reaches what it is in the table for.  At the case's INITIAL state, where the GPU tests take
+    every minibatch's gradient: every rank's every minibatch holds its clip cells with every ratio at least 1e-3 from
+    the clip edges (float32 and float64 take the same branch), as check_coverage asks of a single rank; a case with
+    seeded moments, whose float64 CHAIN the GPU tests compare, meets the same along the chain.  A case without
+    norm_clip clips on no rank anywhere.  A clipped case, on its first minibatch (the one max_grad_norm was placed
+    on; a tail of a few rows has norms of its own, and tests/test_dp_twin.py holds every minibatch to the
+    right-from-wrong condition instead):
+      ('straddle', net)  at least one rank of that network with coef <= 0.95 and at least one with norm <= 0.95 max_grad_norm
+      ('all', .)         every rank of every network the case updates has coef < 1."""
+    clip = _f32(case['hp']['clip'])
+    info = {'edge': np.inf, 'coefs': []}
+    seen = set()
+    nmb = len(minibatches(case['M'], case['B']))
+    first = [dp_case_step(case, case['state'], k) for k in range(nmb)]
+    chain = dp_run_pass(case)[0]
+    for k, r in enumerate(first + (chain if case['seeded_moments'] else [])):
+        if 'actor' in r:
+            for a in r['actor']['ranks']:
+                ratio, adv = a['ratio'].numpy(), a['adv'].numpy()
+                edge = np.minimum(np.abs(ratio - (1 - clip)), np.abs(ratio - (1 + clip))).min()
+                info['edge'] = min(info['edge'], float(edge))
+                assert edge >= 1e-3 and np.abs(adv).min() > 0, (k, edge)
+                rng = np.where(ratio < 1 - clip, 0, np.where(ratio > 1 + clip, 2, 1))
+                cells = {(int(g), bool(s)) for g, s in zip(rng, adv > 0)}
+                assert len(cells) == min(len(ratio), 6), (k, sorted(cells))
+                seen |= cells
+    if case['update_actor']:
+        assert len(seen) == 6, sorted(seen)
+    mg = _f32(case['hp']['max_grad_norm'])
+    if case['norm_clip'] is None:
+        if case['hp']['use_max_grad_norm']:
+            assert all(c == 1.0 for r in chain + first for net in r for c in r[net]['coefs'])
+    else:
+        which, arg = case['norm_clip']
+        for k, r in enumerate(first):
+            for net in r:
+                info['coefs'].append((k, net, [round(c, 3) for c in r[net]['coefs']]))
+        for net, r in first[0].items():
+            if which == 'all':
+                assert all(c < 1.0 for c in r['coefs']), (net, r['coefs'])
+            elif net == arg:
+                assert min(r['coefs']) <= 0.95 and min(r['gnorms']) <= 0.95 * mg, (net, r['coefs'], r['gnorms'], mg)
+    if case.get('w1_scale', 1.0) != 1.0:
+        info['saturated'] = first_layer_saturation(case)
+        assert max(info['saturated'].values()) <= 0.02, info['saturated']
+    return info
+
+
+def dp_wrong_statements(case: dict, k: int, state: dict | None = None) -> dict:
+    """{what: {net: {tensor: gradient}}}: statements of minibatch k's averaged gradient that are NOT the data-parallel
+    step, in float64, next to 'right' -- what a kernel would compute that
+      clip-after-average   averaged the unclipped gradients and clipped the average by its own norm
+      mean-factor          applied the mean of the ranks' factors to every rank
+      next-rank-factor     applied rank (r + 1 mod W)'s factor to rank r
+      sum                  summed the clipped gradients without dividing by W
+      tail-over-B          (a minibatch of n < B rows) divided the ranks' row sums by B: the data term of every rank's
+                           gradient (everything but the critics' L2 term 2 c p) x n / B, norms and factors from that."""
+    state = case['state'] if state is None else state
+    r = dp_case_step(case, state, k)
+    hp = dict(DEFAULT_HP, **case['hp'])
+    mg, use = _f32(hp['max_grad_norm']), bool(hp['use_max_grad_norm'])
+    W, (_, n) = case['W'], minibatches(case['M'], case['B'])[k]
+
+    def factor(norm):
+        return min(1.0, mg / (float(norm) + 1e-6)) if use else 1.0
+
+    def norm_of(g):
+        return math.sqrt(sum(float((x * x).sum()) for x in g.values()))
+
+    out = {w: {} for w in ('right', 'clip-after-average', 'mean-factor', 'next-rank-factor', 'sum')}
+    if n < case['B']:
+        out['tail-over-B'] = {}
+    for net, res in r.items():
+        gr = [rk['grads'] for rk in res['ranks']]
+        c = res['coefs']
+        avg = lambda coefs, grads=gr: OrderedDict((t, sum(cf * g[t] for cf, g in zip(coefs, grads)) / W) for t in grads[0])  # noqa: E731
+        out['right'][net] = res['g']
+        plain = avg([1.0] * W)
+        fa = factor(norm_of(plain))
+        out['clip-after-average'][net] = OrderedDict((t, fa * x) for t, x in plain.items())
+        out['mean-factor'][net] = avg([sum(c) / W] * W)
+        out['next-rank-factor'][net] = avg([c[(i + 1) % W] for i in range(W)])
+        out['sum'][net] = OrderedDict((t, W * x) for t, x in res['g'].items())
+        if n < case['B']:
+            l2 = (2.0 * _f32(hp['critic_norm_coef'])) if (net != 'actor' and hp['use_critic_norm']) else 0.0
+            p = state['params'][net]
+            wrong = []
+            for g in gr:
+                reg = {t: l2 * torch.as_tensor(np.asarray(p[t], np.float64)) for t in g}
+                wrong.append(OrderedDict((t, (g[t] - reg[t]) * (n / case['B']) + reg[t]) for t in g))
+            out['tail-over-B'][net] = avg([factor(norm_of(g)) for g in wrong], wrong)
+    return out
+
+
+def dp_state_tolerances(r: dict, units: dict, net: str, k_grad: float) -> dict:
+    """state_tolerances of tests/test_step_oracle_gpu.py for a data-parallel step.  There the clipped gradient is the
+    unclipped one times ONE factor, both observed, and the factor's own tolerance (`ec`) is added to the gradient's.
+    Here the ranks' factors are not observable -- the kernels publish the rank-averaged norm alone -- and they are
+    INSIDE g = (1 / W) sum_r coef_r g_r, the quantity whose float32 error `units` measures (dp_f32_error) and the GPU
+    test bounds by k_grad units; so dg = k_grad unit |g| with no second term:
+      |dm| <= (1 - b1) dg + 2^-23 |m'|,   |dv| <= (1 - b2) dg max|2.5 g| + 2^-22 |v'|."""
+    omb1, omb2 = float(F32(1) - F32(0.9)), float(F32(1) - F32(0.999))
+    out = {}
+    for t, g in r[net]['g'].items():
+        g = g.numpy()
+        dg = k_grad * units[t] * np.linalg.norm(g)
+        out[t] = (omb1 * dg + 2.0 ** -23 * np.linalg.norm(r[net]['m'][t].numpy()),
+                  omb2 * dg * 2.5 * np.abs(g).max() + 2.0 ** -22 * np.linalg.norm(r[net]['v'][t].numpy()))
+    return out
+
+
+def dp_f32_error(case: dict) -> tuple:
+    """f32_error for a data-parallel case: the float32 run of dp_case_step against its float64 run on every minibatch
+    from the case's INITIAL state -- per reference tensor of the AVERAGED CLIPPED gradient g (the quantity the device
+    shows; the ranks' factors are inside it) and per rank-mean scalar -- worst of ROW_ORDERS orders of the rows, permuted
+    within each rank (`worst`), and with the rows as drawn (`single`).
+
+    The critics' one-element output bias gets the second unit of OUT_BIAS_ROWS, stated for W ranks: its gradient is
+    (1 / W) sum_r coef_r (2 / n) sum_rows (v - target) (+ L2), W n independent forward errors of rms_r each, typically
+    (1 / W) sqrt(sum_r (coef_r (2 / sqrt n) rms_r)^2) / |g_64| -- from the float32 TWIN's forward values."""
+    worst, single = {}, {}
+    W = case['W']
+    for k, (_, n) in enumerate(minibatches(case['M'], case['B'])):
+        r64 = dp_case_step(case, case['state'], k)
+        rs = np.random.RandomState(977 + k)
+        for orders in [None] + [[rs.permutation(n) for _ in range(W)] for _ in range(ROW_ORDERS - 1)]:
+            r32 = dp_case_step(case, case['state'], k, torch.float32, orders)
+            for net in r64:
+                errs = {name: rel_l2(r32[net]['g'][name].numpy(), g.numpy()) for name, g in r64[net]['g'].items()}
+                errs.update((sc, rel_l2(float(r32[net][sc]), float(r64[net][sc]))) for sc in SCALARS[net])
+                if net != 'actor':
+                    ob, acc = out_bias(case), 0.0
+                    for i in range(W):
+                        v64 = r64[net]['ranks'][i]['value'].numpy()
+                        v64 = v64 if orders is None else v64[orders[i]]
+                        rms = float(np.sqrt(np.mean((r32[net]['ranks'][i]['value'].numpy().astype(np.float64) - v64) ** 2)))
+                        acc += (r64[net]['coefs'][i] * 2.0 / math.sqrt(n) * rms) ** 2
+                    errs[ob + '/rows'] = math.sqrt(acc) / W / abs(float(r64[net]['g'][ob]))
+                for dst in (worst,) if orders is not None else (worst, single):
+                    o = dst.setdefault(net, {})
+                    for name, e in errs.items():
+                        o[name] = max(o.get(name, 0.0), e)
+    return worst, single
+
+
+# form -> how PPOUpdater.run_pass_replicated is brought to it (coop / use_graph arguments, environment, the wide
+# switch _repl_wide) and what PPOUpdater._dp must report afterwards
+DP_FORMS = OrderedDict([
+    ('dp-steps', dict(coop=False, graph=False, env={})),  # osa_ppo_dp_step + osa_dp_apply_kernel, osa_ppo_dp_end_pass
+    ('dp-steps-graph', dict(coop=False, graph=True, env={})),  # the same launches: warm pass, capture, replay
+    ('dp-coop', dict(coop=True, env={'OSA_DP_XCH': 'local'}, chunked=False, local=True)),  # osa_ppo_dp_pass_placed
+    ('dp-coop-uncached', dict(coop=True, env={'OSA_DP_XCH': 'uncached'}, chunked=False, local=False)),
+    ('dp-coop-walk', dict(coop=True, env={'OSA_CHUNKED_PASS': '0'}, chunked=False, local=True)),  # B > 64, one workgroup per rank
+    ('dp-chunked', dict(coop=True, env={}, chunked=True, local=True)),  # osa_ppo_dp_chunked_pass
+    ('dp-split', dict(wide=True, env={'OSA_WIDE_DP': 'place'}, place=True)),  # osa_ppo_split_dp_pass
+    ('dp-split-spread', dict(wide=True, env={'OSA_WIDE_DP': 'spread'}, place=False)),
+])
+DP_ENV_KEYS = ('OSA_DP_XCH', 'OSA_CHUNKED_PASS', 'OSA_WIDE_DP', 'OSA_WIDE_SPLIT', 'OSA_DEBUG_PLACEMENT', 'OSA_DP_PLAIN_LAUNCH')
+# (obs, act, W, B, M per rank): the smallest shapes at which each mechanism is at work
+DP_NARROW = [(60, 2, 2, 64, 65),    # a tail of one row on every rank
+             (60, 2, 3, 48, 100),   # B no multiple of 16, an odd world, a tail of 4
+             (65, 17, 8, 64, 100),  # two output tiles, an observation width that is no multiple of 4; one rank per XCC
+             (1, 1, 1, 5, 12),      # a world of one
+             (60, 2, 11, 64, 64),   # more ranks than XCCs, an odd count
+             (60, 2, 16, 64, 64)]
+DP_CHUNK = [(60, 2, 2, 65, 130),    # a second chunk of one row
+            (65, 17, 3, 128, 300),  # a tail of 44 rows: one empty chunk on every rank
+            (60, 2, 8, 200, 500),   # two empty chunks; 8 x 4 = 32 peers, the local-placement limit
+            (27, 8, 16, 128, 128)]  # 16 ranks, the chunked form's limit
+DP_WIDE = [(376, 17, 2, 64, 65), (376, 17, 8, 40, 100), (97, 3, 3, 64, 100), (193, 5, 5, 5, 12)]
+# the variants: one shape per family on the family's cooperative form (narrow: also on the stepwise form)
+DP_VARIANT_SHAPES = [((65, 17, 8, 64, 100), ('dp-coop', 'dp-steps')), ((65, 17, 3, 128, 300), ('dp-chunked',)),
+                     ((376, 17, 2, 64, 65), ('dp-split',))]
+
+
+def dp_variants() -> 'OrderedDict[str, dict]':
+    v = OrderedDict()
+    v['losskind1'] = dict(loss_kind=1)
+    v['lam-0'] = dict(lam=0.0)
+    v['nocost'] = dict(use_cost=False)
+    v['actor-off'] = dict(update_actor=False)
+    v['critics-off'] = dict(update_critics=False)
+    v['l2-off'] = dict(use_critic_norm=0)
+    v['l2-0.05'] = dict(critic_norm_coef=0.05)
+    for net in NETS:
+        v[f'straddle-{net}'] = dict(norm_clip=('straddle', net))
+    v['normclip-all'] = dict(norm_clip=('all', 0.5))
+    v['normclip-off'] = dict(use_max_grad_norm=0)
+    v['seeded'] = dict(seeded_moments=True, t0=(3, 5, 7))
+    v['t0-250000'] = dict(seeded_moments=True, t0=(250000, 250000, 250000))
+    v['lr'] = dict(lr_actor=3e-4, lr_critic=1e-3, seeded_moments=True, t0=(3, 5, 7))
+    return v
+
+
+def dp_kw(od: int, ad: int, W: int, B: int, M: int) -> dict:
+    kw = dict(obs_dim=od, act_dim=ad, W=W, B=B, M=M)
+    return dict(kw, w1_scale=math.sqrt(64.0 / od)) if od > 96 else kw  # (the wide family: wide_kw)
+
+
+def dp_name(tag: str, kw: dict) -> str:
+    return f"{tag}-{kw['obs_dim']}x{kw['act_dim']}-W{kw['W']}-B{kw['B']}-M{kw['M']}"
+
+
+def dp_table() -> 'OrderedDict[str, dict]':
+    """name -> dict(kw = make_dp_case keyword arguments, forms = the DP_FORMS the case runs on[, tail = (rows, empty
+    chunks)]); names end in the shape and -W<ranks>-B<batch>-M<rows per rank>, which no name of the other tables does."""
+    t = OrderedDict()
+
+    def add(tag, kw, forms, **more):
+        name = dp_name(tag, kw)
+        assert name not in t
+        t[name] = dict(kw=kw, forms=tuple(forms), **more)
+
+    for i, shape in enumerate(DP_NARROW):
+        forms = ('dp-steps', 'dp-coop') + (('dp-steps-graph',) if i in (0, 2) else ()) + (
+            ('dp-coop-uncached',) if i in (0, 4, 5) else ())
+        add('base', dp_kw(*shape), forms)
+    for i, shape in enumerate(DP_CHUNK):
+        _, _, _, B, M = shape
+        n = minibatches(M, B)[-1][1]
+        add('base', dp_kw(*shape), ('dp-coop-walk', 'dp-chunked') + (('dp-steps',) if i == 1 else ()),
+            tail=(n, empty_chunks(B, n)))
+    for shape in DP_WIDE:
+        add('base', dp_kw(*shape), ('dp-split',) + (('dp-split-spread',) if shape[:3] in ((376, 17, 8), (376, 17, 2)) else ()))
+    for shape, forms in DP_VARIANT_SHAPES:
+        for tag, change in dp_variants().items():
+            add(tag, dict(dp_kw(*shape), **change), forms)
+    # ---- seeded moments at worlds that are no power of two, on the other families' forms: 1 / W is then no exact
+    # factor, and the average must reach both moments as ONE float32 number (DP_VARIANT_SHAPES has W = 3 on the
+    # chunked form alone)
+    seeded = dp_variants()['seeded']
+    add('seeded', dict(dp_kw(60, 2, 3, 48, 100), **seeded), ('dp-steps', 'dp-coop'))
+    add('seeded', dict(dp_kw(60, 2, 11, 64, 64), **seeded), ('dp-coop', 'dp-coop-uncached'))
+    add('seeded', dict(dp_kw(97, 3, 3, 64, 100), **seeded), ('dp-split', 'dp-split-spread'))
+    walk = dp_name('seeded', dp_kw(65, 17, 3, 128, 300))
+    t[walk] = dict(t[walk], forms=t[walk]['forms'] + ('dp-coop-walk',))
+    return t

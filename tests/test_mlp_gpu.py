@@ -386,7 +386,8 @@ def test_replicated_data_parallel_step_equals_allreduce_semantics(W, M, B, use_g
     """osa_ppo_dp_step (every rank computes the whole global step on the all-gathered rollout: W
     workgroups per network -> average of the locally clipped gradients -> Adam) vs the reference's
     data-parallel semantics emulated rank by rank with the per-step kernels (gradient + local clip per
-    rank, average, Adam): policy_gradient.py:437-442, distributed.py:193-198."""
+    rank, average, Adam): policy_gradient.py:437-442, distributed.py:193-198.
+    (The statement of correctness of this step is tests/test_dp_forms_gpu.py: the float64 twin, rank by rank.)"""
     import ctypes as C
 
     from omnisafe_amd import _lib
@@ -466,7 +467,8 @@ def test_wide_split_data_parallel_pass_equals_allreduce_semantics(W, M, obs_dim,
     helpers) in ONE cooperative launch; the owners of the same parameters average their locally clipped shares)
     vs the reference's data-parallel semantics emulated rank by rank with the per-step kernels (gradient + local
     clip per rank, average, Adam): policy_gradient.py:437-442, 478-483, 519-524, distributed.py:167-198.  Includes a
-    ragged last minibatch (M % 64 != 0) and a max_grad_norm small enough that the clip is ACTIVE on some ranks."""
+    ragged last minibatch (M % 64 != 0) and a max_grad_norm small enough that the clip is ACTIVE on some ranks.
+    (The statement of correctness of this step is tests/test_dp_forms_gpu.py: the float64 twin, rank by rank.)"""
     import ctypes as C
 
     from omnisafe_amd import _lib
@@ -586,7 +588,8 @@ def test_chunked_data_parallel_pass_equals_allreduce_semantics(W, M, B, obs_dim,
     reference's data-parallel semantics emulated rank by rank with the per-step kernels (B-row gradient + local
     clip per rank, average, Adam): natural_pg.py:205-223, policy_gradient.py:437-442, distributed.py:167-198.
     max_grad_norm is small enough that the clip is active on most steps of the reward critic.  `chunked = False`:
-    the same through one workgroup per rank walking the chunks (OSA_CHUNKED_PASS=0)."""
+    the same through one workgroup per rank walking the chunks (OSA_CHUNKED_PASS=0).
+    (The statement of correctness of this step is tests/test_dp_forms_gpu.py: the float64 twin, rank by rank.)"""
     import ctypes as C
 
     from omnisafe_amd import _lib

@@ -274,9 +274,11 @@ def check_structure(h, before, after, steps):
         assert after['t'][net] == before['t'][net] + (steps if net in h.nets else 0), (net, after['t'], before['t'])
 
 
-def check_scalars(name, path, kind, r, stats, e32, failures):
-    """Statistics row against the twin: |x_kernel - x_64| <= K_SCALAR max(e32, 2^-22) |x_64|."""
-    case = reference(name)['case']
+def check_scalars(name, path, kind, r, stats, e32, failures, case=None, e32_single=None):
+    """Statistics row against the twin: |x_kernel - x_64| <= K_SCALAR max(e32, 2^-22) |x_64|.
+    (`case`, `e32_single`: of a case from another table than this file's -- tests/test_dp_forms_gpu.py.)"""
+    case = reference(name)['case'] if case is None else case
+    e32_single = E32_SINGLE[name] if e32_single is None else e32_single
     for net, res in r.items():
         for what, col in COL[net].items():
             if what == 'penalty' and not (case['ext'] or {}).get('cost_kappa', 0) > 0:
@@ -286,7 +288,7 @@ def check_scalars(name, path, kind, r, stats, e32, failures):
             want = float(res[what])
             err = T.rel_l2(float(stats[col]), want)
             u = unit(e32, net, what)
-            record(name, path, kind + '/scalar', net, what, err / u, K_SCALAR, err / unit(E32_SINGLE[name], net, what))
+            record(name, path, kind + '/scalar', net, what, err / u, K_SCALAR, err / unit(e32_single, net, what))
             if not err <= K_SCALAR * u:
                 failures.append((kind, net, what, float(stats[col]), want, err / u))
 
@@ -317,6 +319,28 @@ def kernel_gradient(h, after, stats, net):
     return g, factor, {k: x / factor for k, x in g.items()}
 
 
+def check_second_moment(name, path, kind, net, g, v_after, failures):
+    """v' of a step from zero moments against (1 - b2) g_kernel^2: 4 ulp."""
+    worst = 0.0
+    for t, x in g.items():
+        want = OMB2 * x * x
+        worst = max(worst, float((np.abs(v_after[t] - want) / ulps(want)).max()))
+    record(name, path, kind + '/moments', net, "v' - (1 - b2) g^2 [ulp]", worst, 4.0)
+    if not worst <= 4.0:
+        failures.append((kind, net, "v' against (1 - b2) g_kernel^2, ulp", worst))
+
+
+def check_step_moments(name, path, kind, net, tol, after, r, failures):
+    """m', v' of one step against the twin's step from the same state, per tensor within `tol` (state_tolerances)."""
+    for t in tol:
+        em = np.linalg.norm(after['m'][net][t] - r[net]['m'][t].numpy())
+        ev = np.linalg.norm(after['v'][net][t] - r[net]['v'][t].numpy())
+        record(name, path, kind + '/state', net, t + " m'", em / tol[t][0], 1.0)
+        record(name, path, kind + '/state', net, t + " v'", ev / tol[t][1], 1.0)
+        if not (em <= tol[t][0] and ev <= tol[t][1]):
+            failures.append((kind, net, t, 'moments / tolerance', em / tol[t][0], ev / tol[t][1]))
+
+
 def check_first_step(name, path, h, ref, k, failures):
     """Minibatch k from the zero-moment state: gradient, clip factor, v', statistics, Adam, bias-correction columns."""
     zero, r = ref['zero'], ref['first'][k]
@@ -340,13 +364,7 @@ def check_first_step(name, path, h, ref, k, failures):
         record(name, path, kind + '/scalar', net, 'clip factor', err / u, K_SCALAR, err / unit(E32_SINGLE[name], net, 'gnorm'))
         if not err <= K_SCALAR * u:
             failures.append((kind, net, 'clip factor', factor, float(r[net]['coef']), err / u))
-        worst = 0.0
-        for t, x in g.items():
-            want = OMB2 * x * x
-            worst = max(worst, float((np.abs(after['v'][net][t] - want) / ulps(want)).max()))
-        record(name, path, kind + '/moments', net, "v' - (1 - b2) g^2 [ulp]", worst, 4.0)
-        if not worst <= 4.0:
-            failures.append((kind, net, "v' against (1 - b2) g_kernel^2, ulp", worst))
+        check_second_moment(name, path, kind, net, g, after['v'][net], failures)
     if h.bias_columns:
         check_bias_columns(h, kind, stats, after['t'], failures)
     check_adam(name, path, kind, h, before, after, failures)
@@ -403,14 +421,7 @@ def check_chain(name, path, h, ref, failures):
             r = T.case_step(case, {w: before[w] for w in ('params', 'm', 'v', 't')}, k)
             check_scalars(name, path, f'chain{k}', r, stats, e32, failures)
             for net in h.nets:
-                tol = state_tolerances(r, e32, net)
-                for t in tol:
-                    em = np.linalg.norm(after['m'][net][t] - r[net]['m'][t].numpy())
-                    ev = np.linalg.norm(after['v'][net][t] - r[net]['v'][t].numpy())
-                    record(name, path, f'chain{k}/state', net, t + " m'", em / tol[t][0], 1.0)
-                    record(name, path, f'chain{k}/state', net, t + " v'", ev / tol[t][1], 1.0)
-                    if not (em <= tol[t][0] and ev <= tol[t][1]):
-                        failures.append((f'chain{k}', net, t, 'moments / tolerance', em / tol[t][0], ev / tol[t][1]))
+                check_step_moments(name, path, f'chain{k}', net, state_tolerances(r, e32, net), after, r, failures)
             check_adam(name, path, f'chain{k}', h, before, after, failures)
             state = {w: after[w] for w in ('params', 'm', 'v', 't')}
         before, final, stats = h.whole_pass(case['state'])
@@ -427,8 +438,10 @@ def check_chain(name, path, h, ref, failures):
     check_final_state(name, path, h.nets, chain, e32, final, failures)
 
 
-def check_final_state(name, path, nets, chain, e32, final, failures):
-    """The state a chain of float32 steps leaves against the twin's float64 chain of the same steps."""
+def check_final_state(name, path, nets, chain, e32, final, failures, tolerances=None):
+    """The state a chain of float32 steps leaves against the twin's float64 chain of the same steps.
+    (`tolerances`: state_tolerances' counterpart for the steps of another twin -- tests/test_dp_forms_gpu.py.)"""
+    tolerances = state_tolerances if tolerances is None else tolerances
     for net in nets:
         # the steps' tolerances add up (a step inherits b1 of the previous first moment's error); a parameter inherits,
         # ELEMENT BY ELEMENT, ss dm / den + |D| dv / (2 v') of its step's moments on top of the Adam bound (dm, dv: the
@@ -436,7 +449,7 @@ def check_final_state(name, path, nets, chain, e32, final, failures):
         # its own bound and no other
         tm, tv, tp = {}, {}, {}
         for r in chain:
-            tol = state_tolerances(r, e32, net)
+            tol = tolerances(r, e32, net)
             for t in tol:
                 tm[t] = tm.get(t, 0.0) + tol[t][0]
                 tv[t] = tv.get(t, 0.0) + tol[t][1]

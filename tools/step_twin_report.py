@@ -13,6 +13,12 @@ measuring stick of that file, on the CPU (the float32 twin against the float64 t
     OSA_STEP_TWIN_FIGURES=general.json python -m pytest -m gpu tests/test_general_step_gpu.py
     python tools/step_twin_report.py general.json > profiles/general_twin_error.md
 
+and profiles/dp_twin_error.md from tests/test_dp_forms_gpu.py (paths dp-steps ... dp-split-spread, p2p; a gradient entry
+there is the AVERAGED CLIPPED gradient, a scalar the mean over the ranks, the units those of step_twin.dp_f32_error):
+
+    OSA_STEP_TWIN_FIGURES=dp.json python -m pytest -m gpu tests/test_dp_forms_gpu.py
+    python tools/step_twin_report.py dp.json > profiles/dp_twin_error.md
+
 The columns of the tables are the paths found in the figures, in their order of appearance (`per-step / persistent`
 for the 64-row table; per-step, chunked, wide, split, split-spread, balanced, strided for the forms, where a case runs
 on the forms of its family only and the other cells stay `-`).
@@ -56,6 +62,7 @@ def main(path: str) -> None:
             paths.append(f[1])
     narrow = paths == ['per-step', 'persistent']
     general = 'general' in paths
+    dp = any(q.startswith('dp-') for q in paths)  # tests/test_dp_forms_gpu.py (its last column, p2p: cases and units of the 64-row table)
     per_path = collections.defaultdict(lambda: (0.0, None))  # (class, path) -> worst
     by = collections.defaultdict(float)   # (class, case, net, what, path) -> worst over the steps
     worst = collections.defaultdict(lambda: (0.0, None))
@@ -68,9 +75,10 @@ def main(path: str) -> None:
             if sgl > single[key][0]:
                 single[key] = (sgl, (case, p, kind, net, what))
         by[(cls, case, net, what, p)] = max(by[(cls, case, net, what, p)], meas)
-        bound[cls] = bnd
+        bound.setdefault(cls, bnd)
         if meas > worst[cls][0]:
             worst[cls] = (meas, (case, p, kind, net, what))
+            bound[cls] = bnd  # (the bound of the worst figure: v' after a zero-moment step has 4 ulp, the seeded recurrences 2)
         if meas > per_path[(cls, p)][0]:
             per_path[(cls, p)] = (meas, (case, p, kind, net, what))
     out = []
@@ -78,16 +86,20 @@ def main(path: str) -> None:
     cols_txt = ' / '.join(paths)
     w('# The 64-row optimiser step against its float64 twin: measured error ratios (MI355X)\n' if narrow else
       '# The optimiser step of general networks against the float64 twin: measured error ratios (MI355X)\n' if general else
+      '# The data-parallel forms of the optimiser step against the float64 twin: measured error ratios (MI355X)\n' if dp else
       '# The chunked, wide, split and large-batch steps against the float64 twin: measured error ratios (MI355X)\n')
     w('Written by `tools/step_twin_report.py` from one run of '
       + ('`tests/test_step_oracle_gpu.py` ' if narrow else '`tests/test_general_step_gpu.py` ' if general
-         else '`tests/test_step_forms_gpu.py` ') +
+         else '`tests/test_dp_forms_gpu.py` ' if dp else '`tests/test_step_forms_gpu.py` ') +
       f'({len(fig)} figures, {len({f[0] for f in fig})} cases, '
       + ('both paths' if narrow else f'{len({(f[0], f[1]) for f in fig})} (case, form) pairs') + ').  A gradient or scalar entry is '
       '`error / max(e32, 2^-22)`: the relative L2 error of the kernel against `tests/step_twin.py` in float64, in units of '
       'what the float32 run of the same twin loses (`tests/golden/'
-      + ('general_twin' if general else 'step_twin') + '_f32_error.json`), worst over the '
+      + ('general_twin' if general else 'dp_twin' if dp else 'step_twin') + '_f32_error.json`), worst over the '
       f'minibatches of the case.  Columns `{cols_txt}`' + ('' if narrow else ' (`-`: the case does not run on that form)') + '.\n')
+    if dp and 'p2p' in paths:
+        w('The last column, `p2p`, is the peer-exchange pass at a world of one on three cases of the 64-row table: single-rank '
+          'twin, units from `tests/golden/step_twin_f32_error.json`.\n')
     w('## Summary\n')
     w('| quantity | worst measured | where | bound in the test |')
     w('|---|---|---|---|')
@@ -103,9 +115,12 @@ def main(path: str) -> None:
       'The bounds are those of the 64-row table (`tests/test_step_oracle_gpu.py`; a clipped gradient of mode 1 adds the '
       'clip factor\'s bound to its tensor\'s and is listed rescaled to K_GRAD); nothing was fitted to this path.\n' if general else
       'The bounds are those of the 64-row table (`tests/test_step_oracle_gpu.py`); nothing was fitted to these forms.  '
-      + ('Every quantity stayed inside its bound in the units of the float32 twin (the sums over up to 6000 rows and '
+      + ('Every quantity stayed inside its bound in the units of the float32 twin of the data-parallel step (the '
+         'averaged clipped gradient, the rank-mean scalars): no unit was re-derived for these forms.\n'
+         if dp and all(f[5] <= f[6] for f in fig) else
+         'Every quantity stayed inside its bound in the units of the float32 twin (the sums over up to 6000 rows and '
          'the slab sums of the large-batch forms included): no unit was re-derived for these forms.\n'
-         if all(worst[c][0] <= bound[c] for c in worst) else
+         if all(f[5] <= f[6] for f in fig) else
          'NOT every quantity stayed inside its bound: see the rows above.\n'))
     if not narrow:
         w('## Worst ratio per form\n')
