@@ -313,7 +313,10 @@ int osa_ppo_wide_pass(int obs_dim, int act_dim, int hidden, float* params, float
  * Same arguments, statistics and per-step arithmetic as osa_ppo_wide_pass (float32 re-association of the
  * layer-1 sum only).  OSA_EUNSUPPORTED when the shape is not supported or the device cannot hold the
  * workgroups together: use osa_ppo_wide_pass.  A peer that never arrives raises a sticky flag instead of
- * hanging the device: osa_ppo_split_pass_timed_out(xch, &flag) reads it (synchronous copy; 0 = fine). */
+ * hanging the device: osa_ppo_split_pass_timed_out(xch, &flag) reads it (synchronous copy; 0 = fine).
+ * A process that the runtime refuses the cooperative launch for another reason than the grid's size (several
+ * processes on one device: the cooperative queue belongs to one of them) launches plainly behind an occupancy
+ * check of its own, this form and the data-parallel one below. */
 int osa_ppo_split_pass_supported(int obs_dim, int act_dim, int hidden);
 size_t osa_ppo_split_pass_xch_floats(int obs_dim, int act_dim, int hidden);
 int osa_ppo_split_pass(int obs_dim, int act_dim, int hidden, float* params, float* adam_m, float* adam_v,

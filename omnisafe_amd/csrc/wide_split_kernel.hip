@@ -1277,16 +1277,31 @@ static int osa_launch_split(const OsaSplitArgs& a, hipStream_t stream) {
   }
   // the workgroups of a network wait for each other every step, so they MUST be co-resident: a cooperative
   // launch makes the runtime verify that and refuses otherwise (the caller then takes the one-CU kernel)
-  OsaSplitArgs arg = a;
-  void* kargs[] = {&arg};
   const int nblk = DP ? (a.dp_place == 1 ? 8 * ((3 * (a.C + 1) + 7) / 8) * a.world : a.world * 3 * (a.C + 1))
                       : (a.local == 1 ? 8 * (a.C + 1) : 3 * (a.C + 1));
-  const hipError_t e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&osa_wide_split_kernel<OT, DP>),
-                                                  dim3(nblk), dim3(256), kargs,
-                                                  (unsigned)lds, stream);
-  if (e == hipSuccess) return OSA_OK;
-  (void)hipGetLastError();
-  return e == hipErrorCooperativeLaunchTooLarge ? OSA_EUNSUPPORTED : OSA_EHIP;
+  const void* kernel = reinterpret_cast<const void*>(&osa_wide_split_kernel<OT, DP>);
+  // A device may hand its cooperative queue to ONE process at a time: with several ranks on one GPU every other
+  // process is refused it ("failed to acquire a cooperative queue", an error that is not ...TooLarge).  As
+  // osa_launch_pass_kernel (ppo_pass_body.h) does, such a process verifies the co-residency itself (occupancy x CUs
+  // >= grid) and launches plainly from then on; a peer that never arrives still raises the sticky flag.
+  static bool coop_refused = false;
+  if (!coop_refused) {
+    OsaSplitArgs arg = a;
+    void* kargs[] = {&arg};
+    const hipError_t e = hipLaunchCooperativeKernel(kernel, dim3(nblk), dim3(256), kargs, (unsigned)lds, stream);
+    if (e == hipSuccess) return OSA_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorCooperativeLaunchTooLarge) return OSA_EUNSUPPORTED;
+    coop_refused = true;
+  }
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess ||
+      hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return OSA_EHIP;
+  if ((long)per_cu * cus < (long)nblk) return OSA_EUNSUPPORTED;
+  hipLaunchKernelGGL((osa_wide_split_kernel<OT, DP>), dim3(nblk), dim3(256), lds, stream, a);
+  return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
 }
 
 extern "C" {
