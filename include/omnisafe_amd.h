@@ -1097,6 +1097,70 @@ int osa_crr_step(const osa_crr_desc* desc, const osa_crr_hparams* hp, const osa_
                  const osa_crr_data* data, const osa_crr_draw_buffers* draws, float* stats, float* ws, size_t ws_floats,
                  int nsteps, void* stream);
 
+/* ---- offline VAE-BC (csrc/vae_kernels.hip) -------------------------------------------------------------------------
+ * The conditional VAE of omnisafe/models/actor/vae_actor.py:43-138 trained from a device-resident dataset
+ * (omnisafe/algorithms/offline/vae_bc.py:79-97; the first half of a BCQ step, bcq.py:179-185).  Two networks in ONE
+ * padded float32 block [Pe + Pd], each in the layout of osa_crr_layout's blocks: the encoder
+ * [obs_dim + act_dim, *hidden, 4 act_dim] at 0, the decoder [obs_dim + 2 act_dim, *hidden, act_dim] at Pe.  Hidden
+ * activation any OSA_ACT_*, output activation identity, 1 .. OSA_GMLP_MAX_LAYERS - 1 hidden layers, act_dim <= 32. */
+#define OSA_VAE_NSTAT 4
+/* a step's statistics row: 0 Loss_vae, 1 Loss_recon, 2 Loss_kl, 3 unused (vae_bc.py:91-97) */
+#define OSA_VAE_ROUTE_TILE 0   /* body layers on the 64 x 64 tile GEMM of the general networks */
+#define OSA_VAE_ROUTE_SKINNY 1 /* every layer on the skinny-batch kernel */
+typedef struct osa_vae_desc {
+  int obs_dim, act_dim;
+  int n_hidden;
+  int hidden[OSA_GMLP_MAX_LAYERS]; /* widths of the hidden layers, shared by both networks */
+  int activation;                  /* OSA_ACT_* of the hidden layers */
+  int batch;
+} osa_vae_desc;
+typedef struct osa_vae_hparams {
+  float lr;
+  int route;                     /* OSA_VAE_ROUTE_* */
+  double beta1, beta2, adam_eps; /* double: torch rounds 1 - beta to float32 from the double difference */
+} osa_vae_hparams;
+typedef struct osa_vae_state { /* device memory, 16-byte aligned blocks */
+  float *params, *m, *v;       /* [Pe + Pd] */
+  int* adam_step;              /* [1] */
+  long* step;                  /* [1] steps taken: advanced by every step on the device */
+} osa_vae_state;
+typedef struct osa_vae_draw_buffers { /* step t reads slot t % nslots */
+  const long* idx;                    /* [nslots][B] in [0, N) */
+  const float* eps;                   /* [nslots][B][2 act_dim]: the noise of dist.rsample(), vae_actor.py:108 */
+  int nslots;
+} osa_vae_draw_buffers;
+/* out[0..3] = Pe, Pd, OSA_VAE_NSTAT, 0; then (oW, ob, ld) of layers 0..OSA_GMLP_MAX_LAYERS-1 of the encoder and of the
+ * decoder, offsets inside the network's own block (-1, -1, 0 for absent layers): 4 + 48 ints.  OSA_EUNSUPPORTED for no
+ * hidden layer, too many, act_dim > 32 or batch > 2^20.  Host only. */
+int osa_vae_layout(const osa_vae_desc* desc, int* out);
+/* floats of the step's workspace; 0 for a description osa_vae_layout refuses.  Host only. */
+size_t osa_vae_ws_floats(const osa_vae_desc* desc);
+/* 1 when OSA_VAE_ROUTE_SKINNY takes the description's body layers (batch <= 512, widths <= 4096), else 0. */
+int osa_vae_skinny_supported(const osa_vae_desc* desc);
+/* The draws of steps first_step .. first_step + nsteps - 1 into their slots (dataset.py:237-247's randint and the
+ * noise of vae_actor.py:108): the scheme of osa_crr_draws with two keys of its own, element = row * 2 act_dim + d. */
+int osa_vae_draws(const osa_vae_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                  long n_rows, long* idx, float* eps, void* stream);
+/* nsteps train steps enqueued on `stream`, each VAE.loss (vae_actor.py:100-112) and one torch.optim.Adam step over
+ * every parameter of both networks (vae_bc.py:85-89): the first layers read obs || act and obs || z straight from
+ * the dataset rows data->obs / data->act through idx (the other fields of `data` are not read); the encoder head
+ * (chunk, clamp of log_std to [-20, 2], exp, z = mu + sigma eps, the KL against N(0, 1)) and the decoder head (MSE and
+ * dL/dpred) are one small kernel each; one Adam launch.  No host synchronisation, no allocation, no float atomics;
+ * the draws' slot and the row of stats [nslots][OSA_VAE_NSTAT] follow *state->step, so a captured step advances on
+ * replay.  OSA_EINVAL before any launch for null pointers, a short or misaligned workspace; OSA_EUNSUPPORTED for what
+ * osa_vae_layout refuses and for OSA_VAE_ROUTE_SKINNY where osa_vae_skinny_supported is 0. */
+int osa_vae_step(const osa_vae_desc* desc, const osa_vae_hparams* hp, const osa_vae_state* state,
+                 const osa_crr_data* data, const osa_vae_draw_buffers* draws, float* stats, float* ws,
+                 size_t ws_floats, int nsteps, void* stream);
+/* floats of osa_vae_decode's workspace for n rows; 0 for a refused description or n < 1.  Host only. */
+size_t osa_vae_decode_ws_floats(const osa_vae_desc* desc, long n);
+/* VAE.decode (vae_actor.py:83-98) of n rows: out[r][0 .. act_dim) = decoder(obs[r] || z[r]).  z NULL: the latent is
+ * drawn on the device, the first Box-Muller normal of Philox(seed, offset, r * 2 act_dim + d) (vae_actor.py:95-96;
+ * VAE.predict, :121-138).  `decoder`: the decoder's block (params + Pe).  n <= 2^20. */
+int osa_vae_decode(const osa_vae_desc* desc, int route, const float* decoder, const float* obs, int ld_obs,
+                   const float* z, int ld_z, long n, unsigned long long seed, unsigned long long offset, float* out,
+                   int ld_out, float* ws, size_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

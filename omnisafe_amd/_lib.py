@@ -147,6 +147,14 @@ SIGNATURES: dict[str, tuple] = {
     'osa_crr_ws_floats': (C.c_size_t, [_P]),
     'osa_crr_draws': (_I, [_P, _U, _L, _I, _I, _L, _P, _P, _P, _P, _P]),
     'osa_crr_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
+    # offline VAE-BC (csrc/vae_kernels.hip): structs of vae_step.py, passed by reference
+    'osa_vae_layout': (_I, [_P, _P]),
+    'osa_vae_ws_floats': (C.c_size_t, [_P]),
+    'osa_vae_skinny_supported': (_I, [_P]),
+    'osa_vae_draws': (_I, [_P, _U, _L, _I, _I, _L, _P, _P, _P]),
+    'osa_vae_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
+    'osa_vae_decode_ws_floats': (C.c_size_t, [_P, _L]),
+    'osa_vae_decode': (_I, [_P, _I, _P, _P, _I, _P, _I, _L, _U, _U, _P, _I, _P, C.c_size_t, _P]),
 }
 
 

@@ -6,9 +6,10 @@ from .siblings import (CPPOPID, CUP, FOCOPS, IPO, P3O, PCPO, PDO, RCPO, TRPOPID,
                        PPOSimmerPID, TRPOSaute, TRPOSimmerPID)
 
 ALGORITHMS = {'on-policy': tuple(sorted(registry.REGISTRY._module_dict))}  # noqa: SLF001
-from .offline import CCRR, CRR  # noqa: E402  (after the on-policy tuple: the registry holds both families)
+from .offline import CCRR, CRR, VAEBC  # noqa: E402  (after the on-policy tuple: the registry holds every family)
 
 ALGORITHMS['offline'] = ('CCRR', 'CRR')
-__all__ = ['CRR', 'CCRR','PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
+ALGORITHMS['offline-bc'] = ('VAEBC',)
+__all__ = ['CRR', 'CCRR', 'VAEBC','PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
            'OnCRPO', 'CPPOPID', 'TRPOPID', 'PCPO', 'FOCOPS', 'CUP', 'P3O', 'PPOSaute', 'TRPOSaute',
            'PPOSimmerPID', 'TRPOSimmerPID', 'registry', 'ALGORITHMS']

@@ -1,5 +1,5 @@
-"""Offline CRR and CCRR trained on the device from a collected dataset -- mirror of
-omnisafe/algorithms/offline/base.py:32-152, crr.py:30-200 and c_crr.py:30-206.
+"""Offline CRR, CCRR and VAE-BC trained on the device from a collected dataset -- mirror of
+omnisafe/algorithms/offline/base.py:32-152, crr.py:30-200, c_crr.py:30-206 and vae_bc.py:29-97.
 
     col.collect(data_dir)
     agent = omnisafe_amd.Agent('CCRR', env_id, custom_cfgs={'train_cfgs': {'dataset': '<data_dir>/<env_id>_data.npz'}})
@@ -16,8 +16,9 @@ Deviations from the reference:
   * CCRR trains the cost critic pair on the cost targets with its own optimiser and values the sampled actions' cost
     with it.  c_crr.py:103-133 as written trains the reward pair a second time and :160-161 evaluates the sampled cost
     with the reward pair; ``OSA_CCRR_WIRING=reference`` selects that wiring.
-  * Checkpoints hold the actor under ``actor`` (what the reference saves) and under ``pi`` (what every Evaluator,
-    the reference's included, reads).
+  * Checkpoints hold the actor under ``actor`` (VAE-BC: ``vae``; what the reference saves) and under ``pi`` (what
+    every Evaluator, the reference's included, reads).
+  * VAE-BC's per-epoch evaluation plays the VAE as ``VAE.predict`` does: a fresh latent per step, drawn on the device.
   * The ``total_steps % steps_per_epoch`` steps after the last epoch, which the reference trains but never logs,
     evaluates or saves, are not run.
 """
@@ -32,6 +33,7 @@ from ..crr_step import CRR_STATS, STAT_KEYS, CrrStep, load_dataset, make_desc
 from ..evaluator import Evaluator
 from ..logger import Logger
 from ..saved_policy import device_env_class
+from .. import vae_step
 from .. import envs as envs_mod
 from .base_algo import BaseAlgo
 from .registry import register
@@ -42,7 +44,7 @@ MAX_SLOTS = 8192  # steps whose draws and statistics are resident at a time (an 
 class _ActorState:
     """What the logger's saver calls: the actor's state dict in the reference's names and order."""
 
-    def __init__(self, step: CrrStep) -> None:
+    def __init__(self, step) -> None:
         self._step = step
 
     def state_dict(self):
@@ -53,6 +55,9 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
     """base.py:32-152."""
 
     pairs = 1
+    stat_keys = STAT_KEYS      # names of the statistics row's columns
+    base_columns = CRR_STATS   # the columns every algorithm of the class logs
+    saved_as = 'actor'         # the checkpoint key the reference saves the actor under
 
     def __init__(self, env_id: str, cfgs) -> None:
         self.epoch = 0
@@ -99,7 +104,7 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
             self._cfgs.train_cfgs.recurisve_update({'dataset': self._dataset_name})
 
     def _stat_columns(self) -> tuple[int, ...]:
-        return CRR_STATS
+        return self.base_columns
 
     def _init_log(self) -> None:
         """base.py:52-96, crr.py:39-69."""
@@ -110,13 +115,16 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         for key in ('Metrics/EpRet', 'Metrics/EpCost', 'Metrics/EpLen', 'Time/Total', 'Time/Epoch', 'Time/Update',
                     'Time/Evaluate', 'Train/Epoch', 'TotalSteps'):
             self._logger.register_key(key)
-        self._logger.setup_torch_saver({'actor': self._actor, 'pi': self._actor})
-        for col in CRR_STATS:
-            self._logger.register_key(STAT_KEYS[col])
+        self._logger.setup_torch_saver({self.saved_as: self._actor, 'pi': self._actor})
+        for col in self.base_columns:
+            self._logger.register_key(self.stat_keys[col])
 
     # ------------------------------------------------------------------ training
     def _lagrange_open(self) -> bool:
         return False
+
+    def _run_steps(self, n: int) -> None:
+        self._step.run(n, lagrange_open=self._lagrange_open())
 
     def _train_epoch(self) -> torch.Tensor:
         """``steps_per_epoch`` train steps (base.py:105-107 that many times); the steps' statistics rows, on the
@@ -127,7 +135,7 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         for done in range(0, spe, self._nslots):
             n = min(self._nslots, spe - done)
             self._step.draw(self._seed, first + done, n)
-            self._step.run(n, lagrange_open=self._lagrange_open())
+            self._run_steps(n)
             slots = (torch.arange(n, device=self._device) + (first + done)) % self._nslots
             rows.append(self._step.stats[slots])
         return rows[0] if len(rows) == 1 else torch.cat(rows)
@@ -141,7 +149,7 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
             for _ in range(int(self._cfgs.train_cfgs.total_steps) // spe):
                 stats = self._train_epoch().cpu()  # the epoch's one read of the device
                 for col in self._stat_columns():
-                    self._logger.extend(STAT_KEYS[col], stats[:, col].tolist())
+                    self._logger.extend(self.stat_keys[col], stats[:, col].tolist())
                 self.epoch += 1
                 self._logger.store({'Time/Update': time.time() - epoch_time})
                 eval_time = time.time()
@@ -166,7 +174,7 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         if not hasattr(self, '_evaluator'):
             self._evaluator = Evaluator(seed=self._seed, device=self._device, verbose=False)
         ev = self._evaluator
-        ev.load_policy(self._cfgs.todict(), {'pi': self._step.actor_state_dict()})
+        ev.load_policy(self._cfgs.todict(), {'pi': self._actor.state_dict()})
         rets, costs = ev.evaluate(num_episodes=int(self._cfgs.train_cfgs.evaluate_epoisodes))
         self._logger.extend('Metrics/EpRet', [float(x) for x in rets])
         self._logger.extend('Metrics/EpCost', [float(x) for x in costs])
@@ -199,4 +207,26 @@ class CCRR(BaseOffline):
         return self.epoch * a.steps_per_epoch > a.lagrange_start_step
 
 
-__all__ = ['BaseOffline', 'CRR', 'CCRR']
+@register
+class VAEBC(BaseOffline):
+    """Behaviour cloning with a conditional VAE (vae_bc.py:29-97): vae_step.VaeStep, csrc/vae_kernels.hip."""
+
+    stat_keys = vae_step.STAT_KEYS
+    base_columns = (0, 1, 2)
+    saved_as = 'vae'
+
+    def _init_model(self) -> None:
+        """vae_bc.py:61-77: the VAE and one Adam over all its parameters."""
+        m, a = self._cfgs.model_cfgs, self._cfgs.algo_cfgs
+        assert isinstance(m.learning_rate, float), 'The learning rate must be a float number.'
+        desc = vae_step.make_desc(self._obs_dim, self._act_dim, m.hidden_sizes, m.activation, a.batch_size)
+        self._nslots = min(int(a.steps_per_epoch), MAX_SLOTS)
+        self._step = vae_step.VaeStep(desc, None, lr=m.learning_rate, nslots=self._nslots, device=self._device)
+        self._step.init_parameters(m.weight_initialization_mode)
+        self._actor = self._step  # (its state_dict() is the reference's VAE.state_dict())
+
+    def _run_steps(self, n: int) -> None:
+        self._step.run(n)
+
+
+__all__ = ['BaseOffline', 'CRR', 'CCRR', 'VAEBC']

@@ -191,13 +191,28 @@ _CCRR['lagrange_cfgs'] = {'cost_limit': 25.0, 'lagrangian_multiplier_init': 1.0,
                           'lambda_optimizer': 'Adam'}
 OFFLINE_DEFAULTS = {'CRR': _CRR, 'CCRR': _CCRR}
 
+# ---- behaviour cloning (configs/offline/VAEBC.yaml): one VAE, no actor / critic blocks, no gamma.  A table of its
+# own: the entries of OFFLINE_DEFAULTS all carry the actor-critic keys.  Same deviations as above.
+_VAEBC = {
+    'seed': 0,
+    'train_cfgs': copy.deepcopy(_CRR['train_cfgs']),
+    'algo_cfgs': {'batch_size': 256, 'steps_per_epoch': 1000},
+    'logger_cfgs': copy.deepcopy(_CRR['logger_cfgs']),
+    'model_cfgs': {'weight_initialization_mode': 'kaiming_uniform', 'hidden_sizes': [750, 750], 'activation': 'relu',
+                   'learning_rate': 0.001},
+    'env_cfgs': {},
+}
+BC_DEFAULTS = {'VAEBC': _VAEBC}
+
 
 def get_default_kwargs(algo: str) -> dict:
     """get_default_kwargs_yaml (config.py:235-262) for the accelerated algorithms."""
-    if algo in OFFLINE_DEFAULTS:
-        return copy.deepcopy(OFFLINE_DEFAULTS[algo])
+    for table in (OFFLINE_DEFAULTS, BC_DEFAULTS):
+        if algo in table:
+            return copy.deepcopy(table[algo])
     if algo not in DEFAULTS:
-        raise KeyError(f'{algo} is not an omnisafe_amd algorithm (have {sorted(DEFAULTS) + sorted(OFFLINE_DEFAULTS)})')
+        raise KeyError(f'{algo} is not an omnisafe_amd algorithm '
+                       f'(have {sorted(DEFAULTS) + sorted(OFFLINE_DEFAULTS) + sorted(BC_DEFAULTS)})')
     return copy.deepcopy(DEFAULTS[algo])
 
 
@@ -214,12 +229,14 @@ def recursive_check_config(config: dict, default: dict, exclude_keys=()) -> None
 def check_all_configs(cfgs: Config) -> None:
     """Subset of config.py:265-409 that guards this path."""
     a = cfgs.algo_cfgs
-    if getattr(cfgs, 'algo', None) in OFFLINE_DEFAULTS:  # the offline family has none of the on-policy keys
+    algo = getattr(cfgs, 'algo', None)
+    if algo in OFFLINE_DEFAULTS or algo in BC_DEFAULTS:  # the offline family has none of the on-policy keys
         t = cfgs.train_cfgs
         assert isinstance(a.steps_per_epoch, int) and a.steps_per_epoch > 0
         assert isinstance(a.batch_size, int) and a.batch_size > 0
-        assert isinstance(a.sampled_action_num, int) and a.sampled_action_num > 0
-        assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0 and a.beta > 0
+        if algo in OFFLINE_DEFAULTS:  # (behaviour cloning has no critic: no samples, discount or target network)
+            assert isinstance(a.sampled_action_num, int) and a.sampled_action_num > 0
+            assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0 and a.beta > 0
         assert isinstance(t.total_steps, int) and t.total_steps > 0
         assert isinstance(t.evaluate_epoisodes, int) and t.evaluate_epoisodes > 0
         assert t.parallel == 1 and t.vector_env_nums == 1, 'offline only supports parallel 1 and vector_env_nums 1'

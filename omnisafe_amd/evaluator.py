@@ -14,7 +14,8 @@ Two paths, one semantics:
               SynthNavCarGoal*-v0, SynthNavCarCircle*-v0, Synth*-v0, and the ids of register_device_env):
               every episode in ONE launch of osa_eval_episodes (csrc/eval_kernels.hip; a custom env: its own library's
               osa_custom_eval_episodes, the same kernel template), episode k = env index k of a fresh env.
-  per-step    everything else (general networks, host envs, an env object given as ``env=``): the existing launches
+  per-step    everything else (general networks, host envs, an env object given as ``env=``, the VAE of a VAE-BC run:
+              saved_policy.VaePolicy, stochastic by construction): the existing launches
               per vector step -- Normalizer.apply, ConstraintActorCritic.step(deterministic=True, nets_mask=1) with
               ActionScale fused, env.step -- and the same float64 sums in the same order.
 ``OSA_EVAL_PATH=per-step|persistent`` forces a path (the persistent one raises when it cannot take the case).
@@ -104,7 +105,7 @@ class Evaluator:  # pylint: disable=too-many-instance-attributes
         self._cost_limit = float(a.cost_limit) if self._early_terminated else 0.0
         obs_dim, act_dim = self._env_dims()
         self._actor, self._normalizer = build_policy(self._cfgs, ck, obs_dim, act_dim, self._device,
-                                                     extra_inputs=int(self._saute))
+                                                     extra_inputs=int(self._saute), seed=self._seed)
 
     def _env_dims(self) -> tuple[int, int]:
         if self._user_env is not None:

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import Config
+from .config import BC_DEFAULTS, Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
 from .spaces import Box
@@ -36,9 +36,40 @@ def load_checkpoint(save_dir: str, model_name: str):
     return dict_cfgs, cfgs, torch.load(os.path.join(save_dir, 'torch_save', model_name), weights_only=False)
 
 
-def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: int = 0):
+class VaePolicy:
+    """The actor of a VAE-BC run for the per-step players: ``VAE.predict`` (models/actor/vae_actor.py:121-138) is
+    ``decode(obs)`` with a fresh standard-normal latent, so the policy is stochastic by construction and
+    ``deterministic`` is ignored.  The latent of call k is drawn on the device from Philox(seed, k, element)
+    (osa_vae_decode).  ``general`` keeps it off the persistent players, whose kernels hold a Gaussian actor."""
+
+    general = True
+
+    def __init__(self, cfgs, state, obs_dim: int, act_dim: int, device, seed: int) -> None:
+        from .vae_step import VaeDecoder, make_desc
+
+        m = cfgs.model_cfgs
+        self._dec = VaeDecoder(make_desc(obs_dim, act_dim, m.hidden_sizes, m.activation, 1), device)
+        self._dec.load_state_dict(state['pi'])
+        self._seed, self._calls, self._act_dim = int(seed), 0, int(act_dim)
+
+    def step(self, obs: torch.Tensor, deterministic: bool = False, nets_mask: int = 1, out: dict | None = None):
+        act = self._dec.decode(obs, None, seed=self._seed, offset=self._calls)
+        self._calls += 1
+        if out and 'scale' in out:  # ActionScale, as the Gaussian actors' step fuses it
+            dst, lo, hi, min_a, max_a = out['scale']
+            n, A = act.shape[0], self._act_dim
+            _lib.check(_lib.load().osa_action_scale(_lib.ptr(act), act.stride(0), _lib.ptr(dst), dst.stride(0), n, A,
+                                                    _lib.ptr(lo), _lib.ptr(hi), min_a, max_a, _lib.stream_ptr()),
+                       'osa_action_scale')
+        return (act,)
+
+
+def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: int = 0, seed: int = 0):
     """``(actor, normalizer)`` of a checkpoint (evaluator.py:174-177, 250-303); ``extra_inputs``: policy input columns
-    behind the observation (the Saute / Simmer safety column); ``normalizer`` is None without ``obs_normalize``."""
+    behind the observation (the Saute / Simmer safety column); ``normalizer`` is None without ``obs_normalize``.  A
+    VAE-BC run gives a ``VaePolicy`` whose latent draws are seeded by ``seed``."""
+    if str(getattr(cfgs, 'algo', '')) in BC_DEFAULTS:
+        return VaePolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     actor = ConstraintActorCritic(Box(-np.inf, np.inf, (obs_dim + extra_inputs,)), Box(-1.0, 1.0, (act_dim,)),
                                   cfgs.model_cfgs, epochs=1, device=device)
     actor.actor.load_state_dict(state['pi'])
