@@ -1161,6 +1161,98 @@ int osa_vae_decode(const osa_vae_desc* desc, int route, const float* decoder, co
                    const float* z, int ld_z, long n, unsigned long long seed, unsigned long long offset, float* out,
                    int ld_out, float* ws, size_t ws_floats, void* stream);
 
+/* ---- offline BCQ / BCQ-Lag (csrc/bcq_kernels.hip) ------------------------------------------------------------------
+ * Batch-Constrained Q-learning and its Lagrangian form trained from a device-resident dataset
+ * (omnisafe/algorithms/offline/bcq.py:122-213, bcq_lag.py:91-193).  Networks: the VAE of osa_vae_layout over the
+ * actor's hidden sizes (one block [Pe + Pd]), the perturbation network [obs_dim + act_dim, *hidden[0], act_dim] with a
+ * tanh output (block [Pp]) and `pairs` pairs of Q critics [obs_dim + act_dim, *hidden[1], 1] with a target copy each
+ * (blocks [Pc], in osa_crr_layout's order); every block in the padded layout of osa_crr_layout.  act_dim <= 32. */
+#define OSA_BCQ_NSTAT 16
+/* a step's statistics row: 0 Loss_vae, 1 Loss_recon, 2 Loss_kl, 3 Loss_reward_critic, 4 data_Qr, 5 target_Qr,
+ * 6 Loss_cost_critic, 7 data_Qc, 8 target_Qc, 9 Loss_actor, 10 current_Qr, 11 current_Qc, 12 LagrangeMultiplier; the Q
+ * entries are FIRST-ROW values (bcq.py:174-175, 197). */
+#define OSA_BCQ_ROUTE_LAYER 0 /* the target chain and predict as one tile-GEMM launch per layer */
+#define OSA_BCQ_ROUTE_FUSED 1 /* ... as ONE launch of the row-resident chain kernel (osa_bcq_chain_supported) */
+typedef struct osa_bcq_desc {
+  int obs_dim, act_dim;
+  int n_hidden[2];                     /* hidden layers of the actor's networks (VAE, perturbation) / of a critic */
+  int hidden[2][OSA_GMLP_MAX_LAYERS];  /* their widths */
+  int activation[2];                   /* OSA_ACT_* of the hidden layers */
+  int batch, samples, pairs;           /* B, sampled_action_num S, 1 (BCQ) or 2 (BCQ-Lag) */
+} osa_bcq_desc;
+typedef struct osa_bcq_hparams {
+  float gamma, cost_gamma;
+  float polyak, one_minus_polyak;            /* float32 roundings of tau and 1 - tau */
+  float phi;                                 /* the largest perturbation (perturbation_actor.py:90) */
+  float min_weight, one_minus_min_weight;    /* w and 1 - w of w min(q1, q2) + (1 - w) max(q1, q2) */
+  float lr_actor, lr_critic;                 /* lr_actor: the VAE's Adam and the perturbation network's */
+  double beta1, beta2, adam_eps;
+  float cost_limit, lambda_lr;
+  int lagrange_open; /* bcq_lag.py:166-170: epoch * steps_per_epoch > lagrange_start_step, constant over a block */
+  int route;         /* OSA_BCQ_ROUTE_* of the target chain */
+  int vae_route;     /* OSA_VAE_ROUTE_* of the VAE update */
+} osa_bcq_hparams;
+typedef struct osa_bcq_state {                /* device memory, 16-byte aligned blocks */
+  float *vae, *vae_m, *vae_v;                 /* [Pe + Pd] */
+  float *pert, *pert_m, *pert_v;              /* [Pp] */
+  float *critic, *critic_m, *critic_v;        /* [2 pairs][Pc] */
+  float* target;                              /* [2 pairs][Pc] */
+  int* adam_step;                             /* [4]: VAE, perturbation, reward pair, cost pair */
+  float* lagrange;                            /* [4]: lambda, its Adam m, v and step count (BCQ-Lag) */
+  long* step;                                 /* [2]: steps taken, advanced by every step on the device; [1] is the copy
+                                                 that the VAE update's launches read and advance (equal between steps) */
+  float* vae_stats;                           /* [nslots][OSA_VAE_NSTAT]: the VAE update's own row */
+} osa_bcq_state;
+typedef struct osa_bcq_draw_buffers {         /* step t reads slot t % nslots */
+  const long* idx;                            /* [nslots][B] in [0, N) */
+  const float *z_r, *z_c;                     /* [nslots][B S][2 act_dim]: the target chains' latents (z_c: BCQ-Lag) */
+  const float* eps;                           /* [nslots][B][2 act_dim]: the VAE update's rsample noise */
+  const float* z_a;                           /* [nslots][B][2 act_dim]: the actor update's latent */
+  int nslots;
+} osa_bcq_draw_buffers;
+/* out[0..5] = Pe, Pd, Pp, Pc, OSA_BCQ_NSTAT, 0; then (oW, ob, ld) of layers 0..OSA_GMLP_MAX_LAYERS-1 of the
+ * perturbation network and of a critic (-1, -1, 0 for absent layers): 6 + 48 ints; the VAE block is osa_vae_layout's.
+ * OSA_EUNSUPPORTED for no hidden layer, too many, act_dim > 32 or B S > 2^20.  Host only. */
+int osa_bcq_layout(const osa_bcq_desc* desc, int* out);
+/* floats of the step's workspace; 0 for a description osa_bcq_layout refuses.  Host only. */
+size_t osa_bcq_ws_floats(const osa_bcq_desc* desc);
+/* 1 when OSA_BCQ_ROUTE_FUSED takes the description: every hidden width of the decoder, the perturbation network and
+ * the critics <= 256 and the kernel's LDS (two [32][260] activation buffers, the K-split scratch and 32 rows of
+ * obs || z) within the compute unit's 160 KB.  Host only. */
+int osa_bcq_chain_supported(const osa_bcq_desc* desc);
+/* The draws of steps first_step .. first_step + nsteps - 1 into their slots: the scheme of osa_crr_draws with a key of
+ * its own per buffer (idx, z_r, z_c, eps, z_a), element = row * 2 act_dim + d.  z_c may be NULL with pairs == 1. */
+int osa_bcq_draws(const osa_bcq_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                  long n_rows, long* idx, float* z_r, float* z_c, float* eps, float* z_a, void* stream);
+/* nsteps train steps enqueued on `stream`.  Per step: (1) the no-grad target chain over the B S rows
+ * next_obs[idx[r / S]]: decoder(obs || z) -> act, a = act + phi tanh(perturbation(obs || act)), w min + (1 - w) max of
+ * the target pair -- one launch on OSA_BCQ_ROUTE_FUSED; (2) max over a row's S values (for the cost pair too, as
+ * bcq_lag.py:126-128 writes it), y = signal + (1 - done) gamma max, the online pair's MSE update, Adam with the Polyak
+ * update of the target fused in (the target is not read again in the step); (3) BCQ-Lag: the same for the cost pair
+ * with latents of its own; (4) the VAE update (osa_vae_step's launches, Adam at lr_actor); (5) the perturbation
+ * network's update on -mean(q1r - lambda q1c) through the UPDATED VAE and critics (lambda read before its update);
+ * (6) BCQ-Lag with lagrange_open: the multiplier's Adam step on mean(q1c), clamped at 0.  No host synchronisation, no
+ * allocation, no float atomics; the draws' slot and the row of stats [nslots][OSA_BCQ_NSTAT] follow *state->step, so a
+ * captured step advances on replay.  OSA_EINVAL before any launch for null pointers, a short or misaligned workspace;
+ * OSA_EUNSUPPORTED for what osa_bcq_layout refuses and for OSA_BCQ_ROUTE_FUSED where osa_bcq_chain_supported is 0. */
+int osa_bcq_step(const osa_bcq_desc* desc, const osa_bcq_hparams* hp, const osa_bcq_state* state,
+                 const osa_crr_data* data, const osa_bcq_draw_buffers* draws, float* stats, float* ws, size_t ws_floats,
+                 int nsteps, void* stream);
+/* The target chain alone, for inspection: out[B S] = the chain's values of pair `pair` over next_obs[idx[slot][r / S]]
+ * (slot = *state->step % nslots) with the given latents z [B S][2 act_dim].  ws as osa_bcq_step's. */
+int osa_bcq_target_q(const osa_bcq_desc* desc, const osa_bcq_hparams* hp, const osa_bcq_state* state,
+                     const osa_crr_data* data, const long* idx, int nslots, int pair, const float* z, float* out,
+                     float* ws, size_t ws_floats, void* stream);
+/* floats of osa_bcq_predict's workspace for n rows; 0 for a refused description or n < 1.  Host only. */
+size_t osa_bcq_predict_ws_floats(const osa_bcq_desc* desc, long n);
+/* PerturbationActor.predict (perturbation_actor.py:76-90) of n plain rows: out[r][0 .. act_dim) = act + phi
+ * tanh(perturbation(obs[r] || act)), act = decoder(obs[r] || z[r]).  z NULL: the latent is drawn on the device as
+ * osa_vae_decode draws it.  `decoder`: the decoder's block (vae + Pe).  desc->batch and samples are not read.
+ * n <= 2^20. */
+int osa_bcq_predict(const osa_bcq_desc* desc, int route, float phi, const float* decoder, const float* pert,
+                    const float* obs, int ld_obs, const float* z, int ld_z, long n, unsigned long long seed,
+                    unsigned long long offset, float* out, int ld_out, float* ws, size_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,15 @@ SIGNATURES: dict[str, tuple] = {
     'osa_vae_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
     'osa_vae_decode_ws_floats': (C.c_size_t, [_P, _L]),
     'osa_vae_decode': (_I, [_P, _I, _P, _P, _I, _P, _I, _L, _U, _U, _P, _I, _P, C.c_size_t, _P]),
+    # offline BCQ / BCQ-Lag (csrc/bcq_kernels.hip): structs of bcq_step.py, passed by reference
+    'osa_bcq_layout': (_I, [_P, _P]),
+    'osa_bcq_ws_floats': (C.c_size_t, [_P]),
+    'osa_bcq_chain_supported': (_I, [_P]),
+    'osa_bcq_draws': (_I, [_P, _U, _L, _I, _I, _L, _P, _P, _P, _P, _P, _P]),
+    'osa_bcq_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
+    'osa_bcq_target_q': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    'osa_bcq_predict_ws_floats': (C.c_size_t, [_P, _L]),
+    'osa_bcq_predict': (_I, [_P, _I, C.c_float, _P, _P, _P, _I, _P, _I, _L, _U, _U, _P, _I, _P, C.c_size_t, _P]),
 }
 
 

@@ -14,7 +14,7 @@ import os
 
 from . import distributed as dist
 from .algorithms import registry
-from .config import Config, check_all_configs, get_default_kwargs, recursive_check_config
+from .config import Config, check_all_configs, default_kwargs, recursive_check_config
 
 
 class Agent:  # the reference exposes AlgoWrapper under this name (omnisafe/__init__.py:25)
@@ -30,7 +30,7 @@ class Agent:  # the reference exposes AlgoWrapper under this name (omnisafe/__in
         if self.algo not in registry.REGISTRY._module_dict:  # noqa: SLF001
             raise AssertionError(f"{self.algo} doesn't exist in omnisafe_amd "
                                  f'({sorted(registry.REGISTRY._module_dict)})')  # noqa: SLF001
-        default = get_default_kwargs(self.algo)
+        default = default_kwargs(self.algo)
         cfgs = Config.dict2config(default)
         cfgs.recurisve_update({'exp_name': f'{self.algo}-{{{self.env_id}}}', 'env_id': self.env_id,
                                'algo': self.algo})

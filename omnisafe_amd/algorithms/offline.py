@@ -1,5 +1,6 @@
-"""Offline CRR, CCRR and VAE-BC trained on the device from a collected dataset -- mirror of
-omnisafe/algorithms/offline/base.py:32-152, crr.py:30-200, c_crr.py:30-206 and vae_bc.py:29-97.
+"""Offline CRR, CCRR, VAE-BC, BCQ and BCQ-Lag trained on the device from a collected dataset -- mirror of
+omnisafe/algorithms/offline/base.py:32-152, crr.py:30-200, c_crr.py:30-206, vae_bc.py:29-97, bcq.py:31-213 and
+bcq_lag.py:31-193.
 
     col.collect(data_dir)
     agent = omnisafe_amd.Agent('CCRR', env_id, custom_cfgs={'train_cfgs': {'dataset': '<data_dir>/<env_id>_data.npz'}})
@@ -33,7 +34,7 @@ from ..crr_step import CRR_STATS, STAT_KEYS, CrrStep, load_dataset, make_desc
 from ..evaluator import Evaluator
 from ..logger import Logger
 from ..saved_policy import device_env_class
-from .. import vae_step
+from .. import bcq_step, vae_step
 from .. import envs as envs_mod
 from .base_algo import BaseAlgo
 from .registry import register
@@ -229,4 +230,57 @@ class VAEBC(BaseOffline):
         self._step.run(n)
 
 
-__all__ = ['BaseOffline', 'CRR', 'CCRR', 'VAEBC']
+@register
+class BCQ(BaseOffline):
+    """Batch-Constrained Q-learning (bcq.py:31-213): bcq_step.BcqStep, csrc/bcq_kernels.hip.  The checkpoint's
+    ``actor`` is ``PerturbationActor.state_dict()``: ``_phi``, ``vae.*``, ``perturbation.*``."""
+
+    stat_keys = bcq_step.STAT_KEYS
+    base_columns = bcq_step.BCQ_STATS
+
+    def _init_model(self) -> None:
+        """bcq.py:78-120, bcq_lag.py:64-89: the actor (VAE, perturbation network), the reward pair, (BCQ-Lag) the cost
+        pair; the VAE and the perturbation network each have an Adam of their own at ``actor.lr``."""
+        m, a = self._cfgs.model_cfgs, self._cfgs.algo_cfgs
+        assert isinstance(m.actor.lr, float), 'The learning rate of actor must be a float number.'
+        assert isinstance(m.critic.lr, float), 'The learning rate of critic must be a float number.'
+        desc = bcq_step.make_desc(self._obs_dim, self._act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes,
+                                  m.actor.activation, m.critic.activation, a.batch_size, a.sampled_action_num, self.pairs)
+        lag = self._cfgs.lagrange_cfgs if self.pairs == 2 else None
+        if lag is not None and lag.lambda_optimizer != 'Adam':
+            raise NotImplementedError(f'lambda_optimizer {lag.lambda_optimizer!r}: the device Lagrange step is Adam')
+        self._nslots = min(int(a.steps_per_epoch), MAX_SLOTS)
+        self._step = bcq_step.BcqStep(
+            desc, None, gamma=float(a.gamma), polyak=float(a.polyak), phi=float(a.phi),
+            minimum_weighting=float(a.minimum_weighting), lr_actor=m.actor.lr, lr_critic=m.critic.lr,
+            nslots=self._nslots, cost_gamma=float(getattr(a, 'cost_gamma', a.gamma)),
+            cost_limit=float(lag.cost_limit) if lag else 0.0, lambda_lr=float(lag.lambda_lr) if lag else 0.0,
+            lambda_init=float(lag.lagrangian_multiplier_init) if lag else 0.0, device=self._device)
+        self._step.init_parameters(m.weight_initialization_mode)
+        self._actor = self._step  # (its state_dict() is the reference's PerturbationActor.state_dict())
+
+
+@register
+class BCQLag(BCQ):
+    """BCQ with a cost critic pair and a Lagrange multiplier (bcq_lag.py:31-193).  As the reference writes it
+    (bcq_lag.py:121-129), the cost target takes the max over the sampled actions and the ``minimum_weighting`` mix of
+    the target pair, like the reward target."""
+
+    pairs = 2
+
+    def _stat_columns(self) -> tuple[int, ...]:
+        return tuple(range(len(bcq_step.STAT_KEYS)))
+
+    def _init_log(self) -> None:
+        """bcq_lag.py:39-62."""
+        super()._init_log()
+        for col in (6, 7, 8, 11, 12):
+            self._logger.register_key(bcq_step.STAT_KEYS[col])
+
+    def _lagrange_open(self) -> bool:
+        """bcq_lag.py:166-169; constant over an epoch's block of steps."""
+        a = self._cfgs.algo_cfgs
+        return self.epoch * a.steps_per_epoch > a.lagrange_start_step
+
+
+__all__ = ['BaseOffline', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag']

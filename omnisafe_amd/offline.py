@@ -153,6 +153,9 @@ class OfflineDataCollector:  # pylint: disable=too-many-instance-attributes
         if algo == 'VAEBC':
             raise NotImplementedError('VAEBC: the collector\'s players draw the action noise of a Gaussian actor; a VAE '
                                       'policy draws a latent per step instead and is played by the Evaluator only')
+        if algo in ('BCQ', 'BCQLag'):
+            raise NotImplementedError(f'{algo}: the collector\'s players draw the action noise of a Gaussian actor; a BCQ '
+                                      'policy draws a latent per step instead and is played by the Evaluator only')
         actor, normalizer = build_policy(cfgs, model_params, self._obs_dim, self._act_dim, self._device)
 
         def agent_step(obs: torch.Tensor) -> torch.Tensor:

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import BC_DEFAULTS, Config
+from .config import BC_DEFAULTS, BCQ_DEFAULTS, Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
 from .spaces import Box
@@ -52,8 +52,11 @@ class VaePolicy:
         self._dec.load_state_dict(state['pi'])
         self._seed, self._calls, self._act_dim = int(seed), 0, int(act_dim)
 
+    def _act(self, obs: torch.Tensor) -> torch.Tensor:
+        return self._dec.decode(obs, None, seed=self._seed, offset=self._calls)
+
     def step(self, obs: torch.Tensor, deterministic: bool = False, nets_mask: int = 1, out: dict | None = None):
-        act = self._dec.decode(obs, None, seed=self._seed, offset=self._calls)
+        act = self._act(obs)
         self._calls += 1
         if out and 'scale' in out:  # ActionScale, as the Gaussian actors' step fuses it
             dst, lo, hi, min_a, max_a = out['scale']
@@ -64,12 +67,32 @@ class VaePolicy:
         return (act,)
 
 
+class BcqPolicy(VaePolicy):
+    """The actor of a BCQ / BCQ-Lag run for the per-step players: ``PerturbationActor.predict``
+    (models/actor/perturbation_actor.py:76-90), the VAE's decode of a fresh latent perturbed by at most ``phi`` --
+    osa_bcq_predict, one launch of the fused chain kernel where it takes the shape."""
+
+    def __init__(self, cfgs, state, obs_dim: int, act_dim: int, device, seed: int) -> None:  # pylint: disable=super-init-not-called
+        from .bcq_step import BcqActor, make_desc
+
+        m = cfgs.model_cfgs
+        self._dec = BcqActor(make_desc(obs_dim, act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes, m.actor.activation,
+                                       m.critic.activation), device, phi=float(cfgs.algo_cfgs.phi))
+        self._dec.load_state_dict(state['pi'])
+        self._seed, self._calls, self._act_dim = int(seed), 0, int(act_dim)
+
+    def _act(self, obs: torch.Tensor) -> torch.Tensor:
+        return self._dec.predict(obs, None, seed=self._seed, offset=self._calls)
+
+
 def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: int = 0, seed: int = 0):
     """``(actor, normalizer)`` of a checkpoint (evaluator.py:174-177, 250-303); ``extra_inputs``: policy input columns
     behind the observation (the Saute / Simmer safety column); ``normalizer`` is None without ``obs_normalize``.  A
-    VAE-BC run gives a ``VaePolicy`` whose latent draws are seeded by ``seed``."""
+    VAE-BC run gives a ``VaePolicy``, a BCQ / BCQ-Lag run a ``BcqPolicy``, whose latent draws are seeded by ``seed``."""
     if str(getattr(cfgs, 'algo', '')) in BC_DEFAULTS:
         return VaePolicy(cfgs, state, obs_dim, act_dim, device, seed), None
+    if str(getattr(cfgs, 'algo', '')) in BCQ_DEFAULTS:
+        return BcqPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     actor = ConstraintActorCritic(Box(-np.inf, np.inf, (obs_dim + extra_inputs,)), Box(-1.0, 1.0, (act_dim,)),
                                   cfgs.model_cfgs, epochs=1, device=device)
     actor.actor.load_state_dict(state['pi'])
