@@ -1253,6 +1253,77 @@ int osa_bcq_predict(const osa_bcq_desc* desc, int route, float phi, const float*
                     const float* obs, int ld_obs, const float* z, int ld_z, long n, unsigned long long seed,
                     unsigned long long offset, float* out, int ld_out, float* ws, size_t ws_floats, void* stream);
 
+/* ---- offline COptiDICE (csrc/dice_kernels.hip) ---------------------------------------------------------------------
+ * omnisafe/algorithms/offline/coptidice.py:30-323 trained from a device-resident dataset that carries init_obs
+ * (common/offline/dataset.py:262-380).  Networks: nu and chi, two ObsEncoder MLPs obs -> 1 (models/offline/dice.py:27-87)
+ * with shapes, activations and learning rates of their own, and a gaussian_learning actor (log_std behind the layers);
+ * every network is one padded float32 block in osa_crr_layout's layout.  Index 0 / 1 / 2 of the arrays = nu / chi /
+ * actor.  1 .. OSA_GMLP_MAX_LAYERS - 1 hidden layers each; batch <= 1024 (one workgroup forms the batch-wide softmax and
+ * means: one thread per row), OSA_EUNSUPPORTED above. */
+#define OSA_DICE_NSTAT 12
+/* a step's statistics row: 0 Loss_Nu, 1 Loss_Chi, 2 Loss_Lamb, 3 Loss_Tau, 4 CostUB, 5 KL_divergence, 6 tau, 7
+ * lagrange_multiplier (both after their update), 8 Loss_actor, 9 PolicyStd (after the actor's update), 10 - 11 unused */
+#define OSA_DICE_FN_KL 0
+#define OSA_DICE_FN_SOFTCHI 1
+#define OSA_DICE_FN_CHISQUARE 2
+#define OSA_DICE_ROUTE_LIST 0   /* one launch of the problem-list kernel per layer depth */
+#define OSA_DICE_ROUTE_SINGLE 1 /* the same kernel, every problem in a launch of its own (the timing comparison) */
+typedef struct osa_dice_desc {
+  int obs_dim, act_dim;
+  int n_hidden[3];
+  int hidden[3][OSA_GMLP_MAX_LAYERS];
+  int activation[3];                  /* OSA_ACT_* of the hidden layers */
+  int batch, fn_type;                 /* B, OSA_DICE_FN_* */
+} osa_dice_desc;
+typedef struct osa_dice_hparams {
+  float gamma, alpha, cost_limit, cost_ub_eps;
+  float lr_nu, lr_chi, lr_actor, lr_lamb, lr_tau;
+  double beta1, beta2, adam_eps;
+  int route;                          /* OSA_DICE_ROUTE_* */
+} osa_dice_hparams;
+typedef struct osa_dice_state {       /* device memory, 16-byte aligned blocks */
+  float *nu, *nu_m, *nu_v;            /* [Pnu] */
+  float *chi, *chi_m, *chi_v;         /* [Pchi] */
+  float *actor, *actor_m, *actor_v;   /* [Pa] */
+  int* adam_step;                     /* [2]: nu / chi / lambda / tau (one count), the actor */
+  float* mult;                        /* [8]: lambda, its Adam m, v, unused; tau, its Adam m, v, unused */
+  long* step;                         /* [1] steps taken: advanced by every step on the device */
+} osa_dice_state;
+typedef struct osa_dice_data {        /* the dataset: N rows of float32, never written */
+  const float *obs, *act, *reward, *cost, *next_obs, *done, *init_obs;
+  int ld_obs, ld_act, ld_next, ld_init;
+  long n_rows;
+} osa_dice_data;
+typedef struct osa_dice_draw_buffers { /* step t reads slot t % nslots */
+  const long* idx;                    /* [nslots][B] in [0, N) */
+  int nslots;
+} osa_dice_draw_buffers;
+/* out[0..5] = Pnu, Pchi, Pa, offset of log_std in the actor block, OSA_DICE_NSTAT, the largest batch; then (oW, ob, ld)
+ * of layers 0..OSA_GMLP_MAX_LAYERS-1 of nu, chi and the actor (-1, -1, 0 for absent layers): 6 + 72 ints.
+ * OSA_EUNSUPPORTED for a network without a hidden layer or with too many, an unknown fn_type, batch > 1024.  Host only. */
+int osa_dice_layout(const osa_dice_desc* desc, int* out);
+/* floats of the step's workspace; 0 for a description the layout call refuses.  Host only. */
+size_t osa_dice_ws_floats(const osa_dice_desc* desc);
+/* The draws of steps first_step .. first_step + nsteps - 1 into their slots (dataset.py:237-247's randint): the index
+ * scheme of the CRR draws with a key of its own, 0x44494345494458.  COptiDICE draws nothing else: the sample that
+ * actor.predict draws in coptidice.py:257 is discarded. */
+int osa_dice_draws(const osa_dice_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                   long n_rows, long* idx, void* stream);
+/* nsteps train steps enqueued on `stream` (coptidice.py:162-275 per step): (1) nu and chi over obs[idx] || next_obs[idx]
+ * || init_obs[idx], one launch per hidden depth (:186-199); (2) the heads, w, f(w), the losses, the batch softmax, both
+ * heads' gradients and the Adam steps and clamps of lambda and tau in one workgroup (:188-233); (3) both backward passes,
+ * one launch per depth, and one Adam launch over nu and chi (:217-223); (4) the updated nu over obs || next_obs together
+ * with the actor over obs, w with the updated lambda, the weighted log-likelihood step of the actor (:257-268).  No host
+ * synchronisation, no allocation, no float atomics, fixed reduction orders; the draws' slot and the row of stats
+ * [nslots][OSA_DICE_NSTAT] follow *state->step, so a captured step advances on replay.  OSA_EINVAL before any launch for
+ * null pointers, a short or misaligned workspace, alpha <= 0; OSA_EUNSUPPORTED for what the layout call refuses. */
+int osa_dice_step(const osa_dice_desc* desc, const osa_dice_hparams* hp, const osa_dice_state* state,
+                  const osa_dice_data* data, const osa_dice_draw_buffers* draws, float* stats, float* ws,
+                  size_t ws_floats, int nsteps, void* stream);
+/* nu(obs[r]) and chi(obs[r]) of n <= 3 batch plain rows (ObsEncoder.forward, dice.py:77-87); ws as the step's. */
+int osa_dice_values(const osa_dice_desc* desc, int route, const float* nu, const float* chi, const float* obs, int ld_obs,
+                    long n, float* out_nu, float* out_chi, float* ws, size_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,12 @@ SIGNATURES: dict[str, tuple] = {
     'osa_bcq_target_q': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     'osa_bcq_predict_ws_floats': (C.c_size_t, [_P, _L]),
     'osa_bcq_predict': (_I, [_P, _I, C.c_float, _P, _P, _P, _I, _P, _I, _L, _U, _U, _P, _I, _P, C.c_size_t, _P]),
+    # offline COptiDICE (csrc/dice_kernels.hip): structs of dice_step.py, passed by reference
+    'osa_dice_layout': (_I, [_P, _P]),
+    'osa_dice_ws_floats': (C.c_size_t, [_P]),
+    'osa_dice_draws': (_I, [_P, _U, _L, _I, _I, _L, _P, _P]),
+    'osa_dice_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
+    'osa_dice_values': (_I, [_P, _I, _P, _P, _P, _I, _L, _P, _P, _P, C.c_size_t, _P]),
 }
 
 

@@ -6,11 +6,12 @@ from .siblings import (CPPOPID, CUP, FOCOPS, IPO, P3O, PCPO, PDO, RCPO, TRPOPID,
                        PPOSimmerPID, TRPOSaute, TRPOSimmerPID)
 
 ALGORITHMS = {'on-policy': tuple(sorted(registry.REGISTRY._module_dict))}  # noqa: SLF001
-from .offline import BCQ, CCRR, CRR, VAEBC, BCQLag  # noqa: E402  (after the on-policy tuple: the registry holds every family)
+from .offline import BCQ, CCRR, CRR, VAEBC, BCQLag, COptiDICE  # noqa: E402  (after the on-policy tuple: the registry holds every family)
 
 ALGORITHMS['offline'] = ('CCRR', 'CRR')
 ALGORITHMS['offline-bc'] = ('VAEBC',)
+ALGORITHMS['offline-dice'] = ('COptiDICE',)
 ALGORITHMS['offline-bcq'] = ('BCQ', 'BCQLag')
-__all__ = ['CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
+__all__ = ['CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'COptiDICE', 'PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
            'OnCRPO', 'CPPOPID', 'TRPOPID', 'PCPO', 'FOCOPS', 'CUP', 'P3O', 'PPOSaute', 'TRPOSaute',
            'PPOSimmerPID', 'TRPOSimmerPID', 'registry', 'ALGORITHMS']

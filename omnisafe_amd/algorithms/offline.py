@@ -1,6 +1,6 @@
-"""Offline CRR, CCRR, VAE-BC, BCQ and BCQ-Lag trained on the device from a collected dataset -- mirror of
-omnisafe/algorithms/offline/base.py:32-152, crr.py:30-200, c_crr.py:30-206, vae_bc.py:29-97, bcq.py:31-213 and
-bcq_lag.py:31-193.
+"""Offline CRR, CCRR, VAE-BC, BCQ, BCQ-Lag and COptiDICE trained on the device from a collected dataset -- mirror of
+omnisafe/algorithms/offline/base.py:32-152, crr.py:30-200, c_crr.py:30-206, vae_bc.py:29-97, bcq.py:31-213,
+bcq_lag.py:31-193 and coptidice.py:30-323.
 
     col.collect(data_dir)
     agent = omnisafe_amd.Agent('CCRR', env_id, custom_cfgs={'train_cfgs': {'dataset': '<data_dir>/<env_id>_data.npz'}})
@@ -34,7 +34,7 @@ from ..crr_step import CRR_STATS, STAT_KEYS, CrrStep, load_dataset, make_desc
 from ..evaluator import Evaluator
 from ..logger import Logger
 from ..saved_policy import device_env_class
-from .. import bcq_step, vae_step
+from .. import bcq_step, dice_step, vae_step
 from .. import envs as envs_mod
 from .base_algo import BaseAlgo
 from .registry import register
@@ -95,10 +95,13 @@ class BaseOffline(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         self._step.init_parameters(m.weight_initialization_mode)
         self._actor = _ActorState(self._step)
 
+    def _load_data(self, source) -> dict:
+        return load_dataset(source, self._obs_dim, self._act_dim, self._device)
+
     def _init(self) -> None:
         """base.py:42-47: the dataset, on the device."""
         source = self._cfgs.train_cfgs.dataset
-        self._step.set_data(load_dataset(source, self._obs_dim, self._act_dim, self._device))
+        self._step.set_data(self._load_data(source))
         self._dataset_name = (os.path.splitext(os.path.basename(os.fspath(source)))[0]
                               if isinstance(source, (str, os.PathLike)) else f'{self._env_id}_data')
         if not isinstance(source, (str, os.PathLike)):  # (config.json holds the run's settings, not a collector)
@@ -283,4 +286,37 @@ class BCQLag(BCQ):
         return self.epoch * a.steps_per_epoch > a.lagrange_start_step
 
 
-__all__ = ['BaseOffline', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag']
+@register
+class COptiDICE(BaseOffline):
+    """Offline constrained RL by stationary distribution correction (coptidice.py:30-323): dice_step.DiceStep,
+    csrc/dice_kernels.hip.  The checkpoint's ``actor`` is the Gaussian actor's state dict.  Kept as the reference writes
+    them: ``actor.predict`` draws and discards a sample (coptidice.py:257: nothing is drawn here), ``polyak`` is read
+    by nothing."""
+
+    stat_keys = dice_step.STAT_KEYS
+    base_columns = tuple(range(len(dice_step.STAT_KEYS)))
+
+    def _init_model(self) -> None:
+        """coptidice.py:93-160: the actor, nu, chi with an Adam each, lambda and tau with a scalar Adam each."""
+        m, a = self._cfgs.model_cfgs, self._cfgs.algo_cfgs
+        assert isinstance(m.actor.lr, float), 'The learning rate must be a float number.'
+        nets = {'nu': m.nu, 'chi': m.chi, 'actor': m.actor}
+        desc = dice_step.make_desc(self._obs_dim, self._act_dim, {k: v.hidden_sizes for k, v in nets.items()},
+                                   {k: v.activation for k, v in nets.items()}, a.batch_size, a.fn_type)
+        self._nslots = min(int(a.steps_per_epoch), MAX_SLOTS)
+        self._step = dice_step.DiceStep(
+            desc, None, gamma=float(a.gamma), alpha=float(a.alpha), cost_limit=float(a.cost_limit),
+            cost_ub_eps=float(a.cost_ub_eps), lr_nu=float(m.nu.lr), lr_chi=float(m.chi.lr), lr_actor=m.actor.lr,
+            lr_lamb=float(m.lamb.lr), lr_tau=float(m.tau.lr), lamb_init=float(m.lamb.init), tau_init=float(m.tau.init),
+            nslots=self._nslots, device=self._device)
+        self._step.init_parameters(m.weight_initialization_mode)
+        self._actor = _ActorState(self._step)
+
+    def _load_data(self, source) -> dict:
+        """coptidice.py:40-46: the dataset with the first observation of every row's episode."""
+        data = super()._load_data(source)
+        data['init_obs'] = dice_step.load_init_obs(source, data)
+        return data
+
+
+__all__ = ['BaseOffline', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'COptiDICE']

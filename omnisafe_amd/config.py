@@ -201,6 +201,22 @@ _BCQLAG['algo_cfgs'].update({'cost_gamma': 0.99, 'lagrange_start_step': 150000})
 _BCQLAG['lagrange_cfgs'] = copy.deepcopy(_CCRR['lagrange_cfgs'])
 BCQ_DEFAULTS = {'BCQ': _BCQ, 'BCQLag': _BCQLAG}
 
+# ---- COptiDICE (configs/offline/COptiDICE.yaml): no critic; nu, chi and the two multipliers have blocks of their own.
+# A table of its own like BCQ's.  `polyak` is in the YAML and read by nothing (coptidice.py never uses it).
+_DICE_NET = {'hidden_sizes': [256, 256, 256], 'activation': 'relu', 'lr': 0.003}
+_COPTIDICE = {
+    'seed': 0,
+    'train_cfgs': copy.deepcopy(_CRR['train_cfgs']),
+    'algo_cfgs': {'gamma': 0.99, 'batch_size': 256, 'steps_per_epoch': 1000, 'fn_type': 'softchi', 'alpha': 0.0008,
+                  'cost_ub_eps': 0.05, 'cost_limit': 0.06, 'polyak': 0.005},
+    'logger_cfgs': copy.deepcopy(_CRR['logger_cfgs']),
+    'model_cfgs': {'weight_initialization_mode': 'kaiming_uniform', 'actor': copy.deepcopy(_DICE_NET),
+                   'nu': copy.deepcopy(_DICE_NET), 'chi': copy.deepcopy(_DICE_NET),
+                   'lamb': {'init': 0, 'lr': 0.035}, 'tau': {'init': 1, 'lr': 0.003}},
+    'env_cfgs': {},
+}
+DICE_DEFAULTS = {'COptiDICE': _COPTIDICE}
+
 # ---- behaviour cloning (configs/offline/VAEBC.yaml): one VAE, no actor / critic blocks, no gamma.  A table of its
 # own: the entries of OFFLINE_DEFAULTS all carry the actor-critic keys.  Same deviations as above.
 _VAEBC = {
@@ -230,8 +246,9 @@ def default_kwargs(algo: str) -> dict:
     """The defaults of any registered algorithm: what ``Agent`` reads.  ``get_default_kwargs`` keeps to the three
     tables it was written for -- tests/test_crr_cpu.py and tests/test_vae_cpu.py hold it to a KeyError for 'BCQ' --
     so the BCQ family is looked up here, in its own table."""
-    if algo in BCQ_DEFAULTS:
-        return copy.deepcopy(BCQ_DEFAULTS[algo])
+    for table in (BCQ_DEFAULTS, DICE_DEFAULTS):
+        if algo in table:
+            return copy.deepcopy(table[algo])
     return get_default_kwargs(algo)
 
 
@@ -249,11 +266,13 @@ def check_all_configs(cfgs: Config) -> None:
     """Subset of config.py:265-409 that guards this path."""
     a = cfgs.algo_cfgs
     algo = getattr(cfgs, 'algo', None)
-    if algo in OFFLINE_DEFAULTS or algo in BC_DEFAULTS or algo in BCQ_DEFAULTS:  # (none of the on-policy keys)
-        t = cfgs.train_cfgs
+    if algo in OFFLINE_DEFAULTS or algo in BC_DEFAULTS or algo in BCQ_DEFAULTS or algo in DICE_DEFAULTS:
+        t = cfgs.train_cfgs  # (none of the on-policy keys)
         assert isinstance(a.steps_per_epoch, int) and a.steps_per_epoch > 0
         assert isinstance(a.batch_size, int) and a.batch_size > 0
-        if algo not in BC_DEFAULTS:  # (behaviour cloning has no critic: no samples, discount or target network)
+        if algo in DICE_DEFAULTS:  # (no critic either: a divergence, its regulariser and the two thresholds)
+            assert 0.0 <= a.gamma <= 1.0 and a.alpha > 0 and a.fn_type in ('kl', 'softchi', 'chisquare')
+        elif algo not in BC_DEFAULTS:  # (behaviour cloning has no critic: no samples, discount or target network)
             assert isinstance(a.sampled_action_num, int) and a.sampled_action_num > 0
             assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0
             if algo in BCQ_DEFAULTS:  # (no advantage temperature: beta is CRR's)

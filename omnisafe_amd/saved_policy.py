@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import BC_DEFAULTS, BCQ_DEFAULTS, Config
+from .config import BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
 from .spaces import Box
@@ -85,6 +85,17 @@ class BcqPolicy(VaePolicy):
         return self._dec.predict(obs, None, seed=self._seed, offset=self._calls)
 
 
+class _ActorOnly:
+    """The ``model_cfgs`` of a COptiDICE run as ``ConstraintActorCritic`` reads them: the critics, which no player
+    evaluates, take the actor's shape."""
+
+    def __init__(self, model_cfgs) -> None:
+        self._m = model_cfgs
+
+    def __getattr__(self, key):
+        return self._m.actor if key == 'critic' else getattr(self._m, key)
+
+
 def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: int = 0, seed: int = 0):
     """``(actor, normalizer)`` of a checkpoint (evaluator.py:174-177, 250-303); ``extra_inputs``: policy input columns
     behind the observation (the Saute / Simmer safety column); ``normalizer`` is None without ``obs_normalize``.  A
@@ -93,8 +104,11 @@ def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: 
         return VaePolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     if str(getattr(cfgs, 'algo', '')) in BCQ_DEFAULTS:
         return BcqPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
+    model_cfgs = cfgs.model_cfgs
+    if str(getattr(cfgs, 'algo', '')) in DICE_DEFAULTS:  # (a Gaussian actor and no critic: the players read the actor)
+        model_cfgs = _ActorOnly(model_cfgs)
     actor = ConstraintActorCritic(Box(-np.inf, np.inf, (obs_dim + extra_inputs,)), Box(-1.0, 1.0, (act_dim,)),
-                                  cfgs.model_cfgs, epochs=1, device=device)
+                                  model_cfgs, epochs=1, device=device)
     actor.actor.load_state_dict(state['pi'])
     normalizer = None
     if getattr(cfgs.algo_cfgs, 'obs_normalize', False):  # (absent in an offline run: that family has no normaliser)
