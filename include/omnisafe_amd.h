@@ -1324,6 +1324,98 @@ int osa_dice_step(const osa_dice_desc* desc, const osa_dice_hparams* hp, const o
 int osa_dice_values(const osa_dice_desc* desc, int route, const float* nu, const float* chi, const float* obs, int ld_obs,
                     long n, float* out_nu, float* out_chi, float* ws, size_t ws_floats, void* stream);
 
+/* ---- off-policy TD3 / DDPG (csrc/td3_kernels.hip) --------------------------------------------------------------------
+ * One gradient step of omnisafe/algorithms/off_policy/ddpg.py:382-547 and td3.py:50-116 from a replay ring on the
+ * device.  Networks: the deterministic actor (MLPActor: hidden layers, a tanh head) with its target, num_critics reward
+ * Q critics on obs || act with their targets and, with use_cost, ONE cost critic with its target
+ * (constraint_actor_q_critic.py:70-78).  Blocks are padded as osa_crr_layout pads them; the critic blocks are
+ * [num_critics + use_cost][Pc]: the reward critics, then the cost critic. */
+#define OSA_TD3_NSTAT 8
+/* a statistics row: 0 Loss/Loss_reward_critic, 1 Value/reward_critic, 2 Loss/Loss_pi (0 on a step without an actor
+ * update), 3 Loss/Loss_cost_critic, 4 Value/cost_critic */
+#define OSA_TD3_ROUTE_LAYER 0 /* the step's forward as one tile-GEMM launch per layer */
+#define OSA_TD3_ROUTE_FUSED 1 /* ... as ONE launch of the row-resident kernel (osa_td3_chain_supported) */
+typedef struct osa_td3_desc {
+  int obs_dim, act_dim;
+  int n_hidden[2];                     /* hidden layers of the actor, of a critic */
+  int hidden[2][OSA_GMLP_MAX_LAYERS];  /* their widths */
+  int activation[2];                   /* OSA_ACT_* of the hidden layers */
+  int batch, num_critics, use_cost;    /* B; 1 (DDPG) or 2 (TD3); 0 or 1 */
+} osa_td3_desc;
+typedef struct osa_td3_hparams {
+  float gamma, polyak, one_minus_polyak;
+  float policy_noise, policy_noise_clip; /* td3.py:78-84; policy_noise 0: no noise term (DDPG) */
+  int target_actor;                      /* 1: the reward target's action comes from the target actor (td3.py:77), 0: from
+                                          * the online actor (ddpg.py:424).  The cost target's always does (ddpg.py:471). */
+  int policy_delay;                      /* the actor steps and every Polyak update run when update count % delay == 0 */
+  float lr_actor, lr_critic;
+  double beta1, beta2, adam_eps;
+  float max_grad_norm;                   /* clip_grad_norm_ per optimiser; 0: none */
+  float critic_norm_coeff;               /* ddpg.py:430-432, the coefficient; 0: use_critic_norm off */
+  int route;                             /* OSA_TD3_ROUTE_* */
+} osa_td3_hparams;
+typedef struct osa_td3_state {                /* device memory, 16-byte aligned blocks */
+  float *actor, *actor_m, *actor_v, *actor_t; /* [Pa]: parameters, Adam moments, target */
+  float *critic, *critic_m, *critic_v, *critic_t; /* [num_critics + use_cost][Pc] */
+  int* adam_step;                             /* [3]: actor, reward critics, cost critic */
+  long* step;                                 /* update steps done: the draws' slot and the statistics row follow it */
+} osa_td3_state;
+typedef struct osa_td3_ring {                 /* the replay ring: `size` rows of float32 */
+  float *obs, *act, *reward, *cost, *done, *next_obs;
+  long* pos;                                  /* [2] on the device: the write position, the rows filled */
+  long size;
+  int ld_obs, ld_act;
+} osa_td3_ring;
+typedef struct osa_td3_draw_buffers {         /* step t reads slot t % nslots */
+  long* idx;                                  /* [nslots][B] ring rows */
+  float* eps;                                 /* [nslots][B][act_dim] standard normals of the target-policy noise */
+  int nslots;
+} osa_td3_draw_buffers;
+/* out[0..3] = Pa, Pc, OSA_TD3_NSTAT, 0; then (oW, ob, ld) of layers 0..OSA_GMLP_MAX_LAYERS-1 of the actor and of a
+ * critic (-1, -1, 0 for absent layers): 4 + 48 ints.  OSA_EUNSUPPORTED for no hidden layer, too many, act_dim > 32,
+ * num_critics outside 1..2 or batch > 2^20.  Host only. */
+int osa_td3_layout(const osa_td3_desc* desc, int* out);
+/* floats of the step's workspace; 0 for a description osa_td3_layout refuses.  Host only. */
+size_t osa_td3_ws_floats(const osa_td3_desc* desc);
+/* 1 when OSA_TD3_ROUTE_FUSED takes the description: every hidden width of the actor and the critic <= 256 and
+ * obs_dim + act_dim within the kernel's LDS budget.  Host only. */
+int osa_td3_chain_supported(const osa_td3_desc* desc);
+/* n transitions (rows of the env's step buffers; done = terminated, uint8) into the ring at the device-held write
+ * position, which advances with the fill count.  final_obs / final_mask non-NULL: a row whose mask byte is set stores
+ * final_obs as its next_obs (off_policy_adapter.py: the observation before the auto-reset).  ep_acc [n][3], ep_out
+ * [ep_cap][3], ep_count non-NULL: the running return, cost and length of every env; a row with terminated or truncated
+ * set appends them to ep_out at *ep_count (dropped beyond ep_cap) and starts over.  One launch. */
+int osa_td3_store(const osa_td3_ring* ring, int n, int obs_dim, int act_dim, const float* obs, int ld_obs,
+                  const float* act, int ld_act, const float* reward, const float* cost, const unsigned char* terminated,
+                  const unsigned char* truncated, const float* next_obs, int ld_next, const float* final_obs, int ld_final,
+                  const unsigned char* final_mask, float* ep_acc, float* ep_out, long ep_cap, long* ep_count, void* stream);
+/* The draws of steps first_step .. first_step + nsteps - 1 into their slots, one launch: idx uniform over the rows the
+ * ring holds WHEN THE LAUNCH RUNS (ring->pos[1], read on the device; 64 Philox bits, multiply-high), eps the first
+ * Box-Muller normal of element row * act_dim + d.  Keys seed ^ 0x54443349445831 and seed ^ 0x54443345505331, counter
+ * (step, element). */
+int osa_td3_draws(const osa_td3_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                  const osa_td3_ring* ring, long* idx, float* eps, void* stream);
+/* nsteps gradient steps enqueued on `stream`; update_count: the steps done before the call (= *state->step, which the
+ * host mirrors so that it knows the actor steps without reading the device).  Per step: (1) the forward -- on
+ * OSA_TD3_ROUTE_FUSED ONE launch: per 32-row tile the rows of slot idx straight from the ring, the target chain on
+ * next_obs (actor with a tanh head, + clamp(policy_noise eps, +-clip), clamp to [-1, 1], the target critics, min,
+ * y = r + gamma (1 - done) min; with use_cost the online actor without noise and the cost target critic), then the
+ * online critics on obs || act with every layer's output written once to the workspace, dq = 2 (q - y) / B and the rows'
+ * squared errors; (2) the critics' backward, one launch per layer and kind; (3) per optimiser the fixed-order gradient
+ * norm (with the L2 term 2 coeff W added) and Adam with the clip scale; on actor steps the Polyak update of the critic
+ * targets rides on it; (4) on actor steps: the actor on obs, critic 1 on obs || pi(obs), its data gradient down to the
+ * action columns, tanh', the actor's backward, norm, Adam with the target actor's Polyak update.  No host
+ * synchronisation, no allocation, no atomics.  OSA_EINVAL before any launch for null pointers, a short or misaligned
+ * workspace; OSA_EUNSUPPORTED for what osa_td3_layout refuses and for the fused route where it is not supported. */
+int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* state,
+                 const osa_td3_ring* ring, const osa_td3_draw_buffers* draws, float* stats, float* ws, size_t ws_floats,
+                 long update_count, int nsteps, void* stream);
+/* Actions of n <= 1024 rows, one small VALU workgroup per row.  mode 0: tanh-headed actor forward + noise * normal,
+ * clamped to [-1, 1] (noise 0: the deterministic action); mode 1: uniform over [-1, 1] (use_rand_action).  Draws:
+ * Philox(seed ^ 0x54443341435431, offset, row * act_dim + d). */
+int osa_td3_act(const osa_td3_desc* desc, const float* actor, const float* obs, int ld_obs, long n, int mode,
+                float noise, unsigned long long seed, unsigned long long offset, float* out, int ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,14 @@ SIGNATURES: dict[str, tuple] = {
     'osa_dice_draws': (_I, [_P, _U, _L, _I, _I, _L, _P, _P]),
     'osa_dice_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
     'osa_dice_values': (_I, [_P, _I, _P, _P, _P, _I, _L, _P, _P, _P, C.c_size_t, _P]),
+    # off-policy TD3 / DDPG (csrc/td3_kernels.hip): structs of td3_step.py, passed by reference
+    'osa_td3_layout': (_I, [_P, _P]),
+    'osa_td3_ws_floats': (C.c_size_t, [_P]),
+    'osa_td3_chain_supported': (_I, [_P]),
+    'osa_td3_store': (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _L, _P, _P]),
+    'osa_td3_draws': (_I, [_P, _U, _L, _I, _I, _P, _P, _P, _P]),
+    'osa_td3_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _L, _I, _P]),
+    'osa_td3_act': (_I, [_P, _P, _P, _I, _L, _I, C.c_float, _U, _U, _P, _I, _P]),
 }
 
 

@@ -1,0 +1,230 @@
+"""Off-policy DDPG and TD3 trained on the device from a replay ring -- mirror of
+omnisafe/algorithms/off_policy/ddpg.py:40-565, td3.py:28-116 and adapter/offpolicy_adapter.py.
+
+    agent = omnisafe_amd.Agent('TD3', 'SynthNavGoal1-v0')
+    agent.learn(); agent.evaluate()
+
+The env, the ring, the networks and the draws all live on the device.  An epoch is enqueued on one stream with no host
+read inside it: ``steps_per_epoch / (update_cycle num_envs)`` rounds of act -> ``env.step`` -> store -> (``update_iters``
+gradient steps of td3_step.Td3Step once ``step > start_learning_steps``).  Episode returns, costs and lengths are
+accumulated on the device and read once at the epoch's end together with the steps' statistics rows.
+
+Deviations from the reference:
+  * The env must be a device env (a built-in family or one of ``register_device_env``); a host env raises
+    NotImplementedError.
+  * ``obs_normalize``, ``reward_normalize``, ``cost_normalize`` and ``linear_lr_decay`` set to True raise
+    NotImplementedError (the YAML default is False for all four).
+  * One ring of ``size`` rows shared by the envs, written ``vector_env_nums`` rows at a time (the reference keeps
+    ``size`` rows per env).
+  * All draws (warm-up actions, exploration noise, minibatch indices, target-policy noise) are Philox streams on the
+    device keyed by the seed and the step.
+  * The epoch's evaluation plays its ``eval_episodes`` side by side through ``Evaluator``.
+"""
+from __future__ import annotations
+
+import time
+
+import torch
+
+from .. import envs as envs_mod
+from .. import td3_step
+from ..evaluator import Evaluator
+from ..logger import Logger
+from ..saved_policy import device_env_class
+from .base_algo import BaseAlgo
+from .registry import register
+
+K = td3_step.STAT_KEYS
+
+
+class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
+    """ddpg.py:40-565 around a Td3Step."""
+
+    num_critics = 1
+
+    def _hparams(self) -> dict:
+        """DDPG: TD3 with one critic, no target-policy noise and the online actor in the target (ddpg.py:424)."""
+        return dict(policy_noise=0.0, policy_noise_clip=0.0, target_actor=False)
+
+    # ------------------------------------------------------------------ construction, in the reference's order
+    def _init_env(self) -> None:
+        """ddpg.py:51-92."""
+        t, a, m = self._cfgs.train_cfgs, self._cfgs.algo_cfgs, self._cfgs.model_cfgs
+        if device_env_class(self._env_id) is None:
+            raise NotImplementedError(f'{self._env_id} is a host env: the off-policy family trains on device envs only '
+                                      '(the built-in families and those of register_device_env)')
+        for name, on in (('obs_normalize', a.obs_normalize), ('reward_normalize', a.reward_normalize),
+                         ('cost_normalize', a.cost_normalize), ('linear_lr_decay', m.linear_lr_decay)):
+            if on:
+                raise NotImplementedError(f'{name}=True is not implemented for the off-policy family')
+        self._num_envs = int(t.vector_env_nums)
+        env_cfgs = dict(self._cfgs.env_cfgs.todict()) if hasattr(self._cfgs, 'env_cfgs') else {}
+        self._env = envs_mod.make(self._env_id, num_envs=self._num_envs, device=self._device, **env_cfgs)
+        self._env.set_seed(self._seed)
+        self._obs_dim, self._act_dim = (int(self._env.observation_space.shape[0]),
+                                        int(self._env.action_space.shape[0]))
+        assert a.steps_per_epoch % self._num_envs == 0, \
+            'The number of steps per epoch is not divisible by the number of environments.'
+        assert int(t.total_steps) % a.steps_per_epoch == 0, \
+            'The total number of steps is not divisible by the number of steps per epoch.'
+        self._epochs = int(t.total_steps) // a.steps_per_epoch
+        self._steps_per_epoch = a.steps_per_epoch // self._num_envs
+        self._update_cycle = int(a.update_cycle)
+        assert self._steps_per_epoch % self._update_cycle == 0, \
+            'The number of steps per epoch is not divisible by the number of steps per sample.'
+        self._samples_per_epoch = self._steps_per_epoch // self._update_cycle
+
+    def _init_model(self) -> None:
+        """ddpg.py:94-133: actor, critics, targets, the ring."""
+        m, a = self._cfgs.model_cfgs, self._cfgs.algo_cfgs
+        m.critic.recurisve_update({'num_critics': self.num_critics})
+        desc = td3_step.make_desc(self._obs_dim, self._act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes,
+                                  m.actor.activation, m.critic.activation, a.batch_size, self.num_critics, a.use_cost)
+        self._nslots = self._samples_per_epoch * int(a.update_iters)
+        self._step = td3_step.Td3Step(
+            desc, size=int(a.size), gamma=float(a.gamma), polyak=float(a.polyak), lr_actor=float(m.actor.lr),
+            lr_critic=float(m.critic.lr), nslots=self._nslots, policy_delay=int(a.policy_delay),
+            max_grad_norm=float(a.max_grad_norm or 0.0),
+            critic_norm_coeff=float(a.critic_norm_coeff) if a.use_critic_norm else 0.0, device=self._device,
+            **self._hparams())
+        self._step.init_parameters(m.weight_initialization_mode)
+
+    def _init(self) -> None:
+        f32 = dict(dtype=torch.float32, device=self._device)
+        cap = self._samples_per_epoch * self._update_cycle * self._num_envs
+        self._episodes = (torch.zeros(self._num_envs, 3, **f32), torch.zeros(cap, 3, **f32),
+                          torch.zeros(1, dtype=torch.int64, device=self._device))
+        self._act = torch.zeros(self._num_envs, self._act_dim, **f32)
+        self._obs = None
+        self._env_steps = 0     # vector steps taken: the Philox offset of the acting draws
+        self.total_env_steps = 0
+        self.epoch_stats: list = []  # per epoch: the rounds' statistics rows (zeros before learning starts)
+
+    def _init_log(self) -> None:
+        """ddpg.py:135-252."""
+        lc, a = self._cfgs.logger_cfgs, self._cfgs.algo_cfgs
+        self._logger = Logger(output_dir=lc.log_dir, exp_name=self._cfgs.exp_name, seed=self._cfgs.seed,
+                              use_tensorboard=lc.use_tensorboard, use_wandb=lc.use_wandb, config=self._cfgs,
+                              verbose=bool(getattr(lc, 'verbose', True)))
+        self._logger.setup_torch_saver({'pi': self._step})
+        self._logger.torch_save()
+        keys = [('Metrics/EpRet', lc.window_lens), ('Metrics/EpCost', lc.window_lens), ('Metrics/EpLen', lc.window_lens)]
+        if self._cfgs.train_cfgs.eval_episodes > 0:
+            keys += [(k, lc.window_lens) for k in ('Metrics/TestEpRet', 'Metrics/TestEpCost', 'Metrics/TestEpLen')]
+        keys += [(k, None) for k in ('Train/Epoch', 'Train/LR', 'TotalEnvSteps') + K[:3]]
+        if a.use_cost:
+            keys += [(k, None) for k in K[3:]]
+        keys += [(k, None) for k in ('Time/Total', 'Time/Rollout', 'Time/Update', 'Time/Evaluate', 'Time/Epoch',
+                                     'Time/FPS')]
+        for key, window in keys:
+            self._logger.register_key(key, window_length=window)
+
+    # ------------------------------------------------------------------ training
+    def _train_epoch(self, epoch: int) -> tuple[torch.Tensor, int]:
+        """ddpg.py:277-305 for one epoch, enqueued without a host read: the statistics slots used and the number of
+        rounds that logged zeros."""
+        a, st, env = self._cfgs.algo_cfgs, self._step, self._env
+        noise = float(a.exploration_noise) if a.use_exploration_noise else 0.0
+        first_update, idle = st.update_count, 0
+        if self._obs is None:
+            self._obs, _ = env.reset()
+        for sample_step in range(epoch * self._samples_per_epoch, (epoch + 1) * self._samples_per_epoch):
+            step = sample_step * self._update_cycle * self._num_envs
+            warm = step <= a.start_learning_steps  # known from the counter alone: no device read
+            for _ in range(self._update_cycle):
+                st.act(self._obs, noise=noise, random=warm, seed=self._seed, offset=self._env_steps, out=self._act)
+                obs = self._obs
+                self._obs, r, c, term, trunc, info = env.step(self._act)
+                st.store(obs, self._act, r, c, term, trunc, self._obs, info.get('final_observation'),
+                         info.get('_final_observation'), self._episodes)
+                self._env_steps += 1
+            if warm:
+                idle += 1
+                continue
+            for _ in range(int(a.update_iters)):
+                st.draw(self._seed, st.update_count, 1)  # after the store: the fill count is read on the device
+                st.run(1)
+        env.commit()
+        slots = (torch.arange(st.update_count - first_update, device=self._device) + first_update) % self._nslots
+        return slots, idle
+
+    def learn(self) -> tuple[float, float, float]:
+        """ddpg.py:254-348."""
+        self._logger.log('INFO: Start training')
+        a, spe = self._cfgs.algo_cfgs, int(self._cfgs.algo_cfgs.steps_per_epoch)
+        start_time = time.time()
+        try:
+            for epoch in range(self._epochs):
+                epoch_time = time.time()
+                slots, idle = self._train_epoch(epoch)
+                # the epoch's one read of the device: the steps' rows, the finished episodes
+                rows = self._step.stats[slots][:, :len(K)].cpu() if slots.numel() else torch.zeros(0, len(K))
+                n_ep = int(self._episodes[2].cpu())
+                eps = self._episodes[1][:min(n_ep, self._episodes[1].shape[0])].cpu()
+                self._episodes[2].zero_()
+                update_time = time.time() - epoch_time
+                iters, delay = int(a.update_iters), int(a.policy_delay)
+                first = self._step.update_count - rows.shape[0]
+                actor_rows = [(first + i + 1) % delay == 0 for i in range(rows.shape[0])]
+                per_round = torch.zeros(idle + rows.shape[0] // iters, len(K))  # _log_when_not_update: zeros
+                if rows.shape[0]:
+                    per_round[idle:] = rows[iters - 1::iters]
+                self.epoch_stats.append(per_round.tolist())
+                cols = range(len(K)) if a.use_cost else range(3)
+                for col in cols:
+                    vals = [0.0] * idle + [float(v) for i, v in enumerate(rows[:, col].tolist())
+                                           if col != 2 or actor_rows[i]]
+                    self._logger.extend(K[col], vals or [0.0])
+                for k, col in (('Metrics/EpRet', 0), ('Metrics/EpCost', 1), ('Metrics/EpLen', 2)):
+                    self._logger.extend(k, eps[:, col].tolist())
+                eval_start = time.time()
+                self._evaluate()
+                env_steps = (epoch + 1) * spe
+                self.total_env_steps = env_steps
+                self._logger.store({'Time/Update': update_time, 'Time/Rollout': 0.0,
+                                    'Time/Evaluate': time.time() - eval_start, 'TotalEnvSteps': env_steps,
+                                    'Time/FPS': spe / (time.time() - epoch_time), 'Time/Total': time.time() - start_time,
+                                    'Time/Epoch': time.time() - epoch_time, 'Train/Epoch': epoch,
+                                    'Train/LR': float(self._cfgs.model_cfgs.actor.lr)})
+                ep_ret, ep_cost, ep_len = (self._logger.get_stats(k)[0] for k in
+                                           ('Metrics/EpRet', 'Metrics/EpCost', 'Metrics/EpLen'))
+                self._logger.dump_tabular()
+                if (epoch + 1) % self._cfgs.logger_cfgs.save_model_freq == 0:
+                    self._logger.torch_save()
+        finally:
+            self._logger.close()
+            self._env.close()
+        return ep_ret, ep_cost, ep_len
+
+    def _evaluate(self) -> None:
+        """offpolicy_adapter.py:71-117: ``eval_episodes`` deterministic episodes of the current actor."""
+        n = int(self._cfgs.train_cfgs.eval_episodes)
+        if n <= 0:
+            return
+        if not hasattr(self, '_evaluator'):
+            self._evaluator = Evaluator(seed=self._seed, device=self._device, verbose=False)
+        ev = self._evaluator
+        ev.load_policy(self._cfgs.todict(), {'pi': self._step.state_dict()})
+        rets, costs = ev.evaluate(num_episodes=n)
+        self._logger.extend('Metrics/TestEpRet', [float(x) for x in rets])
+        self._logger.extend('Metrics/TestEpCost', [float(x) for x in costs])
+        self._logger.extend('Metrics/TestEpLen', [float(x) for x in ev.episode_lengths])
+
+
+@register
+class DDPG(BaseOffPolicy):
+    """Deep Deterministic Policy Gradient (ddpg.py:40-565)."""
+
+
+@register
+class TD3(BaseOffPolicy):
+    """Twin Delayed DDPG (td3.py:28-116): two reward critics, the target actor with clipped noise in the target."""
+
+    num_critics = 2
+
+    def _hparams(self) -> dict:
+        a = self._cfgs.algo_cfgs
+        return dict(policy_noise=float(a.policy_noise), policy_noise_clip=float(a.policy_noise_clip), target_actor=True)
+
+
+__all__ = ['BaseOffPolicy', 'DDPG', 'TD3']

@@ -230,6 +230,31 @@ _VAEBC = {
 }
 BC_DEFAULTS = {'VAEBC': _VAEBC}
 
+# ---- off-policy family (configs/off-policy/DDPG.yaml, TD3.yaml `defaults` blocks).  A table of its own, reached
+# through default_kwargs like BCQ's.  Deviations as above: device cuda:0, use_tensorboard off, the `verbose` extension
+# and the env_cfgs block.  TD3 is DDPG with two critics, a policy delay of 2 and the target-policy noise.
+_DDPG = {
+    'seed': 0,
+    'train_cfgs': {'device': 'cuda:0', 'torch_threads': 16, 'vector_env_nums': 1, 'parallel': 1,
+                   'total_steps': 1000000, 'eval_episodes': 1},
+    'algo_cfgs': {'steps_per_epoch': 2000, 'update_cycle': 1, 'update_iters': 1, 'size': 1000000, 'batch_size': 256,
+                  'reward_normalize': False, 'cost_normalize': False, 'obs_normalize': False, 'max_grad_norm': 40,
+                  'use_critic_norm': False, 'critic_norm_coeff': 0.001, 'polyak': 0.005, 'gamma': 0.99,
+                  'start_learning_steps': 25000, 'policy_delay': 1, 'use_exploration_noise': True,
+                  'exploration_noise': 0.1, 'use_cost': False},
+    'logger_cfgs': {'use_wandb': False, 'wandb_project': 'omnisafe', 'use_tensorboard': False,
+                    'save_model_freq': 100, 'log_dir': './runs', 'window_lens': 50, 'verbose': True},
+    'model_cfgs': {'weight_initialization_mode': 'kaiming_uniform', 'actor_type': 'mlp', 'linear_lr_decay': False,
+                   'actor': {'hidden_sizes': [256, 256], 'activation': 'relu', 'lr': 0.0003},
+                   'critic': {'num_critics': 1, 'hidden_sizes': [256, 256], 'activation': 'relu', 'lr': 0.0003}},
+    'env_cfgs': {},
+}
+_TD3 = copy.deepcopy(_DDPG)
+_TD3['algo_cfgs'].update({'policy_delay': 2, 'policy_noise': 0.2, 'policy_noise_clip': 0.5})
+_TD3['logger_cfgs']['window_lens'] = 10
+_TD3['model_cfgs']['critic']['num_critics'] = 2
+OFFPOLICY_DEFAULTS = {'DDPG': _DDPG, 'TD3': _TD3}
+
 
 def get_default_kwargs(algo: str) -> dict:
     """get_default_kwargs_yaml (config.py:235-262) for the accelerated algorithms."""
@@ -245,8 +270,8 @@ def get_default_kwargs(algo: str) -> dict:
 def default_kwargs(algo: str) -> dict:
     """The defaults of any registered algorithm: what ``Agent`` reads.  ``get_default_kwargs`` keeps to the three
     tables it was written for -- tests/test_crr_cpu.py and tests/test_vae_cpu.py hold it to a KeyError for 'BCQ' --
-    so the BCQ family is looked up here, in its own table."""
-    for table in (BCQ_DEFAULTS, DICE_DEFAULTS):
+    so the BCQ family, COptiDICE and the off-policy family are looked up here, in their own tables."""
+    for table in (BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS):
         if algo in table:
             return copy.deepcopy(table[algo])
     return get_default_kwargs(algo)
@@ -266,6 +291,18 @@ def check_all_configs(cfgs: Config) -> None:
     """Subset of config.py:265-409 that guards this path."""
     a = cfgs.algo_cfgs
     algo = getattr(cfgs, 'algo', None)
+    if algo in OFFPOLICY_DEFAULTS:  # (config.py:362-409's off-policy part: no GAE, no KL)
+        t = cfgs.train_cfgs
+        for k in ('steps_per_epoch', 'update_cycle', 'update_iters', 'size', 'batch_size', 'policy_delay'):
+            assert isinstance(a[k], int) and a[k] > 0, f'{k} must be a positive int'
+        assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0 and a.start_learning_steps >= 0
+        assert a.exploration_noise >= 0 and a.critic_norm_coeff >= 0 and (a.max_grad_norm or 0) >= 0
+        if algo == 'TD3':
+            assert a.policy_noise >= 0 and a.policy_noise_clip >= 0
+        assert isinstance(t.total_steps, int) and t.total_steps > 0 and t.eval_episodes >= 0
+        assert t.vector_env_nums >= 1 and t.parallel == 1, 'the off-policy family supports parallel 1 only'
+        assert a.batch_size <= a.size and t.vector_env_nums <= a.size
+        return
     if algo in OFFLINE_DEFAULTS or algo in BC_DEFAULTS or algo in BCQ_DEFAULTS or algo in DICE_DEFAULTS:
         t = cfgs.train_cfgs  # (none of the on-policy keys)
         assert isinstance(a.steps_per_epoch, int) and a.steps_per_epoch > 0

@@ -1,0 +1,839 @@
+// Off-policy TD3 and DDPG trained on the device from a replay ring: replaces omnisafe/algorithms/off_policy/
+// ddpg.py:382-547 and td3.py:50-116, the ring of common/buffer/vector_offpolicy_buffer.py and MLPActor.predict.
+//
+// At the YAML defaults every env step is followed by one gradient step over 256 rows through seven small MLPs, each
+// three dependent layers: the family is bound by launches, not by arithmetic.  td3_forward_kernel runs the whole
+// forward of a step in ONE plain launch:
+//   * a workgroup of four waves owns 32 rows of the batch and carries them through five networks (TD3: target actor,
+//     two target critics, two online critics; with use_cost the online actor, the cost target and the cost critic too);
+//     the activations never leave the chip: two ping-pong LDS buffers [32][256 + 4], one LDS array [32][obs || act]
+//     that first holds next_obs || a' -- the action columns written by the actor's head -- and is then refilled with
+//     obs || act of the same ring rows;
+//   * rows come straight from the ring through idx[slot][row]: no gather launch;
+//   * weights skip LDS (chain_layer.h: every wave owns output columns, one 16-byte global load feeds four float32
+//     32x32x2 MFMAs); the heads (action, q) split K over the waves and meet in LDS in wave order;
+//   * bias, activation, tanh, the clipped target-policy noise, the clamp, the min over the target pair, the TD target
+//     and the TD error are fused into the accumulator write-backs; the online critics' layer outputs are written once to
+//     the workspace on their way through, for the per-layer backward launches (crr_layers.h);
+//   * no cooperative groups, no spin-waits, no atomics; the losses are reduced in a fixed order by the Adam launch.
+// The layer route (OSA_TD3_ROUTE_LAYER) runs the same forward as one tile-GEMM launch per layer with small row kernels
+// between the networks: the fallback for a hidden width above 256 or an observation too wide for the LDS budget, and the
+// baseline the fused kernel is measured against.
+#include <math.h>
+
+#include "chain_layer.h"
+
+namespace {
+
+constexpr int T_NB = 32;  // workgroups (= partial sums) of a gradient-norm reduction
+
+struct TLayout {
+  CNet pi, q;
+  int D, A, B, nq, cost, nc, ldsa, lda, ldxin;
+};
+
+int td3_make_layout(const osa_td3_desc* d, TLayout* lo) {
+  if (!d) return OSA_EINVAL;
+  if (d->obs_dim < 1 || d->obs_dim > 4096 || d->act_dim < 1 || d->batch < 1) return OSA_EINVAL;
+  if (d->use_cost < 0 || d->use_cost > 1) return OSA_EINVAL;
+  if (d->act_dim > 32 || d->batch > (1 << 20) || d->num_critics < 1 || d->num_critics > 2) return OSA_EUNSUPPORTED;
+  for (int k = 0; k < 2; ++k)
+    if (d->n_hidden[k] < 1 || d->n_hidden[k] + 1 > GM_MAXL) return OSA_EUNSUPPORTED;
+  lo->D = d->obs_dim; lo->A = d->act_dim; lo->B = d->batch; lo->nq = d->num_critics; lo->cost = d->use_cost;
+  lo->nc = lo->nq + lo->cost;
+  lo->ldsa = c4(lo->D + lo->A); lo->lda = c4(lo->A); lo->ldxin = lo->ldsa + 4;
+  int width[GM_MAXL], rc;
+  const int na = d->n_hidden[0], nq = d->n_hidden[1];
+  for (int l = 0; l < na; ++l) width[l] = d->hidden[0][l];
+  width[na] = lo->A;
+  if ((rc = crr_make_net(lo->pi, lo->D, na + 1, width, d->activation[0], lo->A, false)) != OSA_OK) return rc;
+  for (int l = 0; l < nq; ++l) width[l] = d->hidden[1][l];
+  width[nq] = 1;
+  return crr_make_net(lo->q, lo->D + lo->A, nq + 1, width, d->activation[1], 1, false);
+}
+
+// ---- the workspace -----------------------------------------------------------------------------------------------
+struct TWs {
+  size_t xq, xc, xn[2], rcd, ho[3][GM_MAXL], ht[3][GM_MAXL], ha[2][GM_MAXL], hp[GM_MAXL], hq[GM_MAXL];
+  size_t z[3][2], dx, gq, gp, rows, part, hstride, zstride, total;
+};
+TWs td3_ws(const TLayout& lo) {
+  TWs w = {};
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    const size_t o = off;
+    off += (n + 3) / 4 * 4;
+    return o;
+  };
+  const size_t B = lo.B;
+  w.xq = take(B * lo.ldsa); w.xc = take(B * lo.ldsa);
+  for (int g = 0; g < 2; ++g) w.xn[g] = take(B * lo.ldsa);
+  w.rcd = take(3 * B);
+  for (int j = 0; j < 3; ++j)  // (the fused kernel addresses net j's outputs as ho[0] + j hstride)
+    for (int l = 0; l < GM_MAXL; ++l) w.ho[j][l] = l < lo.q.L ? take(B * lo.q.ldh[l]) : 0;
+  w.hstride = w.ho[1][0] - w.ho[0][0];
+  for (int j = 0; j < 3; ++j)
+    for (int l = 0; l < GM_MAXL; ++l) w.ht[j][l] = l < lo.q.L ? take(B * lo.q.ldh[l]) : 0;
+  for (int g = 0; g < 2; ++g)
+    for (int l = 0; l < GM_MAXL; ++l) w.ha[g][l] = l < lo.pi.L ? take(B * lo.pi.ldh[l]) : 0;
+  for (int l = 0; l < GM_MAXL; ++l) w.hp[l] = l < lo.pi.L ? take(B * lo.pi.ldh[l]) : 0;
+  for (int l = 0; l < GM_MAXL; ++l) w.hq[l] = l < lo.q.L ? take(B * lo.q.ldh[l]) : 0;
+  const int mz = lo.pi.maxldh > lo.q.maxldh ? lo.pi.maxldh : lo.q.maxldh;
+  for (int j = 0; j < 3; ++j)
+    for (int k = 0; k < 2; ++k) w.z[j][k] = take(B * mz);
+  w.zstride = w.z[1][0] - w.z[0][0];
+  w.dx = take(B * lo.ldsa);
+  w.gq = take((size_t)3 * lo.q.P);
+  w.gp = take(lo.pi.P);
+  w.rows = take(3 * B);
+  w.part = take((size_t)3 * T_NB * 2 * 2);  // [group][T_NB][2] doubles
+  w.total = off;
+  return w;
+}
+
+// ---- the step's scalar algebra, shared by both routes ----------------------------------------------------------------
+// td3.py:80-84: (a + clamp(policy_noise eps, -clip, clip)) clamped to [-1, 1]
+__device__ __forceinline__ float td3_noisy(float a, float eps, float pn, float clip) {
+  const float nz = fminf(fmaxf(__fmul_rn(eps, pn), -clip), clip);
+  return fminf(fmaxf(__fadd_rn(a, nz), -1.f), 1.f);
+}
+// ddpg.py:426: reward + gamma (1 - done) q
+__device__ __forceinline__ float td3_y(float sig, float done, float gamma, float q) {
+  return __fadd_rn(sig, __fmul_rn(__fmul_rn(gamma, 1.f - done), q));
+}
+
+// ---- the fused forward ---------------------------------------------------------------------------------------------
+size_t td3_fwd_lds(const TLayout& lo) {
+  return sizeof(float) * ((size_t)2 * BC_ROWS * BC_LDH + BC_PART + 5 * BC_ROWS + (size_t)BC_ROWS * lo.ldxin);
+}
+bool td3_chain_ok(const TLayout& lo) {
+  for (const CNet* n : {&lo.pi, &lo.q})
+    for (int l = 0; l + 1 < n->L; ++l)
+      if (n->out[l] > BC_MAXW) return false;
+  return td3_fwd_lds(lo) <= (size_t)BC_LDS_DYN;
+}
+
+struct TFwd {
+  osa_td3_ring r;
+  const long* idx;
+  const float* eps;
+  const long* step;
+  BNetK net[2];         // actor, critic
+  const float* pa[2];   // the actor of the reward target, of the cost target
+  const float* pt[3];   // target critics: reward ..., cost
+  const float* po[3];   // online critics, same order
+  float *xq, *ho0, *dz0, *rows;
+  long hstride, zstride;
+  int hoff[GM_MAXL], ldh[GM_MAXL];  // layer l of online critic j: ho0 + j hstride + hoff[l], rows of ldh[l] floats
+  int nslots, nq, cost, share, noise, D, A, B, ldxin, ldsa;
+  float pn, pclip, gamma, inv2B;
+};
+
+// hidden layer of an online critic: into the other ping-pong buffer AND once to the workspace (the backward reads it)
+struct TEmitStore {
+  float *dst, *out;
+  int N, act, ldo, m0, B;
+  __device__ __forceinline__ void operator()(int row, int n, float v) const {
+    if (n >= ((N + 3) & ~3)) return;
+    const float h = n < N ? gm_act(v, act) : 0.f;
+    dst[row * BC_LDH + n] = h;
+    if (m0 + row < B) out[(long)(m0 + row) * ldo + n] = h;
+  }
+};
+
+__global__ __launch_bounds__(256) void td3_forward_kernel(TFwd g) {
+  extern __shared__ __attribute__((aligned(16))) float t_smem[];
+  __shared__ BNetK nets[2];  // (a run-time layer index into the by-value argument would go through scratch memory)
+  __shared__ int hoff[GM_MAXL], ldh[GM_MAXL];
+  __shared__ long gi[BC_ROWS];
+  float* hb0 = t_smem;
+  float* hb1 = hb0 + BC_ROWS * BC_LDH;
+  float* part = hb1 + BC_ROWS * BC_LDH;
+  float* qv = part + BC_PART;      // [3][32] the target critics' values
+  float* yv = qv + 3 * BC_ROWS;    // [2][32] the TD targets
+  float* xin = yv + 2 * BC_ROWS;   // [32][ldxin] next_obs || a', then obs || act
+  const int tid = threadIdx.x, m0 = blockIdx.x * BC_ROWS;
+  const int D = g.D, A = g.A, B = g.B, ldxin = g.ldxin, nq = g.nq;
+  if (tid == 0) {
+    nets[0] = g.net[0];
+    nets[1] = g.net[1];
+  }
+  if (tid < GM_MAXL) {
+    hoff[tid] = g.hoff[tid];
+    ldh[tid] = g.ldh[tid];
+  }
+  const long slot = *g.step % g.nslots;
+  if (tid < BC_ROWS) {
+    long i = 0;
+    if (m0 + tid < B) {
+      i = g.idx[slot * B + m0 + tid];
+      if (i < 0 || i >= g.r.size) i = 0;  // (injected indices are checked on the host; never read outside the ring)
+    }
+    gi[tid] = i;
+  }
+  __syncthreads();
+  const float* __restrict__ eps = g.eps + slot * (long)B * A;
+  for (int e = tid; e < BC_ROWS * ldxin; e += 256) {
+    const int r = e / ldxin, c = e - r * ldxin;
+    xin[e] = (m0 + r < B && c < D) ? g.r.next_obs[gi[r] * g.r.ld_obs + c] : 0.f;
+  }
+  __syncthreads();
+  // ---- the target chain on next_obs
+  const int lda4 = (D + A + 3) & ~3;
+  const float pn = g.pn, pclip = g.pclip;
+  for (int grp = 0; grp <= g.cost; ++grp) {
+    if (grp == 0 || !g.share) {
+      const bool noise = grp == 0 && g.noise;
+      bc_net(&nets[0], grp == 0 ? g.pa[0] : g.pa[1], xin, ldxin, hb0, hb1, part, [=](int row, int n, float v) {
+        if (n < A) {
+          float a = gm_act(v, OSA_ACT_TANH);
+          if (noise && m0 + row < B) a = td3_noisy(a, eps[(long)(m0 + row) * A + n], pn, pclip);
+          xin[row * ldxin + D + n] = a;
+        } else if (D + n < lda4) {
+          xin[row * ldxin + D + n] = 0.f;
+        }
+      });
+    }
+    const int k0 = grp == 0 ? 0 : nq, k1 = grp == 0 ? nq : nq + 1;
+    for (int k = k0; k < k1; ++k) {
+      float* qk = qv + k * BC_ROWS;
+      bc_net(&nets[1], k == 0 ? g.pt[0] : (k == 1 ? g.pt[1] : g.pt[2]), xin, ldxin, hb0, hb1, part,
+             [=](int row, int n, float v) {
+               if (n == 0) qk[row] = v;
+             });
+    }
+  }
+  if (tid < BC_ROWS && m0 + tid < B) {
+    const long i = gi[tid];
+    const float done = g.r.done[i];
+    const float qm = nq == 2 ? fminf(qv[tid], qv[BC_ROWS + tid]) : qv[tid];
+    yv[tid] = td3_y(g.r.reward[i], done, g.gamma, qm);
+    if (g.cost) yv[BC_ROWS + tid] = td3_y(g.r.cost[i], done, g.gamma, qv[nq * BC_ROWS + tid]);
+  }
+  // ---- the online critics on obs || act of the same rows (the last layer's barrier: every read of xin is done)
+  for (int e = tid; e < BC_ROWS * ldxin; e += 256) {
+    const int r = e / ldxin, c = e - r * ldxin, m = m0 + r;
+    float v = 0.f;
+    if (m < B) {
+      if (c < D) v = g.r.obs[gi[r] * g.r.ld_obs + c];
+      else if (c < D + A) v = g.r.act[gi[r] * g.r.ld_act + c - D];
+      if (c < g.ldsa) g.xq[(long)m * g.ldsa + c] = v;
+    }
+    xin[e] = v;
+  }
+  __syncthreads();
+  const int L = __builtin_amdgcn_readfirstlane(nets[1].L), act = __builtin_amdgcn_readfirstlane(nets[1].act);
+  const float inv2B = g.inv2B;
+  for (int j = 0; j < nq + g.cost; ++j) {
+    const float* __restrict__ p = j == 0 ? g.po[0] : (j == 1 ? g.po[1] : g.po[2]);
+    float* hj = g.ho0 + j * g.hstride;
+    float* dz = g.dz0 + j * g.zstride;
+    float* rows = g.rows + (long)j * B;
+    const float* y = yv + (j < nq ? 0 : BC_ROWS);
+    for (int l = 0; l < L; ++l) {
+      const int N = __builtin_amdgcn_readfirstlane(nets[1].N[l]), ld = __builtin_amdgcn_readfirstlane(nets[1].ld[l]);
+      const float* W = p + __builtin_amdgcn_readfirstlane(nets[1].oW[l]);
+      const float* b = p + __builtin_amdgcn_readfirstlane(nets[1].ob[l]);
+      const float* src = l == 0 ? xin : ((l & 1) ? hb0 : hb1);
+      const int lds = l == 0 ? ldxin : BC_LDH;
+      float* out = hj + __builtin_amdgcn_readfirstlane(hoff[l]);
+      if (l + 1 < L) {
+        bc_layer(W, b, N, ld, src, lds, part,
+                 TEmitStore{(l & 1) ? hb1 : hb0, out, N, act, __builtin_amdgcn_readfirstlane(ldh[l]), m0, B});
+      } else {
+        bc_layer(W, b, N, ld, src, lds, part, [=](int row, int n, float v) {
+          const int m = m0 + row;
+          if (n != 0 || m >= B) return;
+          const float e = v - y[row];
+          const f32x4 qo = {v, 0.f, 0.f, 0.f}, d = {e * inv2B, 0.f, 0.f, 0.f};
+          *reinterpret_cast<f32x4*>(out + 4 * (long)m) = qo;
+          *reinterpret_cast<f32x4*>(dz + 4 * (long)m) = d;
+          rows[m] = e * e;
+        });
+      }
+    }
+  }
+}
+
+// ---- the layer route's row kernels -----------------------------------------------------------------------------------
+struct TGather {
+  osa_td3_ring r;
+  const long* idx;
+  const long* step;
+  int nslots, B, D, A, ldsa;
+  float *xq, *xn0, *xn1, *rcd;
+};
+__global__ __launch_bounds__(256) void td3_gather_kernel(TGather g) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), t = threadIdx.x & 63;
+  if (b >= g.B) return;
+  long i = g.idx[(*g.step % g.nslots) * g.B + b];
+  if (i < 0 || i >= g.r.size) i = 0;
+  const float* o = g.r.obs + i * g.r.ld_obs;
+  const float* a = g.r.act + i * g.r.ld_act;
+  const float* nx = g.r.next_obs + i * g.r.ld_obs;
+  for (int c = t; c < g.ldsa; c += 64) {
+    g.xq[(long)b * g.ldsa + c] = c < g.D ? o[c] : (c < g.D + g.A ? a[c - g.D] : 0.f);
+    const float v = c < g.D ? nx[c] : 0.f;
+    g.xn0[(long)b * g.ldsa + c] = v;
+    if (g.xn1) g.xn1[(long)b * g.ldsa + c] = v;
+  }
+  if (t == 0) {
+    g.rcd[b] = g.r.reward[i];
+    g.rcd[g.B + b] = g.r.cost[i];
+    g.rcd[2 * g.B + b] = g.r.done[i];
+  }
+}
+// x[b][D + j] = the target action of the head's pre-activation pre[b][j]; eps != null: with the clipped noise
+__global__ __launch_bounds__(256) void td3_action_kernel(int B, int A, int D, int lda, int ldsa,
+                                                         const float* __restrict__ pre, const float* __restrict__ eps,
+                                                         const long* __restrict__ step, int nslots, float pn, float pclip,
+                                                         float* __restrict__ x) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * A) return;
+  const int b = e / A, j = e - b * A;
+  float a = gm_act(pre[(long)b * lda + j], OSA_ACT_TANH);
+  if (eps) a = td3_noisy(a, eps[(*step % nslots) * (long)B * A + e], pn, pclip);
+  x[(long)b * ldsa + D + j] = a;
+}
+struct TTd {
+  const float* q[3];   // [B][4] online critics
+  const float* tq[3];  // [B][4] target critics
+  const float* rcd;
+  float* dz[3];
+  float* rows;
+  int B, nq, cost;
+  float gamma;
+};
+__global__ __launch_bounds__(256) void td3_td_kernel(TTd g) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= g.B) return;
+  const float done = g.rcd[2 * g.B + b], inv2B = 2.f / (float)g.B;
+  const float qm = g.nq == 2 ? fminf(g.tq[0][4 * b], g.tq[1][4 * b]) : g.tq[0][4 * b];
+  const float yr = td3_y(g.rcd[b], done, g.gamma, qm);
+  const float yc = g.cost ? td3_y(g.rcd[g.B + b], done, g.gamma, (g.nq == 2 ? g.tq[2] : g.tq[1])[4 * b]) : 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    if (j >= g.nq + g.cost) break;
+    const float e = g.q[j][4 * b] - (j < g.nq ? yr : yc);
+    const f32x4 d = {e * inv2B, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(g.dz[j] + 4 * b) = d;
+    g.rows[(long)j * g.B + b] = e * e;
+  }
+}
+
+// ---- the actor step's row kernels --------------------------------------------------------------------------------
+// xc = obs || tanh(pre) (pre overwritten with the tanh: the backward reads it); dz = d(-mean q)/dq
+__global__ __launch_bounds__(256) void td3_pi_kernel(int B, int A, int D, int lda, int ldsa, float* __restrict__ pre,
+                                                     const float* __restrict__ xq, float* __restrict__ xc,
+                                                     float* __restrict__ dz) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * ldsa) return;
+  const int b = e / ldsa, c = e - b * ldsa;
+  float v = 0.f;
+  if (c < D) {
+    v = xq[e];
+  } else if (c < D + A) {
+    v = gm_act(pre[(long)b * lda + c - D], OSA_ACT_TANH);
+    pre[(long)b * lda + c - D] = v;
+  }
+  xc[e] = v;
+  if (c == 0) {
+    const f32x4 d = {-1.f / (float)B, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(dz + 4 * (long)b) = d;
+  }
+}
+// dL/d(head pre-activation) = dL/da (1 - tanh^2); padding zero
+__global__ __launch_bounds__(256) void td3_dpi_kernel(int B, int A, int D, int lda, int ldsa,
+                                                      const float* __restrict__ dx, const float* __restrict__ th,
+                                                      float* __restrict__ dz) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * lda) return;
+  const int b = e / lda, j = e - b * lda;
+  float d = 0.f;
+  if (j < A) {
+    const float t = th[e];
+    d = dx[(long)b * ldsa + D + j] * (1.f - t * t);
+  }
+  dz[e] = d;
+}
+// the data gradient of a critic down to its input rows: dx[B][ldsa] = dL/d(obs || a)
+int td3_critic_dx(const CNet& n, const float* params, const size_t* h, const size_t* z, size_t dx, int B, int ldsa,
+                  float* ws, hipStream_t st) {
+  int cur = 0;
+  for (int l = n.L - 1; l >= 0; --l) {
+    GArgs gd = {};
+    gd.splits = 1;
+    GProb q = crr_prob();  // dZ_{l-1}[rows][in] = (dZ_l[rows][out] . W_l[out][in]) * act'(H_{l-1})
+    q.A = ws + z[cur]; q.lda = n.ldh[l];
+    q.B = params + n.oW[l]; q.ldb = n.ld[l];
+    q.M = B; q.N = n.in[l]; q.K = n.out[l];
+    if (l > 0) {
+      q.C = ws + z[cur ^ 1]; q.ldc = n.ldh[l - 1];
+      q.dact = n.act; q.aux = ws + h[l - 1]; q.ldaux = n.ldh[l - 1];
+    } else {
+      q.C = ws + dx; q.ldc = ldsa;
+    }
+    gd.p[gd.nprob++] = q;
+    const int rc = gm_gemm<false, true>(gd, st);
+    if (rc != OSA_OK) return rc;
+    cur ^= 1;
+  }
+  return OSA_OK;
+}
+
+// ---- clip_grad_norm_, the L2 term and Adam ---------------------------------------------------------------------------
+// blockIdx.y = optimiser group: over its n contiguous floats, grad += 2 coeff w (ddpg.py:430-432) and the partial sums
+// of grad^2 and w^2 of workgroup x into part[group][x][2]: a fixed assignment of elements to partials, added in order
+// by the Adam launch.  Thread 0 of workgroup 0 advances the group's Adam step count.
+struct TNorm {
+  float* grad[2];
+  const float* w[2];
+  long n[2];
+  int* adam_step[2];
+  double* part;  // of the launch's first group
+  float coeff;
+};
+__global__ __launch_bounds__(256) void td3_norm_kernel(TNorm g) {
+  __shared__ double red[17];
+  const int y = blockIdx.y;
+  float* __restrict__ grad = y == 0 ? g.grad[0] : g.grad[1];
+  const float* __restrict__ w = y == 0 ? g.w[0] : g.w[1];
+  const long n = y == 0 ? g.n[0] : g.n[1];
+  const float c2 = 2.f * g.coeff;
+  double sg = 0.0, sw = 0.0;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)T_NB * 256) {
+    float gr = grad[e];
+    if (g.coeff != 0.f) {
+      const float x = w[e];
+      gr = __fadd_rn(gr, __fmul_rn(c2, x));
+      grad[e] = gr;
+      sw += (double)x * x;
+    }
+    sg += (double)gr * gr;
+  }
+  sg = osa_block_sum<256>(sg, red);
+  sw = osa_block_sum<256>(sw, red);
+  if (threadIdx.x == 0) {
+    g.part[((long)y * T_NB + blockIdx.x) * 2] = sg;
+    g.part[((long)y * T_NB + blockIdx.x) * 2 + 1] = sw;
+    if (blockIdx.x == 0) *(y == 0 ? g.adam_step[0] : g.adam_step[1]) += 1;
+  }
+}
+
+// blockIdx.y = network; networks >= split belong to the launch's second group.  The clip scale from the group's
+// partials, Adam, (target != null) the Polyak update; workgroup 0 of a group's first network writes its statistics.
+struct TAdam {
+  int Pn, split, B, nslots, kind;  // kind 0: critics (MSE rows + L2, mean q), 1: the actor (-mean q)
+  long P, qstride;
+  float *params, *m, *v, *target, *stats;
+  const float *grad, *rows, *qtop;
+  const double* part;
+  const int* adam_step;  // [group]
+  const long* step;
+  float lr, max_norm, coeff, tau, omt;
+  double beta1, beta2, eps;
+};
+__global__ __launch_bounds__(256) void td3_adam_kernel(TAdam g) {
+  __shared__ double red[17];
+  const int net = blockIdx.y, grp = net >= g.split ? 1 : 0;
+  const double* part = g.part + (long)grp * T_NB * 2;
+  double ng = 0.0, nw = 0.0;
+  for (int i = 0; i < T_NB; ++i) {  // (every thread, the same order: no barrier needed for the scale itself)
+    ng += part[2 * i];
+    nw += part[2 * i + 1];
+  }
+  float scale = 1.f;
+  if (g.max_norm > 0.f) scale = fminf(g.max_norm / ((float)sqrt(ng) + 1e-6f), 1.f);  // clip_grad_norm_
+  if (blockIdx.x == 0 && (net == 0 || net == g.split)) {
+    float* s = g.stats + (*g.step % g.nslots) * OSA_TD3_NSTAT;
+    const int first = grp ? g.split : 0, nn = g.kind ? 1 : (grp ? 1 : g.split);
+    const float* qtop = g.qtop + (long)first * g.qstride;
+    double q = 0.0, l = 0.0;
+    for (int b = threadIdx.x; b < g.B; b += 256) q += (double)qtop[4 * b];
+    q = osa_block_sum<256>(q, red);
+    float loss = 0.f;
+    if (g.kind == 0) {
+      for (int j = 0; j < nn; ++j) {  // mse_loss(q1, y) + mse_loss(q2, y): float32 means added in order
+        l = 0.0;
+        for (int b = threadIdx.x; b < g.B; b += 256) l += (double)g.rows[(long)(first + j) * g.B + b];
+        l = osa_block_sum<256>(l, red);
+        loss += (float)(l / g.B);
+      }
+      loss += (float)(nw * (double)g.coeff);
+    }
+    if (threadIdx.x == 0) {
+      if (g.kind == 0) {
+        s[grp ? 3 : 0] = loss;
+        s[grp ? 4 : 1] = (float)(q / g.B);
+      } else {
+        s[2] = (float)(-q / g.B);
+      }
+    }
+  }
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= g.Pn) return;
+  const long o = (long)net * g.P + e;
+  float mm = g.m[o], vv = g.v[o];
+  const float w = crr_adam1(g.grad[o] * scale, mm, vv, g.params[o], g.lr, g.beta1, g.beta2, g.eps, g.adam_step[grp]);
+  g.params[o] = w;
+  g.m[o] = mm;
+  g.v[o] = vv;
+  if (g.target) g.target[o] = __fadd_rn(__fmul_rn(g.tau, w), __fmul_rn(g.omt, g.target[o]));
+}
+
+__global__ void td3_finish_kernel(long* step) {
+  if (threadIdx.x == 0) *step += 1;
+}
+
+// ---- ring, draws, act ------------------------------------------------------------------------------------------------
+struct TStore {
+  osa_td3_ring r;
+  int n, D, A, ld_obs, ld_act, ld_next, ld_final;
+  const float *obs, *act, *reward, *cost, *next_obs, *final_obs;
+  const unsigned char *term, *trunc, *final_mask;
+  float *ep_acc, *ep_out;
+  long ep_cap;
+  long* ep_count;
+};
+__global__ __launch_bounds__(256) void td3_store_kernel(TStore g) {
+  const long pos = g.r.pos[0], fill = g.r.pos[1];
+  const int W = g.D + g.A + g.D;
+  for (int e = threadIdx.x; e < g.n * W; e += 256) {
+    const int i = e / W, c = e - i * W;
+    const long row = (pos + i) % g.r.size;
+    if (c < g.D) {
+      g.r.obs[row * g.r.ld_obs + c] = g.obs[(long)i * g.ld_obs + c];
+    } else if (c < g.D + g.A) {
+      g.r.act[row * g.r.ld_act + c - g.D] = g.act[(long)i * g.ld_act + c - g.D];
+    } else {
+      const int k = c - g.D - g.A;
+      // (the value is selected, not the address: a per-lane choice between the two uniform base pointers came out of
+      // the compiler as one scalar base for the whole wave)
+      float v = g.next_obs[(long)i * g.ld_next + k];
+      if (g.final_obs && g.final_mask[i]) v = g.final_obs[(long)i * g.ld_final + k];
+      g.r.next_obs[row * g.r.ld_obs + k] = v;
+    }
+  }
+  for (int i = threadIdx.x; i < g.n; i += 256) {
+    const long row = (pos + i) % g.r.size;
+    g.r.reward[row] = g.reward[i];
+    g.r.cost[row] = g.cost[i];
+    g.r.done[row] = g.term[i] ? 1.f : 0.f;
+  }
+  __syncthreads();  // every thread has read the position
+  if (threadIdx.x == 0) {
+    g.r.pos[0] = (pos + g.n) % g.r.size;
+    g.r.pos[1] = fill + g.n < g.r.size ? fill + g.n : g.r.size;
+    if (g.ep_acc) {  // the envs in order: the episodes' order in ep_out is fixed
+      long cnt = *g.ep_count;
+      for (int i = 0; i < g.n; ++i) {
+        float* a = g.ep_acc + 3 * i;
+        a[0] += g.reward[i];
+        a[1] += g.cost[i];
+        a[2] += 1.f;
+        if (g.term[i] || g.trunc[i]) {
+          if (cnt < g.ep_cap)
+            for (int k = 0; k < 3; ++k) g.ep_out[3 * cnt + k] = a[k];
+          ++cnt;
+          a[0] = a[1] = a[2] = 0.f;
+        }
+      }
+      *g.ep_count = cnt;
+    }
+  }
+}
+
+#define TD3_KEY_IDX 0x54443349445831ull /* keys of their own: seed ^ key, counter = (step, element) */
+#define TD3_KEY_EPS 0x54443345505331ull
+#define TD3_KEY_ACT 0x54443341435431ull
+
+__device__ __forceinline__ float td3_normal(const uint32_t (&w)[4]) {  // as crr_draw_eps_kernel's
+  const double u1 = (double)osa_u01(w[0]), u2 = (double)osa_u01(w[1]);
+  return (float)(sqrt(-2.0 * log(u1)) * cos(6.28318530717958647692 * u2));
+}
+
+__global__ __launch_bounds__(256) void td3_draw_kernel(unsigned long long seed, long first, int nsteps, int nslots, int B,
+                                                       int A, const long* __restrict__ pos, long* __restrict__ idx,
+                                                       float* __restrict__ eps) {
+  const long per = (long)B * (1 + A), e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nsteps * per) return;
+  const long k = e / per, i = e - k * per, step = first + k, slot = step % nslots;
+  uint32_t w[4];
+  if (i < B) {
+    const long fill = pos[1] > 0 ? pos[1] : 1;
+    osa_philox(seed ^ TD3_KEY_IDX, (uint64_t)step, (uint64_t)i, w);
+    const unsigned long long bits = (unsigned long long)w[0] | ((unsigned long long)w[1] << 32);
+    idx[slot * B + i] = (long)__umul64hi(bits, (unsigned long long)fill);
+  } else {
+    osa_philox(seed ^ TD3_KEY_EPS, (uint64_t)step, (uint64_t)(i - B), w);
+    eps[slot * (long)B * A + (i - B)] = td3_normal(w);
+  }
+}
+
+// one row per workgroup; a wave per output column, lanes over K, the wave's sum in a fixed order
+struct TAct {
+  BNetK net;
+  const float *p, *obs;
+  float* out;
+  int D, A, ld_obs, ld_out, mode;
+  float noise;
+  unsigned long long key, offset;
+};
+constexpr int T_ACT_W = 4096;
+__global__ __launch_bounds__(256) void td3_act_kernel(TAct g) {
+  __shared__ float buf[2][T_ACT_W];
+  __shared__ BNetK nk;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t w[4];
+  if (g.mode == 1) {  // use_rand_action: uniform over the action box [-1, 1]
+    if (tid < g.A) {
+      osa_philox(g.key, g.offset, (uint64_t)row * g.A + tid, w);
+      g.out[(long)row * g.ld_out + tid] = __fsub_rn(__fmul_rn(2.f, osa_u01(w[0])), 1.f);
+    }
+    return;
+  }
+  if (tid == 0) nk = g.net;
+  for (int c = tid; c < g.D; c += 256) buf[0][c] = g.obs[(long)row * g.ld_obs + c];
+  __syncthreads();
+  int cur = 0, K = g.D;
+  for (int l = 0; l < nk.L; ++l) {
+    const int N = nk.N[l], ld = nk.ld[l];
+    const float* __restrict__ W = g.p + nk.oW[l];
+    const float* __restrict__ b = g.p + nk.ob[l];
+    for (int n = wave; n < N; n += 4) {
+      float s = 0.f;
+      for (int k = lane; k < K; k += 64) s = fmaf(W[(long)n * ld + k], buf[cur][k], s);
+      s = osa_wave_sum(s);
+      if (lane == 0) buf[cur ^ 1][n] = gm_act(s + b[n], l + 1 < nk.L ? nk.act : OSA_ACT_TANH);
+    }
+    __syncthreads();
+    cur ^= 1;
+    K = N;
+  }
+  if (tid < g.A) {
+    float a = buf[cur][tid];
+    if (g.noise > 0.f) {  // MLPActor.predict(deterministic=False): clamp(a + N(0, noise), -1, 1)
+      osa_philox(g.key, g.offset, (uint64_t)row * g.A + tid, w);
+      a = fminf(fmaxf(__fadd_rn(a, __fmul_rn(g.noise, td3_normal(w))), -1.f), 1.f);
+    }
+    g.out[(long)row * g.ld_out + tid] = a;
+  }
+}
+
+int td3_route_ok(const TLayout& lo, int route) {
+  if (route != OSA_TD3_ROUTE_LAYER && route != OSA_TD3_ROUTE_FUSED) return OSA_EINVAL;
+  return route == OSA_TD3_ROUTE_FUSED && !td3_chain_ok(lo) ? OSA_EUNSUPPORTED : OSA_OK;
+}
+
+// the forward of a step on either route: leaves xq, the online critics' layer outputs ho, dq in z[j][0] and the rows'
+// squared errors
+int td3_forward(const TLayout& lo, const TWs& w, const osa_td3_hparams* hp, const osa_td3_state* s,
+                const osa_td3_ring* ring, const osa_td3_draw_buffers* dr, float* ws, hipStream_t st) {
+  const int B = lo.B, top = lo.q.L - 1, nq = lo.nq, nc = lo.nc;
+  const long Pc = lo.q.P;
+  const bool noise = hp->policy_noise > 0.f;
+  const float* pa0 = hp->target_actor ? s->actor_t : s->actor;
+  const bool share = lo.cost && !hp->target_actor && !noise;  // (DDPG: both targets take the online actor's action)
+  if (hp->route == OSA_TD3_ROUTE_FUSED) {
+    static OsaPerDeviceOnce attr_set;
+    if (attr_set.need()) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&td3_forward_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, BC_LDS_DYN) != hipSuccess)
+        return OSA_EHIP;
+      attr_set.set();
+    }
+    TFwd g = {};
+    g.r = *ring; g.idx = dr->idx; g.eps = dr->eps; g.step = s->step;
+    g.net[0] = bcq_netk(lo.pi); g.net[1] = bcq_netk(lo.q);
+    g.pa[0] = pa0; g.pa[1] = s->actor;
+    for (int j = 0; j < nc; ++j) {
+      g.pt[j] = s->critic_t + j * Pc;
+      g.po[j] = s->critic + j * Pc;
+    }
+    g.xq = ws + w.xq; g.ho0 = ws + w.ho[0][0]; g.dz0 = ws + w.z[0][0]; g.rows = ws + w.rows;
+    g.hstride = (long)w.hstride; g.zstride = (long)w.zstride;
+    for (int l = 0; l < lo.q.L; ++l) {
+      g.hoff[l] = (int)(w.ho[0][l] - w.ho[0][0]);
+      g.ldh[l] = lo.q.ldh[l];
+    }
+    g.nslots = dr->nslots; g.nq = nq; g.cost = lo.cost; g.share = share; g.noise = noise;
+    g.D = lo.D; g.A = lo.A; g.B = B; g.ldxin = lo.ldxin; g.ldsa = lo.ldsa;
+    g.pn = hp->policy_noise; g.pclip = hp->policy_noise_clip; g.gamma = hp->gamma; g.inv2B = 2.f / (float)B;
+    hipLaunchKernelGGL(td3_forward_kernel, dim3((B + BC_ROWS - 1) / BC_ROWS), dim3(256), td3_fwd_lds(lo), st, g);
+    return hipGetLastError() == hipSuccess ? OSA_OK : OSA_EHIP;
+  }
+  int rc;
+  const bool two = lo.cost && !share;
+  TGather ga = {*ring, dr->idx, s->step, dr->nslots, B, lo.D, lo.A, lo.ldsa, ws + w.xq, ws + w.xn[0],
+                two ? ws + w.xn[1] : nullptr, ws + w.rcd};
+  hipLaunchKernelGGL(td3_gather_kernel, dim3(crr_blocks(B, 4)), dim3(256), 0, st, ga);
+  for (int grp = 0; grp < (two ? 2 : 1); ++grp) {
+    const CFwd af = {grp == 0 ? pa0 : s->actor, ws + w.xn[grp], lo.ldsa, B, w.ha[grp]};
+    if ((rc = crr_forward(lo.pi, &af, 1, ws, st)) != OSA_OK) return rc;
+    hipLaunchKernelGGL(td3_action_kernel, dim3(crr_blocks((long)B * lo.A, 256)), dim3(256), 0, st, B, lo.A, lo.D, lo.lda,
+                       lo.ldsa, ws + w.ha[grp][lo.pi.L - 1], grp == 0 && noise ? dr->eps : (const float*)nullptr,
+                       s->step, dr->nslots, hp->policy_noise, hp->policy_noise_clip, ws + w.xn[grp]);
+  }
+  CFwd tf[3], of[3];
+  for (int j = 0; j < nc; ++j) {
+    tf[j] = {s->critic_t + j * Pc, ws + w.xn[j >= nq && two ? 1 : 0], lo.ldsa, B, w.ht[j]};
+    of[j] = {s->critic + j * Pc, ws + w.xq, lo.ldsa, B, w.ho[j]};
+  }
+  if ((rc = crr_forward(lo.q, tf, nc, ws, st)) != OSA_OK) return rc;
+  if ((rc = crr_forward(lo.q, of, nc, ws, st)) != OSA_OK) return rc;
+  TTd td = {};
+  for (int j = 0; j < nc; ++j) {
+    td.q[j] = ws + w.ho[j][top]; td.tq[j] = ws + w.ht[j][top]; td.dz[j] = ws + w.z[j][0];
+  }
+  td.rcd = ws + w.rcd; td.rows = ws + w.rows; td.B = B; td.nq = nq; td.cost = lo.cost; td.gamma = hp->gamma;
+  hipLaunchKernelGGL(td3_td_kernel, dim3(crr_blocks(B, 256)), dim3(256), 0, st, td);
+  return OSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int osa_td3_layout(const osa_td3_desc* desc, int* out) {
+  TLayout lo;
+  OSA_REQUIRE(desc && out);
+  const int rc = td3_make_layout(desc, &lo);
+  if (rc != OSA_OK) return rc;
+  out[0] = lo.pi.P; out[1] = lo.q.P; out[2] = OSA_TD3_NSTAT; out[3] = 0;
+  int k = 4;
+  for (int net = 0; net < 2; ++net) {
+    const CNet& n = net == 0 ? lo.pi : lo.q;
+    for (int l = 0; l < OSA_GMLP_MAX_LAYERS; ++l) {
+      out[k++] = l < n.L ? n.oW[l] : -1;
+      out[k++] = l < n.L ? n.ob[l] : -1;
+      out[k++] = l < n.L ? n.ld[l] : 0;
+    }
+  }
+  return OSA_OK;
+}
+
+size_t osa_td3_ws_floats(const osa_td3_desc* desc) {
+  TLayout lo;
+  if (td3_make_layout(desc, &lo) != OSA_OK) return 0;
+  return td3_ws(lo).total;
+}
+
+int osa_td3_chain_supported(const osa_td3_desc* desc) {
+  TLayout lo;
+  return td3_make_layout(desc, &lo) == OSA_OK && td3_chain_ok(lo) ? 1 : 0;
+}
+
+static int td3_ring_ok(const osa_td3_ring* r, int D, int A) {
+  return r && r->obs && r->act && r->reward && r->cost && r->done && r->next_obs && r->pos && r->size >= 1 &&
+         r->ld_obs >= D && r->ld_act >= A;
+}
+
+int osa_td3_store(const osa_td3_ring* ring, int n, int obs_dim, int act_dim, const float* obs, int ld_obs,
+                  const float* act, int ld_act, const float* reward, const float* cost, const unsigned char* terminated,
+                  const unsigned char* truncated, const float* next_obs, int ld_next, const float* final_obs, int ld_final,
+                  const unsigned char* final_mask, float* ep_acc, float* ep_out, long ep_cap, long* ep_count, void* stream) {
+  OSA_REQUIRE(obs_dim >= 1 && act_dim >= 1 && td3_ring_ok(ring, obs_dim, act_dim));
+  OSA_REQUIRE(n >= 1 && n <= ring->size && obs && act && reward && cost && terminated && truncated && next_obs);
+  OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim && ld_next >= obs_dim);
+  OSA_REQUIRE(!final_obs || (final_mask && ld_final >= obs_dim));
+  OSA_REQUIRE(!ep_acc || (ep_out && ep_count && ep_cap >= 0));
+  TStore g = {*ring, n, obs_dim, act_dim, ld_obs, ld_act, ld_next, ld_final, obs, act, reward, cost, next_obs, final_obs,
+              terminated, truncated, final_mask, ep_acc, ep_out, ep_cap, ep_count};
+  hipLaunchKernelGGL(td3_store_kernel, dim3(1), dim3(256), 0, osa_stream(stream), g);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+int osa_td3_draws(const osa_td3_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                  const osa_td3_ring* ring, long* idx, float* eps, void* stream) {
+  TLayout lo;
+  OSA_REQUIRE(desc && idx && eps);
+  const int rc = td3_make_layout(desc, &lo);
+  if (rc != OSA_OK) return rc;
+  OSA_REQUIRE(first_step >= 0 && nsteps >= 1 && nslots >= 1 && nsteps <= nslots && td3_ring_ok(ring, lo.D, lo.A));
+  hipLaunchKernelGGL(td3_draw_kernel, dim3(crr_blocks((long)nsteps * lo.B * (1 + lo.A), 256)), dim3(256), 0,
+                     osa_stream(stream), seed, first_step, nsteps, nslots, lo.B, lo.A, ring->pos, idx, eps);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* s, const osa_td3_ring* ring,
+                 const osa_td3_draw_buffers* dr, float* stats, float* ws, size_t ws_floats, long update_count, int nsteps,
+                 void* stream) {
+  TLayout lo;
+  OSA_REQUIRE(desc && hp && s && ring && dr && stats && ws && nsteps >= 1 && update_count >= 0);
+  int rc = td3_make_layout(desc, &lo);
+  if (rc != OSA_OK) return rc;
+  if ((rc = td3_route_ok(lo, hp->route)) != OSA_OK) return rc;
+  const TWs w = td3_ws(lo);
+  OSA_REQUIRE(ws_floats >= w.total && (reinterpret_cast<uintptr_t>(ws) & 15) == 0);
+  OSA_REQUIRE(s->actor && s->actor_m && s->actor_v && s->actor_t && s->critic && s->critic_m && s->critic_v &&
+              s->critic_t && s->adam_step && s->step);
+  OSA_REQUIRE(td3_ring_ok(ring, lo.D, lo.A) && dr->idx && dr->eps && dr->nslots >= 1);
+  OSA_REQUIRE(hp->policy_delay >= 1 && hp->policy_noise >= 0.f && hp->policy_noise_clip >= 0.f && hp->lr_actor >= 0.f &&
+              hp->lr_critic >= 0.f && hp->max_grad_norm >= 0.f && hp->critic_norm_coeff >= 0.f && hp->beta1 >= 0.0 &&
+              hp->beta1 < 1.0 && hp->beta2 >= 0.0 && hp->beta2 < 1.0);
+  for (const float* p : {s->actor, s->actor_m, s->actor_v, s->actor_t, s->critic, s->critic_m, s->critic_v, s->critic_t})
+    OSA_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0);
+  hipStream_t st = osa_stream(stream);
+  const int B = lo.B, top = lo.q.L - 1, nq = lo.nq, nc = lo.nc;
+  const long Pc = lo.q.P;
+  double* part = reinterpret_cast<double*>(ws + w.part);
+  for (int it = 0; it < nsteps; ++it) {
+    const bool actor_step = (update_count + it + 1) % hp->policy_delay == 0;  // ddpg.py:398
+    if ((rc = td3_forward(lo, w, hp, s, ring, dr, ws, st)) != OSA_OK) return rc;
+    // ---- the critics: backward, norm (+ L2), Adam; on actor steps the Polyak update of ddpg.py:400 rides on the Adam
+    // launch -- the targets are not read again in the step
+    CBwd cb[3];
+    for (int j = 0; j < nc; ++j)
+      cb[j] = {s->critic + j * Pc, ws + w.xq, lo.ldsa, w.ho[j], {w.z[j][0], w.z[j][1]}, ws + w.gq + j * Pc};
+    if ((rc = crr_backward(lo.q, cb, nc, B, ws, st)) != OSA_OK) return rc;
+    TNorm nr = {{ws + w.gq, ws + w.gq + nq * Pc}, {s->critic, s->critic + nq * Pc}, {nq * Pc, Pc},
+                {s->adam_step + 1, s->adam_step + 2}, part, hp->critic_norm_coeff};
+    hipLaunchKernelGGL(td3_norm_kernel, dim3(T_NB, 1 + lo.cost), dim3(256), 0, st, nr);
+    TAdam ad = {lo.q.Pn, nq, B, dr->nslots, 0, Pc, (long)w.hstride, s->critic, s->critic_m, s->critic_v,
+                actor_step ? s->critic_t : nullptr, stats, ws + w.gq, ws + w.rows, ws + w.ho[0][top], part,
+                s->adam_step + 1, s->step, hp->lr_critic, hp->max_grad_norm, hp->critic_norm_coeff, hp->polyak,
+                hp->one_minus_polyak, hp->beta1, hp->beta2, hp->adam_eps};
+    hipLaunchKernelGGL(td3_adam_kernel, dim3(crr_blocks(lo.q.Pn, 256), nc), dim3(256), 0, st, ad);
+    if (actor_step) {  // ddpg.py:498-547 with the UPDATED critic 1
+      const CFwd pf = {s->actor, ws + w.xq, lo.ldsa, B, w.hp};
+      if ((rc = crr_forward(lo.pi, &pf, 1, ws, st)) != OSA_OK) return rc;
+      float* th = ws + w.hp[lo.pi.L - 1];
+      hipLaunchKernelGGL(td3_pi_kernel, dim3(crr_blocks((long)B * lo.ldsa, 256)), dim3(256), 0, st, B, lo.A, lo.D, lo.lda,
+                         lo.ldsa, th, ws + w.xq, ws + w.xc, ws + w.z[0][0]);
+      const CFwd qf = {s->critic, ws + w.xc, lo.ldsa, B, w.hq};
+      if ((rc = crr_forward(lo.q, &qf, 1, ws, st)) != OSA_OK) return rc;
+      if ((rc = td3_critic_dx(lo.q, s->critic, w.hq, w.z[0], w.dx, B, lo.ldsa, ws, st)) != OSA_OK) return rc;
+      hipLaunchKernelGGL(td3_dpi_kernel, dim3(crr_blocks((long)B * lo.lda, 256)), dim3(256), 0, st, B, lo.A, lo.D, lo.lda,
+                         lo.ldsa, ws + w.dx, th, ws + w.z[1][0]);
+      const CBwd pb = {s->actor, ws + w.xq, lo.ldsa, w.hp, {w.z[1][0], w.z[1][1]}, ws + w.gp};
+      if ((rc = crr_backward(lo.pi, &pb, 1, B, ws, st)) != OSA_OK) return rc;
+      double* apart = part + (long)2 * T_NB * 2;
+      TNorm na = {{ws + w.gp, nullptr}, {s->actor, nullptr}, {lo.pi.P, 0}, {s->adam_step, nullptr}, apart, 0.f};
+      hipLaunchKernelGGL(td3_norm_kernel, dim3(T_NB, 1), dim3(256), 0, st, na);
+      TAdam aa = {lo.pi.Pn, 1, B, dr->nslots, 1, (long)lo.pi.P, 0, s->actor, s->actor_m, s->actor_v, s->actor_t, stats,
+                  ws + w.gp, nullptr, ws + w.hq[top], apart, s->adam_step, s->step, hp->lr_actor, hp->max_grad_norm, 0.f,
+                  hp->polyak, hp->one_minus_polyak, hp->beta1, hp->beta2, hp->adam_eps};
+      hipLaunchKernelGGL(td3_adam_kernel, dim3(crr_blocks(lo.pi.Pn, 256), 1), dim3(256), 0, st, aa);
+    }
+    hipLaunchKernelGGL(td3_finish_kernel, dim3(1), dim3(64), 0, st, s->step);
+    OSA_CHECK_LAUNCH();
+  }
+  return OSA_OK;
+}
+
+int osa_td3_act(const osa_td3_desc* desc, const float* actor, const float* obs, int ld_obs, long n, int mode, float noise,
+                unsigned long long seed, unsigned long long offset, float* out, int ld_out, void* stream) {
+  TLayout lo;
+  OSA_REQUIRE(desc && out && n >= 1 && n <= 1024 && (mode == 0 || mode == 1) && noise >= 0.f);
+  const int rc = td3_make_layout(desc, &lo);
+  if (rc != OSA_OK) return rc;
+  OSA_REQUIRE(ld_out >= lo.A && (mode == 1 || (actor && obs && ld_obs >= lo.D)));
+  TAct g = {bcq_netk(lo.pi), actor, obs, out, lo.D, lo.A, ld_obs, ld_out, mode, noise, seed ^ TD3_KEY_ACT, offset};
+  hipLaunchKernelGGL(td3_act_kernel, dim3((unsigned)n), dim3(256), 0, osa_stream(stream), g);
+  OSA_CHECK_LAUNCH();
+  return OSA_OK;
+}
+
+}  // extern "C"

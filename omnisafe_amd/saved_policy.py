@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, Config
+from .config import BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
 from .spaces import Box
@@ -85,6 +85,24 @@ class BcqPolicy(VaePolicy):
         return self._dec.predict(obs, None, seed=self._seed, offset=self._calls)
 
 
+class MlpPolicy(VaePolicy):
+    """The deterministic actor of a DDPG / TD3 run for the per-step players: ``MLPActor.predict(deterministic=True)``,
+    the tanh-headed forward (osa_td3_act).  Its ``pi`` state dict holds ``net.*`` keys and no ``log_std``, so the
+    persistent players, whose kernels hold a Gaussian actor's block, do not take it: ``general``."""
+
+    def __init__(self, cfgs, state, obs_dim: int, act_dim: int, device, seed: int) -> None:  # pylint: disable=super-init-not-called
+        from .td3_step import Td3Actor, make_desc
+
+        m = cfgs.model_cfgs
+        self._dec = Td3Actor(make_desc(obs_dim, act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes,
+                                       m.actor.activation, m.critic.activation), device)
+        self._dec.load_state_dict(state['pi'])
+        self._seed, self._calls, self._act_dim = int(seed), 0, int(act_dim)
+
+    def _act(self, obs: torch.Tensor) -> torch.Tensor:
+        return self._dec.act(obs.contiguous())
+
+
 class _ActorOnly:
     """The ``model_cfgs`` of a COptiDICE run as ``ConstraintActorCritic`` reads them: the critics, which no player
     evaluates, take the actor's shape."""
@@ -99,11 +117,14 @@ class _ActorOnly:
 def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: int = 0, seed: int = 0):
     """``(actor, normalizer)`` of a checkpoint (evaluator.py:174-177, 250-303); ``extra_inputs``: policy input columns
     behind the observation (the Saute / Simmer safety column); ``normalizer`` is None without ``obs_normalize``.  A
-    VAE-BC run gives a ``VaePolicy``, a BCQ / BCQ-Lag run a ``BcqPolicy``, whose latent draws are seeded by ``seed``."""
+    VAE-BC run gives a ``VaePolicy``, a BCQ / BCQ-Lag run a ``BcqPolicy``, whose latent draws are seeded by ``seed``; a
+    DDPG / TD3 run gives an ``MlpPolicy``."""
     if str(getattr(cfgs, 'algo', '')) in BC_DEFAULTS:
         return VaePolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     if str(getattr(cfgs, 'algo', '')) in BCQ_DEFAULTS:
         return BcqPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
+    if str(getattr(cfgs, 'algo', '')) in OFFPOLICY_DEFAULTS:
+        return MlpPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     model_cfgs = cfgs.model_cfgs
     if str(getattr(cfgs, 'algo', '')) in DICE_DEFAULTS:  # (a Gaussian actor and no critic: the players read the actor)
         model_cfgs = _ActorOnly(model_cfgs)
