@@ -1416,6 +1416,84 @@ int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_
 int osa_td3_act(const osa_td3_desc* desc, const float* actor, const float* obs, int ld_obs, long n, int mode,
                 float noise, unsigned long long seed, unsigned long long offset, float* out, int ld_out, void* stream);
 
+/* ---- off-policy SAC (csrc/sac_kernels.hip) ------------------------------------------------------------------------------
+ * One gradient step of omnisafe/algorithms/off_policy/sac.py:93-207 on ddpg.py:350-400 from the replay ring of
+ * osa_td3_ring (written by osa_td3_store).  Networks: the tanh-squashed Gaussian actor (GaussianSACActor: hidden layers
+ * and ONE top layer of 2 act_dim columns, [mean | log_std], log_std clamped to [-20, 2]) with its target, TWO reward Q
+ * critics with their targets and, with use_cost, one cost critic with its target.  Blocks are padded as osa_td3_layout
+ * pads them; the critic blocks are [2 + use_cost][Pc]. */
+#define OSA_SAC_NSTAT OSA_TD3_NSTAT
+/* a statistics row: columns 0 .. 4 as OSA_TD3's, 5 Value/alpha (after the step), 6 Loss/alpha_loss (0 on a step without
+ * a temperature update) */
+#define OSA_SAC_HEAD_LAYER 0 /* the Gaussian head as the top layer's tile GEMM + one row kernel, forward and backward */
+#define OSA_SAC_HEAD_FUSED 1 /* ... as ONE launch each way: sac_head_kernel, sac_head_grad_kernel */
+#define OSA_SAC_HEAD_MAX_WIDTH 512 /* osa_sac_head_supported: the actor's last hidden width ... */
+#define OSA_SAC_HEAD_MAX_ROWS 4096 /* ... and the batch the fused head takes */
+typedef struct osa_sac_desc {
+  int obs_dim, act_dim;
+  int n_hidden[2];                     /* hidden layers of the actor, of a critic */
+  int hidden[2][OSA_GMLP_MAX_LAYERS];  /* their widths */
+  int activation[2];                   /* OSA_ACT_* of the hidden layers */
+  int batch, use_cost;                 /* B; 0 or 1 */
+} osa_sac_desc;
+typedef struct osa_sac_hparams {
+  float gamma, polyak, one_minus_polyak;
+  int auto_alpha;                        /* 1: the temperature step of sac.py:163-176 follows every actor step */
+  float target_entropy;                  /* -act_dim */
+  int policy_delay;
+  float lr_actor, lr_critic, lr_alpha;   /* lr_alpha: the reference takes critic.lr */
+  double beta1, beta2, adam_eps;
+  float max_grad_norm;                   /* clip_grad_norm_ per network optimiser; 0: none */
+  float critic_norm_coeff;               /* 0: use_critic_norm off */
+  int head;                              /* OSA_SAC_HEAD_* */
+} osa_sac_hparams;
+typedef struct osa_sac_state {                /* device memory, 16-byte aligned blocks */
+  float *actor, *actor_m, *actor_v, *actor_t; /* [Pa] */
+  float *critic, *critic_m, *critic_v, *critic_t; /* [2 + use_cost][Pc] */
+  int* adam_step;                             /* [4]: actor, reward critics, cost critic, temperature */
+  long* step;                                 /* update steps done */
+  float* log_alpha;                           /* [3]: log alpha and its two Adam moments */
+} osa_sac_state;
+typedef struct osa_sac_draw_buffers {         /* step t reads slot t % nslots */
+  long* idx;                                  /* [nslots][B] ring rows */
+  float* eps;                                 /* [nslots][3][B][act_dim] standard normals: target, actor, temperature */
+  int nslots;
+} osa_sac_draw_buffers;
+/* out as osa_td3_layout's: Pa, Pc, OSA_SAC_NSTAT, 0, then (oW, ob, ld) per layer of the actor (its top layer has
+ * 2 act_dim rows) and of a critic.  OSA_EUNSUPPORTED as osa_td3_layout.  Host only. */
+int osa_sac_layout(const osa_sac_desc* desc, int* out);
+/* floats of the step's workspace; 0 for a description osa_sac_layout refuses.  Host only. */
+size_t osa_sac_ws_floats(const osa_sac_desc* desc);
+/* 1 when OSA_SAC_HEAD_FUSED takes the description: the actor's last hidden width <= OSA_SAC_HEAD_MAX_WIDTH (a workgroup
+ * of the forward walks a quarter of it per wave, one of the backward recomputes the head's dz for every row) and batch <=
+ * OSA_SAC_HEAD_MAX_ROWS (a workgroup of the backward walks all rows).  Host only. */
+int osa_sac_head_supported(const osa_sac_desc* desc);
+/* The draws of steps first_step .. first_step + nsteps - 1 into their slots, one launch: idx as osa_td3_draws draws
+ * them, eps the first Box-Muller normal of element (draw * B + row) * act_dim + d.  Keys seed ^ 0x53414349445831 and
+ * seed ^ 0x53414345505331, counter (step, element). */
+int osa_sac_draws(const osa_sac_desc* desc, unsigned long long seed, long first_step, int nsteps, int nslots,
+                  const osa_td3_ring* ring, long* idx, float* eps, void* stream);
+/* nsteps gradient steps enqueued on `stream`, update_count as osa_td3_step's.  Per step: (1) the gather; ONE forward of
+ * the online actor on next_obs whose head samples a' = tanh(mu + sigma eps), forms log pi(a') and, with use_cost, tanh mu
+ * for the cost target; the target and online critics; y_r = r + gamma (1 - d) (min(tq1, tq2) - alpha log pi(a')),
+ * y_c = c + gamma (1 - d) tqc; the critics' backward, norm (+ L2), Adam, on actor steps with the Polyak update;
+ * (2) every policy_delay-th step the actor on obs, both reward critics on obs || a, the loss mean(alpha log pi -
+ * min(q1, q2)), both critics' data gradients down to the action columns, the head's gradient, the actor's backward, norm,
+ * Adam with the target actor's Polyak update; (3) with auto_alpha one more forward of the updated actor with a fresh
+ * draw and one single-workgroup launch: the fixed-order sum of log pi, Adam on log alpha, Loss/alpha_loss.  Plain
+ * launches only; no host synchronisation, no allocation, no atomics.  The workspace must be ZERO before the first step
+ * and be left to the steps afterwards: the padding columns of the activation rows and the padding between the critics'
+ * gradient blocks are read and never written.  OSA_EINVAL before any launch for null pointers, a short or misaligned
+ * workspace; OSA_EUNSUPPORTED for what osa_sac_layout refuses and for OSA_SAC_HEAD_FUSED where osa_sac_head_supported
+ * is 0. */
+int osa_sac_step(const osa_sac_desc* desc, const osa_sac_hparams* hp, const osa_sac_state* state,
+                 const osa_td3_ring* ring, const osa_sac_draw_buffers* draws, float* stats, float* ws, size_t ws_floats,
+                 long update_count, int nsteps, void* stream);
+/* Actions of n <= 1024 rows, one small VALU workgroup per row.  mode 0: tanh(mu + sigma normal); mode 1: uniform over
+ * [-1, 1] (use_rand_action); mode 2: tanh mu.  Draws: Philox(seed ^ 0x53414341435431, offset, row * act_dim + d). */
+int osa_sac_act(const osa_sac_desc* desc, const float* actor, const float* obs, int ld_obs, long n, int mode,
+                unsigned long long seed, unsigned long long offset, float* out, int ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

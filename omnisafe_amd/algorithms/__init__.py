@@ -8,13 +8,14 @@ from .siblings import (CPPOPID, CUP, FOCOPS, IPO, P3O, PCPO, PDO, RCPO, TRPOPID,
 ALGORITHMS = {'on-policy': tuple(sorted(registry.REGISTRY._module_dict))}  # noqa: SLF001
 from .offline import BCQ, CCRR, CRR, VAEBC, BCQLag, COptiDICE  # noqa: E402  (after the on-policy tuple: the registry holds every family)
 
-from .off_policy import DDPG, TD3  # noqa: E402
+from .off_policy import DDPG, SAC, TD3  # noqa: E402
 
 ALGORITHMS['offline'] = ('CCRR', 'CRR')
 ALGORITHMS['offline-bc'] = ('VAEBC',)
 ALGORITHMS['offline-dice'] = ('COptiDICE',)
 ALGORITHMS['offline-bcq'] = ('BCQ', 'BCQLag')
 ALGORITHMS['off-policy'] = ('DDPG', 'TD3')
-__all__ = ['DDPG', 'TD3', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'COptiDICE', 'PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
+ALGORITHMS['off-policy-sac'] = ('SAC',)
+__all__ = ['DDPG', 'TD3', 'SAC', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'COptiDICE', 'PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
            'OnCRPO', 'CPPOPID', 'TRPOPID', 'PCPO', 'FOCOPS', 'CUP', 'P3O', 'PPOSaute', 'TRPOSaute',
            'PPOSimmerPID', 'TRPOSimmerPID', 'registry', 'ALGORITHMS']

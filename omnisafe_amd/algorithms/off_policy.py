@@ -1,5 +1,5 @@
-"""Off-policy DDPG and TD3 trained on the device from a replay ring -- mirror of
-omnisafe/algorithms/off_policy/ddpg.py:40-565, td3.py:28-116 and adapter/offpolicy_adapter.py.
+"""Off-policy DDPG, TD3 and SAC trained on the device from a replay ring -- mirror of
+omnisafe/algorithms/off_policy/ddpg.py:40-565, td3.py:28-116, sac.py:35-222 and adapter/offpolicy_adapter.py.
 
     agent = omnisafe_amd.Agent('TD3', 'SynthNavGoal1-v0')
     agent.learn(); agent.evaluate()
@@ -27,7 +27,7 @@ import time
 import torch
 
 from .. import envs as envs_mod
-from .. import td3_step
+from .. import sac_step, td3_step
 from ..evaluator import Evaluator
 from ..logger import Logger
 from ..saved_policy import device_env_class
@@ -41,6 +41,9 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
     """ddpg.py:40-565 around a Td3Step."""
 
     num_critics = 1
+    stat_keys = K           # the columns of a statistics row
+    actor_cols = (2,)       # ... that only an actor step writes
+    step_mod = td3_step     # make_desc and the step class come from here
 
     def _hparams(self) -> dict:
         """DDPG: TD3 with one critic, no target-policy noise and the online actor in the target (ddpg.py:424)."""
@@ -78,16 +81,30 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         """ddpg.py:94-133: actor, critics, targets, the ring."""
         m, a = self._cfgs.model_cfgs, self._cfgs.algo_cfgs
         m.critic.recurisve_update({'num_critics': self.num_critics})
-        desc = td3_step.make_desc(self._obs_dim, self._act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes,
+        desc = self.step_mod.make_desc(self._obs_dim, self._act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes,
                                   m.actor.activation, m.critic.activation, a.batch_size, self.num_critics, a.use_cost)
         self._nslots = self._samples_per_epoch * int(a.update_iters)
-        self._step = td3_step.Td3Step(
+        self._step = self._make_step(
             desc, size=int(a.size), gamma=float(a.gamma), polyak=float(a.polyak), lr_actor=float(m.actor.lr),
             lr_critic=float(m.critic.lr), nslots=self._nslots, policy_delay=int(a.policy_delay),
             max_grad_norm=float(a.max_grad_norm or 0.0),
             critic_norm_coeff=float(a.critic_norm_coeff) if a.use_critic_norm else 0.0, device=self._device,
             **self._hparams())
         self._step.init_parameters(m.weight_initialization_mode)
+
+    def _make_step(self, desc, **kw):
+        return td3_step.Td3Step(desc, **kw)
+
+    def _act_into(self, warm: bool) -> None:
+        """The acting launch of one vector step: ``MLPActor.predict`` with the exploration noise, or the warm-up's
+        uniform draw."""
+        a = self._cfgs.algo_cfgs
+        noise = float(a.exploration_noise) if a.use_exploration_noise else 0.0
+        self._step.act(self._obs, noise=noise, random=warm, seed=self._seed, offset=self._env_steps, out=self._act)
+
+    def _idle_row(self) -> list:
+        """What a round before ``start_learning_steps`` logs (``_log_when_not_update``): zeros."""
+        return [0.0] * len(self.stat_keys)
 
     def _init(self) -> None:
         f32 = dict(dtype=torch.float32, device=self._device)
@@ -111,20 +128,22 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         keys = [('Metrics/EpRet', lc.window_lens), ('Metrics/EpCost', lc.window_lens), ('Metrics/EpLen', lc.window_lens)]
         if self._cfgs.train_cfgs.eval_episodes > 0:
             keys += [(k, lc.window_lens) for k in ('Metrics/TestEpRet', 'Metrics/TestEpCost', 'Metrics/TestEpLen')]
-        keys += [(k, None) for k in ('Train/Epoch', 'Train/LR', 'TotalEnvSteps') + K[:3]]
-        if a.use_cost:
-            keys += [(k, None) for k in K[3:]]
+        keys += [(k, None) for k in ('Train/Epoch', 'Train/LR', 'TotalEnvSteps')]
+        keys += [(self.stat_keys[col], None) for col in self._logged_cols()]
         keys += [(k, None) for k in ('Time/Total', 'Time/Rollout', 'Time/Update', 'Time/Evaluate', 'Time/Epoch',
                                      'Time/FPS')]
         for key, window in keys:
             self._logger.register_key(key, window_length=window)
+
+    def _logged_cols(self) -> list:
+        """The statistics columns this run logs: the cost critic's with ``use_cost`` only."""
+        return [0, 1, 2] + ([3, 4] if self._cfgs.algo_cfgs.use_cost else [])
 
     # ------------------------------------------------------------------ training
     def _train_epoch(self, epoch: int) -> tuple[torch.Tensor, int]:
         """ddpg.py:277-305 for one epoch, enqueued without a host read: the statistics slots used and the number of
         rounds that logged zeros."""
         a, st, env = self._cfgs.algo_cfgs, self._step, self._env
-        noise = float(a.exploration_noise) if a.use_exploration_noise else 0.0
         first_update, idle = st.update_count, 0
         if self._obs is None:
             self._obs, _ = env.reset()
@@ -132,7 +151,7 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
             step = sample_step * self._update_cycle * self._num_envs
             warm = step <= a.start_learning_steps  # known from the counter alone: no device read
             for _ in range(self._update_cycle):
-                st.act(self._obs, noise=noise, random=warm, seed=self._seed, offset=self._env_steps, out=self._act)
+                self._act_into(warm)
                 obs = self._obs
                 self._obs, r, c, term, trunc, info = env.step(self._act)
                 st.store(obs, self._act, r, c, term, trunc, self._obs, info.get('final_observation'),
@@ -152,13 +171,14 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         """ddpg.py:254-348."""
         self._logger.log('INFO: Start training')
         a, spe = self._cfgs.algo_cfgs, int(self._cfgs.algo_cfgs.steps_per_epoch)
+        keys, idle_row = self.stat_keys, torch.tensor(self._idle_row())
         start_time = time.time()
         try:
             for epoch in range(self._epochs):
                 epoch_time = time.time()
                 slots, idle = self._train_epoch(epoch)
                 # the epoch's one read of the device: the steps' rows, the finished episodes
-                rows = self._step.stats[slots][:, :len(K)].cpu() if slots.numel() else torch.zeros(0, len(K))
+                rows = self._step.stats[slots][:, :len(keys)].cpu() if slots.numel() else torch.zeros(0, len(keys))
                 n_ep = int(self._episodes[2].cpu())
                 eps = self._episodes[1][:min(n_ep, self._episodes[1].shape[0])].cpu()
                 self._episodes[2].zero_()
@@ -166,15 +186,14 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
                 iters, delay = int(a.update_iters), int(a.policy_delay)
                 first = self._step.update_count - rows.shape[0]
                 actor_rows = [(first + i + 1) % delay == 0 for i in range(rows.shape[0])]
-                per_round = torch.zeros(idle + rows.shape[0] // iters, len(K))  # _log_when_not_update: zeros
+                per_round = idle_row.repeat(idle + rows.shape[0] // iters, 1)
                 if rows.shape[0]:
                     per_round[idle:] = rows[iters - 1::iters]
                 self.epoch_stats.append(per_round.tolist())
-                cols = range(len(K)) if a.use_cost else range(3)
-                for col in cols:
-                    vals = [0.0] * idle + [float(v) for i, v in enumerate(rows[:, col].tolist())
-                                           if col != 2 or actor_rows[i]]
-                    self._logger.extend(K[col], vals or [0.0])
+                for col in self._logged_cols():
+                    vals = [float(idle_row[col])] * idle + [float(v) for i, v in enumerate(rows[:, col].tolist())
+                                                            if col not in self.actor_cols or actor_rows[i]]
+                    self._logger.extend(keys[col], vals or [0.0])
                 for k, col in (('Metrics/EpRet', 0), ('Metrics/EpCost', 1), ('Metrics/EpLen', 2)):
                     self._logger.extend(k, eps[:, col].tolist())
                 eval_start = time.time()
@@ -227,4 +246,39 @@ class TD3(BaseOffPolicy):
         return dict(policy_noise=float(a.policy_noise), policy_noise_clip=float(a.policy_noise_clip), target_actor=True)
 
 
-__all__ = ['BaseOffPolicy', 'DDPG', 'TD3']
+@register
+class SAC(BaseOffPolicy):
+    """Soft Actor-Critic (sac.py:35-222): a tanh-squashed Gaussian actor that acts stochastically while training, the
+    entropy term in the reward target, the min over both critics in the actor loss and, with ``auto_alpha``, the
+    temperature step -- sac_step.SacStep.  ``use_exploration_noise`` has no effect, as in the reference's Gaussian
+    actor, whose ``predict`` has no noise argument."""
+
+    num_critics = 2
+    stat_keys = sac_step.STAT_KEYS
+    actor_cols = (2, 5, 6)  # (sac.py:163-183 stores Value/alpha and Loss/alpha_loss inside _update_actor)
+    step_mod = sac_step
+
+    def _hparams(self) -> dict:
+        a = self._cfgs.algo_cfgs
+        return dict(alpha=float(a.alpha), auto_alpha=bool(a.auto_alpha))
+
+    def _make_step(self, desc, **kw):
+        return sac_step.SacStep(desc, **kw)
+
+    def _act_into(self, warm: bool) -> None:
+        self._step.act(self._obs, mode=sac_step.ACT_UNIFORM if warm else sac_step.ACT_SAMPLE, seed=self._seed,
+                       offset=self._env_steps, out=self._act)
+
+    def _idle_row(self) -> list:
+        """sac.py:209-222: zeros, and the temperature as it stands -- the initial one, known on the host, since no
+        round idles once learning has started."""
+        a = self._cfgs.algo_cfgs
+        row = [0.0] * len(self.stat_keys)
+        row[5] = 1.0 if a.auto_alpha else float(a.alpha)
+        return row
+
+    def _logged_cols(self) -> list:
+        return super()._logged_cols() + [5] + ([6] if self._cfgs.algo_cfgs.auto_alpha else [])
+
+
+__all__ = ['BaseOffPolicy', 'DDPG', 'TD3', 'SAC']

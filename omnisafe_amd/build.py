@@ -27,7 +27,8 @@ PER_FILE_FLAGS = {'ppo_pass_kernel.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],
                   # no packed float32 VALU forms in the VAE kernels' elementwise code
                   'vae_kernels.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
                   'bcq_kernels.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
-                  'td3_kernels.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+                  'td3_kernels.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+                  'sac_kernels.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def _hipcc() -> str:

@@ -255,6 +255,14 @@ _TD3['logger_cfgs']['window_lens'] = 10
 _TD3['model_cfgs']['critic']['num_critics'] = 2
 OFFPOLICY_DEFAULTS = {'DDPG': _DDPG, 'TD3': _TD3}
 
+# ---- SAC (configs/off-policy/SAC.yaml): TD3's blocks with the temperature, a Gaussian actor, no exploration noise and a
+# shorter warm-up.  A table of its own like BCQ's: tests/test_td3_cpu.py holds OFFPOLICY_DEFAULTS to its two entries.
+_SAC = copy.deepcopy(_TD3)
+_SAC['algo_cfgs'].update({'penalty_coef': 0.0, 'start_learning_steps': 10000, 'use_exploration_noise': False,
+                          'alpha': 0.2, 'auto_alpha': False})
+_SAC['model_cfgs']['actor_type'] = 'gaussian_sac'
+SAC_DEFAULTS = {'SAC': _SAC}
+
 
 def get_default_kwargs(algo: str) -> dict:
     """get_default_kwargs_yaml (config.py:235-262) for the accelerated algorithms."""
@@ -270,8 +278,8 @@ def get_default_kwargs(algo: str) -> dict:
 def default_kwargs(algo: str) -> dict:
     """The defaults of any registered algorithm: what ``Agent`` reads.  ``get_default_kwargs`` keeps to the three
     tables it was written for -- tests/test_crr_cpu.py and tests/test_vae_cpu.py hold it to a KeyError for 'BCQ' --
-    so the BCQ family, COptiDICE and the off-policy family are looked up here, in their own tables."""
-    for table in (BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS):
+    so the BCQ family, COptiDICE, the off-policy family and SAC are looked up here, in their own tables."""
+    for table in (BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, SAC_DEFAULTS):
         if algo in table:
             return copy.deepcopy(table[algo])
     return get_default_kwargs(algo)
@@ -291,8 +299,10 @@ def check_all_configs(cfgs: Config) -> None:
     """Subset of config.py:265-409 that guards this path."""
     a = cfgs.algo_cfgs
     algo = getattr(cfgs, 'algo', None)
-    if algo in OFFPOLICY_DEFAULTS:  # (config.py:362-409's off-policy part: no GAE, no KL)
+    if algo in OFFPOLICY_DEFAULTS or algo in SAC_DEFAULTS:  # (config.py:362-409's off-policy part: no GAE, no KL)
         t = cfgs.train_cfgs
+        if algo in SAC_DEFAULTS:
+            assert a.alpha > 0, 'alpha must be positive'
         for k in ('steps_per_epoch', 'update_cycle', 'update_iters', 'size', 'batch_size', 'policy_delay'):
             assert isinstance(a[k], int) and a[k] > 0, f'{k} must be a positive int'
         assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0 and a.start_learning_steps >= 0

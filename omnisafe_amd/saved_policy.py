@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, Config
+from .config import BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, SAC_DEFAULTS, Config
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
 from .spaces import Box
@@ -103,6 +103,26 @@ class MlpPolicy(VaePolicy):
         return self._dec.act(obs.contiguous())
 
 
+class SacPolicy(VaePolicy):
+    """The Gaussian actor of a SAC run for the per-step players: ``GaussianSACActor.predict(deterministic=True)``,
+    ``tanh mu`` (osa_sac_act).  Its ``pi`` state dict holds a ``(2 act_dim, hidden)`` top layer and no ``log_std``
+    parameter: ``general``, like ``MlpPolicy``."""
+
+    def __init__(self, cfgs, state, obs_dim: int, act_dim: int, device, seed: int) -> None:  # pylint: disable=super-init-not-called
+        from .sac_step import SacActor, make_desc
+
+        m = cfgs.model_cfgs
+        self._dec = SacActor(make_desc(obs_dim, act_dim, m.actor.hidden_sizes, m.critic.hidden_sizes,
+                                       m.actor.activation, m.critic.activation), device)
+        self._dec.load_state_dict(state['pi'])
+        self._seed, self._calls, self._act_dim = int(seed), 0, int(act_dim)
+
+    def _act(self, obs: torch.Tensor) -> torch.Tensor:
+        from .sac_step import ACT_MEAN
+
+        return self._dec.act(obs.contiguous(), mode=ACT_MEAN)
+
+
 class _ActorOnly:
     """The ``model_cfgs`` of a COptiDICE run as ``ConstraintActorCritic`` reads them: the critics, which no player
     evaluates, take the actor's shape."""
@@ -125,6 +145,8 @@ def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: 
         return BcqPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     if str(getattr(cfgs, 'algo', '')) in OFFPOLICY_DEFAULTS:
         return MlpPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
+    if str(getattr(cfgs, 'algo', '')) in SAC_DEFAULTS:
+        return SacPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     model_cfgs = cfgs.model_cfgs
     if str(getattr(cfgs, 'algo', '')) in DICE_DEFAULTS:  # (a Gaussian actor and no critic: the players read the actor)
         model_cfgs = _ActorOnly(model_cfgs)

@@ -102,15 +102,17 @@ def _hidden(desc: Td3Desc, net: int) -> list[int]:
 class Td3Layout:
     """Offsets of the reference's tensors inside the padded blocks (osa_td3_layout).  Host only."""
 
-    def __init__(self, desc: Td3Desc) -> None:
+    def __init__(self, desc, entry: str = 'osa_td3_layout', actor_out: int | None = None) -> None:
+        """``entry`` / ``actor_out``: the layout function and the actor's top width of another description with the
+        same ``out`` format (sac_step: osa_sac_layout, 2 act_dim)."""
         out = (C.c_int * (4 + 2 * GMLP_MAX_LAYERS * 3))()
-        _lib.check(_lib.load().osa_td3_layout(C.byref(desc), out), 'osa_td3_layout')
+        _lib.check(getattr(_lib.load(), entry)(C.byref(desc), out), entry)
         self.Pa, self.Pc, self.nstat = (int(x) for x in out[:3])
         D, A = int(desc.obs_dim), int(desc.act_dim)
-        self.num_critics = int(desc.num_critics)
+        self.num_critics = int(getattr(desc, 'num_critics', 2))
         self._layers = []
         k = 4
-        for sizes in ([D] + _hidden(desc, 0) + [A], [D + A] + _hidden(desc, 1) + [1]):
+        for sizes in ([D] + _hidden(desc, 0) + [actor_out or A], [D + A] + _hidden(desc, 1) + [1]):
             rows = []
             for l in range(GMLP_MAX_LAYERS):
                 oW, ob, ld = int(out[k]), int(out[k + 1]), int(out[k + 2])
@@ -152,10 +154,11 @@ def route_of(desc: Td3Desc, name: str | None = None) -> int:
 class Td3Actor:
     """``MLPActor``: the actor block, its state dict and ``act``."""
 
-    def __init__(self, desc: Td3Desc, device) -> None:
+    def __init__(self, desc, device, layout: Td3Layout | None = None) -> None:
+        """``layout``: the layout of another description with the same block format (sac_step.SacLayout)."""
         self._lib = _lib.load(require_gpu=True)
         self.desc, self.device = desc, torch.device(device)
-        self.layout = lay = Td3Layout(desc)
+        self.layout = lay = layout or Td3Layout(desc)
         self.D, self.A, self.B = int(desc.obs_dim), int(desc.act_dim), int(desc.batch)
         self.f32 = dict(dtype=torch.float32, device=self.device)
         self.actor = torch.zeros(lay.Pa, **self.f32)
@@ -193,23 +196,9 @@ class Td3Step(Td3Actor):  # pylint: disable=too-many-instance-attributes
                  route: str | None = None, device='cuda:0') -> None:
         self.route = route_of(desc, route)
         super().__init__(desc, device)
-        self.nslots, self.size = int(nslots), int(size)
-        assert self.nslots >= 1 and self.size >= 1
-        lay, f32, B, D, A = self.layout, self.f32, self.B, self.D, self.A
-        self.nq, self.use_cost = int(desc.num_critics), bool(desc.use_cost)
-        nc = self.nq + int(self.use_cost)
-        self.actor_m, self.actor_v, self.actor_t = (torch.zeros_like(self.actor) for _ in range(3))
-        self.critic, self.critic_m, self.critic_v, self.critic_t = (torch.zeros(nc, lay.Pc, **f32) for _ in range(4))
-        self.adam_step = torch.zeros(3, dtype=torch.int32, device=self.device)
-        self.step = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.update_count = 0  # the host's mirror of ``step``: which steps update the actor
-        self.stats = torch.zeros(self.nslots, lay.nstat, **f32)
-        self.idx = torch.zeros(self.nslots, B, dtype=torch.int64, device=self.device)
+        self._init_training_state(size, nslots, int(desc.num_critics), 3)
+        f32, B, A = self.f32, self.B, self.A
         self.eps = torch.zeros(self.nslots, B, A, **f32)
-        self.ring = {'obs': torch.zeros(self.size, D, **f32), 'act': torch.zeros(self.size, A, **f32),
-                     'reward': torch.zeros(self.size, **f32), 'cost': torch.zeros(self.size, **f32),
-                     'done': torch.zeros(self.size, **f32), 'next_obs': torch.zeros(self.size, D, **f32)}
-        self.pos = torch.zeros(2, dtype=torch.int64, device=self.device)  # write position, rows filled
         self.ws_floats = int(self._lib.osa_td3_ws_floats(C.byref(desc)))
         self.ws = torch.zeros(self.ws_floats, **f32)
         self.hp = Td3HParams(gamma=gamma, polyak=polyak, one_minus_polyak=1.0 - polyak, policy_noise=policy_noise,
@@ -218,12 +207,34 @@ class Td3Step(Td3Actor):  # pylint: disable=too-many-instance-attributes
                              policy_delay=int(policy_delay), lr_actor=lr_actor, lr_critic=lr_critic, beta1=0.9,
                              beta2=0.999, adam_eps=1e-8, max_grad_norm=float(max_grad_norm or 0.0),
                              critic_norm_coeff=float(critic_norm_coeff), route=self.route)
-        p, r = _lib.ptr, self.ring
+        p = _lib.ptr
         self._state = Td3State(p(self.actor), p(self.actor_m), p(self.actor_v), p(self.actor_t), p(self.critic),
                                p(self.critic_m), p(self.critic_v), p(self.critic_t), p(self.adam_step), p(self.step))
+        self._draws = Td3DrawBuffers(p(self.idx), p(self.eps), self.nslots)
+
+    def _init_training_state(self, size: int, nslots: int, nq: int, n_adam: int) -> None:
+        """What every off-policy step built on the actor block holds (``SacStep`` too): the Adam moments and targets,
+        the critic blocks with their state-dict indices, the counters, the statistics rows, the index draws and the
+        replay ring that ``store`` writes."""
+        self.nslots, self.size = int(nslots), int(size)
+        assert self.nslots >= 1 and self.size >= 1
+        lay, f32, B, D, A = self.layout, self.f32, self.B, self.D, self.A
+        self.nq, self.use_cost = int(nq), bool(self.desc.use_cost)
+        nc = self.nq + int(self.use_cost)
+        self.actor_m, self.actor_v, self.actor_t = (torch.zeros_like(self.actor) for _ in range(3))
+        self.critic, self.critic_m, self.critic_v, self.critic_t = (torch.zeros(nc, lay.Pc, **f32) for _ in range(4))
+        self.adam_step = torch.zeros(n_adam, dtype=torch.int32, device=self.device)
+        self.step = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.update_count = 0  # the host's mirror of ``step``: which steps update the actor
+        self.stats = torch.zeros(self.nslots, lay.nstat, **f32)
+        self.idx = torch.zeros(self.nslots, B, dtype=torch.int64, device=self.device)
+        self.ring = {'obs': torch.zeros(self.size, D, **f32), 'act': torch.zeros(self.size, A, **f32),
+                     'reward': torch.zeros(self.size, **f32), 'cost': torch.zeros(self.size, **f32),
+                     'done': torch.zeros(self.size, **f32), 'next_obs': torch.zeros(self.size, D, **f32)}
+        self.pos = torch.zeros(2, dtype=torch.int64, device=self.device)  # write position, rows filled
+        p, r = _lib.ptr, self.ring
         self._ring = Td3Ring(p(r['obs']), p(r['act']), p(r['reward']), p(r['cost']), p(r['done']), p(r['next_obs']),
                              p(self.pos), self.size, D, A)
-        self._draws = Td3DrawBuffers(p(self.idx), p(self.eps), self.nslots)
         self._ix['reward'] = [_index(t, self.device) for t in lay.critic_tensors(self.nq)]
         self._ix['cost'] = [_index(t, self.device) for t in lay.critic_tensors(1)]
 
