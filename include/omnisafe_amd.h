@@ -1416,6 +1416,63 @@ int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_
 int osa_td3_act(const osa_td3_desc* desc, const float* actor, const float* obs, int ld_obs, long n, int mode,
                 float noise, unsigned long long seed, unsigned long long offset, float* out, int ld_out, void* stream);
 
+/* ---- TD3Lag / DDPGLag / TD3PID / DDPGPID (csrc/td3_kernels.hip) --------------------------------------------------------
+ * The constrained members on the step above (ddpg_lag.py, td3_lag.py, ddpg_pid.py, td3_pid.py): the multiplier lives on
+ * the device, the actor loss is mean(-Q_r1(s, pi(s)) + lambda Q_c(s, pi(s))) / (1 + lambda), the ring's cost may be
+ * normalised inside the store launch (envs/wrapper.py:353-408 with common/normalizer.py:88-139). */
+#define OSA_TD3_LAG_ADAM 0 /* Lagrange: torch.optim.Adam on the scalar, loss -lambda (Jc - cost_limit), clamp */
+#define OSA_TD3_LAG_PID 1  /* PIDLagrangian.pid_update */
+#define OSA_TD3_LAG_DACT_GEMM 0    /* layer 0's data gradient as ONE launch of td3_lag_dact_kernel */
+#define OSA_TD3_LAG_DACT_STACKED 1 /* ... as two full-width dX problems and an add-and-tanh' row kernel */
+#define OSA_TD3_LAG_DACT_MAXW 1024 /* widest first critic layer OSA_TD3_LAG_DACT_GEMM takes */
+#define OSA_TD3_LAG_COL 5          /* the statistics column of Metrics/LagrangeMultiplier */
+typedef struct osa_td3_lag {
+  float* multiplier;   /* [1] lambda, float32 */
+  float* adam;         /* [2] ADAM: exp_avg, exp_avg_sq of the scalar */
+  int* count;          /* [1] multiplier updates done (Adam's step count, the PID history's length) */
+  double* pid;         /* [3 + pid_d_delay] PID: integral, error EMA, cost EMA, then the ring of delayed cost EMAs (zero
+                        * at start; pid[0] starts at lagrangian_multiplier_init) */
+  int mode, dact;      /* OSA_TD3_LAG_ADAM / _PID; OSA_TD3_LAG_DACT_* */
+  int window_lens;     /* episodes the mean cost Jc is taken over (the logger's window) */
+  int pid_d_delay, sum_norm, diff_norm;
+  double cost_limit, lambda_lr, upper_bound; /* upper_bound < 0: none */
+  double kp, ki, kd, alpha_p, alpha_d, penalty_max;
+} osa_td3_lag;
+/* floats of osa_td3_lag_step's workspace (osa_td3_ws_floats plus the second critic's pass); 0 for a description that
+ * osa_td3_layout refuses or that has no cost critic.  Host only. */
+size_t osa_td3_lag_ws_floats(const osa_td3_desc* desc);
+/* where in that workspace the actor head's dz [batch][act_dim rounded up to 4] of the last actor step lies, in floats
+ * (what td3_lag_dact_kernel writes: for checks of its values and of its zero padding; a buffer of its own, which
+ * only the backward of an actor with more than one hidden layer writes again).  Host only. */
+size_t osa_td3_lag_dz_offset(const osa_td3_desc* desc);
+/* osa_td3_step with the actor step of ddpg_lag.py:73-100; *lag->multiplier is read on the device when the launches
+ * run.  On actor steps: the actor forward; reward critic 0 and the cost critic on obs || pi(obs), two problems per
+ * launch; one row kernel for dq_r = -1 / (B (1 + lambda)), dq_c = lambda / (B (1 + lambda)) and the rows' loss terms;
+ * the upper layers' data gradients, two problems per launch; layer 0 on lag->dact -- GEMM: td3_lag_dact_kernel, one
+ * launch that multiplies [dZ0_r | dZ0_c] with the action columns of both first layers staged in LDS and applies
+ * 1 - tanh^2, OSA_EUNSUPPORTED for a first width above OSA_TD3_LAG_DACT_MAXW; STACKED: two dX problems and a row
+ * kernel -- then the actor's backward, norm and Adam.  The description must have use_cost 1. */
+int osa_td3_lag_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* state,
+                     const osa_td3_lag* lag, const osa_td3_ring* ring, const osa_td3_draw_buffers* draws, float* stats,
+                     float* ws, size_t ws_floats, long update_count, int nsteps, void* stream);
+/* One single-wave launch after an update round.  Jc = the mean, oldest first in double, of the last window_lens costs
+ * of carry[0 .. ncarry) (earlier epochs' episodes, oldest first) followed by column 1 of ep_out[0 .. min(*ep_count,
+ * ep_cap)) (the running epoch's); update != 0 and at least one episode: the multiplier's step on lag->mode.  No
+ * episode: the multiplier stays (the reference would average an empty window).  Always: lambda into column
+ * OSA_TD3_LAG_COL of statistics row (*step - 1) % nslots. */
+int osa_td3_multiplier_update(const osa_td3_lag* lag, const float* carry, int ncarry, const float* ep_out, long ep_cap,
+                              const long* ep_count, int update, float* stats, const long* step, int nslots,
+                              void* stream);
+/* osa_td3_store with the cost normaliser cn = {mean, sumsq, count} (doubles on the device): one thread pushes the n raw
+ * costs (Normalizer._push: the first push initialises from the batch, later ones are the pairwise update), then every
+ * row's ring cost is clamp((c - mean) / max(sqrt(sumsq / (count - 1)), 1e-2), +-5) in double, rounded to float32; the
+ * raw cost while count <= 1.  ep_acc / ep_out keep the RAW cost. */
+int osa_td3_store_cn(const osa_td3_ring* ring, int n, int obs_dim, int act_dim, const float* obs, int ld_obs,
+                     const float* act, int ld_act, const float* reward, const float* cost,
+                     const unsigned char* terminated, const unsigned char* truncated, const float* next_obs, int ld_next,
+                     const float* final_obs, int ld_final, const unsigned char* final_mask, float* ep_acc, float* ep_out,
+                     long ep_cap, long* ep_count, double* cn, void* stream);
+
 /* ---- off-policy SAC (csrc/sac_kernels.hip) ------------------------------------------------------------------------------
  * One gradient step of omnisafe/algorithms/off_policy/sac.py:93-207 on ddpg.py:350-400 from the replay ring of
  * osa_td3_ring (written by osa_td3_store).  Networks: the tanh-squashed Gaussian actor (GaussianSACActor: hidden layers

@@ -178,6 +178,13 @@ SIGNATURES: dict[str, tuple] = {
     'osa_td3_draws': (_I, [_P, _U, _L, _I, _I, _P, _P, _P, _P]),
     'osa_td3_step': (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _L, _I, _P]),
     'osa_td3_act': (_I, [_P, _P, _P, _I, _L, _I, C.c_float, _U, _U, _P, _I, _P]),
+    # TD3Lag / DDPGLag / TD3PID / DDPGPID: osa_td3_lag is td3_step.Td3Lag
+    'osa_td3_lag_ws_floats': (C.c_size_t, [_P]),
+    'osa_td3_lag_dz_offset': (C.c_size_t, [_P]),
+    'osa_td3_lag_step': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _L, _I, _P]),
+    'osa_td3_multiplier_update': (_I, [_P, _P, _I, _P, _L, _P, _I, _P, _P, _I, _P]),
+    'osa_td3_store_cn': (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _L, _P, _P,
+                              _P]),
     # off-policy SAC (csrc/sac_kernels.hip): structs of sac_step.py, passed by reference; the ring is TD3's
     'osa_sac_layout': (_I, [_P, _P]),
     'osa_sac_ws_floats': (C.c_size_t, [_P]),

@@ -8,7 +8,7 @@ from .siblings import (CPPOPID, CUP, FOCOPS, IPO, P3O, PCPO, PDO, RCPO, TRPOPID,
 ALGORITHMS = {'on-policy': tuple(sorted(registry.REGISTRY._module_dict))}  # noqa: SLF001
 from .offline import BCQ, CCRR, CRR, VAEBC, BCQLag, COptiDICE  # noqa: E402  (after the on-policy tuple: the registry holds every family)
 
-from .off_policy import DDPG, SAC, TD3  # noqa: E402
+from .off_policy import DDPG, DDPGPID, SAC, TD3, TD3PID, DDPGLag, TD3Lag  # noqa: E402
 
 ALGORITHMS['offline'] = ('CCRR', 'CRR')
 ALGORITHMS['offline-bc'] = ('VAEBC',)
@@ -16,6 +16,7 @@ ALGORITHMS['offline-dice'] = ('COptiDICE',)
 ALGORITHMS['offline-bcq'] = ('BCQ', 'BCQLag')
 ALGORITHMS['off-policy'] = ('DDPG', 'TD3')
 ALGORITHMS['off-policy-sac'] = ('SAC',)
-__all__ = ['DDPG', 'TD3', 'SAC', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'COptiDICE', 'PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
+ALGORITHMS['off-policy-lag'] = ('DDPGLag', 'DDPGPID', 'TD3Lag', 'TD3PID')
+__all__ = ['DDPG', 'TD3', 'SAC', 'DDPGLag', 'TD3Lag', 'DDPGPID', 'TD3PID', 'CRR', 'CCRR', 'VAEBC', 'BCQ', 'BCQLag', 'COptiDICE', 'PolicyGradient', 'PPO', 'PPOLag', 'NaturalPG', 'TRPO', 'TRPOLag', 'CPO', 'PDO', 'RCPO', 'IPO',
            'OnCRPO', 'CPPOPID', 'TRPOPID', 'PCPO', 'FOCOPS', 'CUP', 'P3O', 'PPOSaute', 'TRPOSaute',
            'PPOSimmerPID', 'TRPOSimmerPID', 'registry', 'ALGORITHMS']

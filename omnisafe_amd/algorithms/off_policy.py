@@ -13,7 +13,8 @@ Deviations from the reference:
   * The env must be a device env (a built-in family or one of ``register_device_env``); a host env raises
     NotImplementedError.
   * ``obs_normalize``, ``reward_normalize``, ``cost_normalize`` and ``linear_lr_decay`` set to True raise
-    NotImplementedError (the YAML default is False for all four).
+    NotImplementedError (the YAML default is False for all four); DDPGLag, TD3Lag, DDPGPID and TD3PID, whose YAMLs set
+    ``cost_normalize: True``, take it: the normaliser runs inside the store launch.
   * One ring of ``size`` rows shared by the envs, written ``vector_env_nums`` rows at a time (the reference keeps
     ``size`` rows per env).
   * All draws (warm-up actions, exploration noise, minibatch indices, target-policy noise) are Philox streams on the
@@ -44,6 +45,8 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
     stat_keys = K           # the columns of a statistics row
     actor_cols = (2,)       # ... that only an actor step writes
     step_mod = td3_step     # make_desc and the step class come from here
+    round_cols = ()         # ... that a launch after the round's last step writes: one value per round
+    refused = ('obs_normalize', 'reward_normalize', 'cost_normalize', 'linear_lr_decay')
 
     def _hparams(self) -> dict:
         """DDPG: TD3 with one critic, no target-policy noise and the online actor in the target (ddpg.py:424)."""
@@ -58,7 +61,7 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
                                       '(the built-in families and those of register_device_env)')
         for name, on in (('obs_normalize', a.obs_normalize), ('reward_normalize', a.reward_normalize),
                          ('cost_normalize', a.cost_normalize), ('linear_lr_decay', m.linear_lr_decay)):
-            if on:
+            if on and name in self.refused:
                 raise NotImplementedError(f'{name}=True is not implemented for the off-policy family')
         self._num_envs = int(t.vector_env_nums)
         env_cfgs = dict(self._cfgs.env_cfgs.todict()) if hasattr(self._cfgs, 'env_cfgs') else {}
@@ -135,6 +138,12 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
         for key, window in keys:
             self._logger.register_key(key, window_length=window)
 
+    def _after_round(self, epoch: int) -> None:
+        """What follows the gradient steps of an update round on the stream (the multiplier's launch)."""
+
+    def _after_epoch(self, n_ep: int) -> None:
+        """What follows the epoch's one read of the device; ``n_ep`` episodes finished in it."""
+
     def _logged_cols(self) -> list:
         """The statistics columns this run logs: the cost critic's with ``use_cost`` only."""
         return [0, 1, 2] + ([3, 4] if self._cfgs.algo_cfgs.use_cost else [])
@@ -163,6 +172,7 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
             for _ in range(int(a.update_iters)):
                 st.draw(self._seed, st.update_count, 1)  # after the store: the fill count is read on the device
                 st.run(1)
+            self._after_round(epoch)
         env.commit()
         slots = (torch.arange(st.update_count - first_update, device=self._device) + first_update) % self._nslots
         return slots, idle
@@ -181,6 +191,7 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
                 rows = self._step.stats[slots][:, :len(keys)].cpu() if slots.numel() else torch.zeros(0, len(keys))
                 n_ep = int(self._episodes[2].cpu())
                 eps = self._episodes[1][:min(n_ep, self._episodes[1].shape[0])].cpu()
+                self._after_epoch(min(n_ep, self._episodes[1].shape[0]))
                 self._episodes[2].zero_()
                 update_time = time.time() - epoch_time
                 iters, delay = int(a.update_iters), int(a.policy_delay)
@@ -192,7 +203,8 @@ class BaseOffPolicy(BaseAlgo):  # pylint: disable=too-many-instance-attributes
                 self.epoch_stats.append(per_round.tolist())
                 for col in self._logged_cols():
                     vals = [float(idle_row[col])] * idle + [float(v) for i, v in enumerate(rows[:, col].tolist())
-                                                            if col not in self.actor_cols or actor_rows[i]]
+                                                            if (col not in self.actor_cols or actor_rows[i])
+                                                            and (col not in self.round_cols or (i + 1) % iters == 0)]
                     self._logger.extend(keys[col], vals or [0.0])
                 for k, col in (('Metrics/EpRet', 0), ('Metrics/EpCost', 1), ('Metrics/EpLen', 2)):
                     self._logger.extend(k, eps[:, col].tolist())
@@ -281,4 +293,79 @@ class SAC(BaseOffPolicy):
         return super()._logged_cols() + [5] + ([6] if self._cfgs.algo_cfgs.auto_alpha else [])
 
 
-__all__ = ['BaseOffPolicy', 'DDPG', 'TD3', 'SAC']
+class _OffPolicyLag(BaseOffPolicy):
+    """What DDPGLag, TD3Lag, DDPGPID and TD3PID add to their base (ddpg_lag.py:38-112 and its three siblings): the cost
+    critic in the actor loss, ``cost_normalize`` and the multiplier -- all on the device (td3_step.Td3LagStep).  After
+    every update round of an epoch > ``warmup_epochs`` one launch takes the multiplier's step on the mean cost of the
+    last ``window_lens`` finished episodes: a carry of the earlier epochs' tail, refreshed on the device after the
+    epoch's one read, followed by the running epoch's episodes.
+
+    Deviation: while no episode has finished, the step is skipped (the reference averages an empty window: nan)."""
+
+    stat_keys = td3_step.LAG_STAT_KEYS
+    round_cols = (5,)
+    refused = ('obs_normalize', 'reward_normalize', 'linear_lr_decay')
+
+    def _init_env(self) -> None:
+        td3_step.check_lagrange_cfgs(self._cfgs.lagrange_cfgs.todict())  # (before any GPU is touched)
+        self._cfgs.algo_cfgs.recurisve_update({'use_cost': True})
+        super()._init_env()
+
+    def _make_step(self, desc, **kw):
+        return td3_step.Td3LagStep(desc, lagrange_cfgs=self._cfgs.lagrange_cfgs.todict(),
+                                   window_lens=int(self._cfgs.logger_cfgs.window_lens),
+                                   cost_normalize=bool(self._cfgs.algo_cfgs.cost_normalize), **kw)
+
+    def _init(self) -> None:
+        super()._init()
+        self._carry = torch.zeros(int(self._cfgs.logger_cfgs.window_lens), dtype=torch.float32, device=self._device)
+        self._ncarry = 0
+
+    def _idle_row(self) -> list:
+        """``_log_when_not_update``: the multiplier as it stands -- the initial one, since no round idles once learning
+        has started."""
+        row = super()._idle_row()
+        row[5] = self._step.initial_multiplier
+        return row
+
+    def _logged_cols(self) -> list:
+        return super()._logged_cols() + [5]
+
+    def _after_round(self, epoch: int) -> None:
+        self._step.update_multiplier(self._carry, self._ncarry, self._episodes,
+                                     update=epoch > int(self._cfgs.algo_cfgs.warmup_epochs))
+
+    def _after_epoch(self, n_ep: int) -> None:
+        window = self._carry.shape[0]
+        tail = torch.cat([self._carry[:self._ncarry], self._episodes[1][:n_ep, 1]])[-window:]
+        self._ncarry = int(tail.shape[0])
+        self._carry[:self._ncarry] = tail
+
+
+@register
+class DDPGLag(_OffPolicyLag):
+    """DDPG with a Lagrange multiplier (ddpg_lag.py:28-112)."""
+
+
+@register
+class TD3Lag(_OffPolicyLag):
+    """TD3 with a Lagrange multiplier (td3_lag.py:28-112)."""
+
+    num_critics = 2
+    _hparams = TD3._hparams  # noqa: SLF001
+
+
+@register
+class DDPGPID(_OffPolicyLag):
+    """DDPG with a PID-controlled multiplier (ddpg_pid.py:28-111)."""
+
+
+@register
+class TD3PID(_OffPolicyLag):
+    """TD3 with a PID-controlled multiplier (td3_pid.py:28-111)."""
+
+    num_critics = 2
+    _hparams = TD3._hparams  # noqa: SLF001
+
+
+__all__ = ['BaseOffPolicy', 'DDPG', 'TD3', 'SAC', 'DDPGLag', 'TD3Lag', 'DDPGPID', 'TD3PID']

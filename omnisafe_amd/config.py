@@ -263,6 +263,32 @@ _SAC['algo_cfgs'].update({'penalty_coef': 0.0, 'start_learning_steps': 10000, 'u
 _SAC['model_cfgs']['actor_type'] = 'gaussian_sac'
 SAC_DEFAULTS = {'SAC': _SAC}
 
+# ---- the constrained deterministic-actor members (configs/off-policy/{DDPGLag,TD3Lag,DDPGPID,TD3PID}.yaml): their base's
+# blocks with the cost critic and the cost normaliser on, the warm-up epochs of the multiplier, a window of 10 and the
+# multiplier's block; the PID forms take an actor lr of 1e-4.  A table of its own like SAC's.
+_OFFPOLICY_LAGRANGE = {'cost_limit': 25.0, 'lagrangian_multiplier_init': 0.001, 'lambda_lr': 0.00001,
+                       'lambda_optimizer': 'Adam'}
+_OFFPOLICY_PID = {'pid_kp': 0.000001, 'pid_ki': 0.0000001, 'pid_kd': 0.0000001, 'pid_d_delay': 10,
+                  'pid_delta_p_ema_alpha': 0.95, 'pid_delta_d_ema_alpha': 0.95, 'sum_norm': True, 'diff_norm': False,
+                  'cost_limit': 25.0, 'penalty_max': 100.0, 'lagrangian_multiplier_init': 0.001}
+
+
+def _offpolicy_lag(base: dict, lagrange: dict, actor_lr: float | None = None) -> dict:
+    d = copy.deepcopy(base)
+    d['algo_cfgs'].update({'cost_normalize': True, 'use_cost': True, 'warmup_epochs': 100})
+    d['logger_cfgs']['window_lens'] = 10
+    if actor_lr is not None:
+        d['model_cfgs']['actor']['lr'] = actor_lr
+    d['lagrange_cfgs'] = copy.deepcopy(lagrange)
+    return d
+
+
+OFFPOLICY_LAG_DEFAULTS = {
+    'DDPGLag': _offpolicy_lag(_DDPG, _OFFPOLICY_LAGRANGE), 'TD3Lag': _offpolicy_lag(_TD3, _OFFPOLICY_LAGRANGE),
+    # (DDPGPID.yaml starts its multiplier at 0.000, TD3PID.yaml at 0.001)
+    'DDPGPID': _offpolicy_lag(_DDPG, dict(_OFFPOLICY_PID, lagrangian_multiplier_init=0.0), 0.0001),
+    'TD3PID': _offpolicy_lag(_TD3, _OFFPOLICY_PID, 0.0001)}
+
 
 def get_default_kwargs(algo: str) -> dict:
     """get_default_kwargs_yaml (config.py:235-262) for the accelerated algorithms."""
@@ -278,8 +304,9 @@ def get_default_kwargs(algo: str) -> dict:
 def default_kwargs(algo: str) -> dict:
     """The defaults of any registered algorithm: what ``Agent`` reads.  ``get_default_kwargs`` keeps to the three
     tables it was written for -- tests/test_crr_cpu.py and tests/test_vae_cpu.py hold it to a KeyError for 'BCQ' --
-    so the BCQ family, COptiDICE, the off-policy family and SAC are looked up here, in their own tables."""
-    for table in (BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, SAC_DEFAULTS):
+    so the BCQ family, COptiDICE, the off-policy family, its constrained members and SAC are looked up here, in their
+    own tables."""
+    for table in (BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, SAC_DEFAULTS, OFFPOLICY_LAG_DEFAULTS):
         if algo in table:
             return copy.deepcopy(table[algo])
     return get_default_kwargs(algo)
@@ -299,15 +326,25 @@ def check_all_configs(cfgs: Config) -> None:
     """Subset of config.py:265-409 that guards this path."""
     a = cfgs.algo_cfgs
     algo = getattr(cfgs, 'algo', None)
-    if algo in OFFPOLICY_DEFAULTS or algo in SAC_DEFAULTS:  # (config.py:362-409's off-policy part: no GAE, no KL)
-        t = cfgs.train_cfgs
+    if algo in OFFPOLICY_DEFAULTS or algo in SAC_DEFAULTS or algo in OFFPOLICY_LAG_DEFAULTS:
+        t = cfgs.train_cfgs  # (config.py:362-409's off-policy part: no GAE, no KL)
         if algo in SAC_DEFAULTS:
             assert a.alpha > 0, 'alpha must be positive'
+        if algo in OFFPOLICY_LAG_DEFAULTS:
+            g = cfgs.lagrange_cfgs
+            assert isinstance(a.warmup_epochs, int) and a.warmup_epochs >= 0, 'warmup_epochs must be an int >= 0'
+            assert g.cost_limit >= 0 and g.lagrangian_multiplier_init >= 0
+            assert isinstance(cfgs.logger_cfgs.window_lens, int) and cfgs.logger_cfgs.window_lens >= 1
+            if 'pid_kp' in g:
+                assert min(g.pid_kp, g.pid_ki, g.pid_kd) >= 0 and isinstance(g.pid_d_delay, int) and g.pid_d_delay >= 1
+                assert 0.0 <= g.pid_delta_p_ema_alpha <= 1.0 and 0.0 <= g.pid_delta_d_ema_alpha <= 1.0
+            else:
+                assert g.lambda_lr >= 0
         for k in ('steps_per_epoch', 'update_cycle', 'update_iters', 'size', 'batch_size', 'policy_delay'):
             assert isinstance(a[k], int) and a[k] > 0, f'{k} must be a positive int'
         assert 0.0 <= a.gamma <= 1.0 and 0.0 <= a.polyak <= 1.0 and a.start_learning_steps >= 0
         assert a.exploration_noise >= 0 and a.critic_norm_coeff >= 0 and (a.max_grad_norm or 0) >= 0
-        if algo == 'TD3':
+        if algo in ('TD3', 'TD3Lag', 'TD3PID'):
             assert a.policy_noise >= 0 and a.policy_noise_clip >= 0
         assert isinstance(t.total_steps, int) and t.total_steps > 0 and t.eval_episodes >= 0
         assert t.vector_env_nums >= 1 and t.parallel == 1, 'the off-policy family supports parallel 1 only'

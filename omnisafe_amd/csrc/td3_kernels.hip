@@ -19,6 +19,12 @@
 // The layer route (OSA_TD3_ROUTE_LAYER) runs the same forward as one tile-GEMM launch per layer with small row kernels
 // between the networks: the fallback for a hidden width above 256 or an observation too wide for the LDS budget, and the
 // baseline the fused kernel is measured against.
+//
+// The constrained members (ddpg_lag.py, td3_lag.py, ddpg_pid.py, td3_pid.py) add three pieces further down: the cost
+// normaliser inside td3_store_kernel (td3_cn_push), td3_multiplier_kernel -- the Adam or PID step of the multiplier on
+// the windowed mean episode cost, one single-wave launch per update round -- and the actor step on reward critic 0 and
+// the cost critic, whose layer-0 data gradient runs as td3_lag_dact_kernel (one K-concatenated MFMA tile over the action
+// columns staged in LDS) or as two dX problems and td3_lag_dpi_kernel.
 #include <math.h>
 
 #include "offpolicy_shared.h"
@@ -325,6 +331,191 @@ __global__ __launch_bounds__(256) void td3_dpi_kernel(int B, int A, int D, int l
 }
 // (td3_critic_dx, the norm, Adam and finish kernels: offpolicy_shared.h)
 
+// ---- the constrained actor step (ddpg_lag.py:73-100) -----------------------------------------------------------------
+// Extra workspace behind TD3's: the cost critic's layer outputs on obs || pi(obs), its input gradient (the stacked
+// composition only) and the rows' negated loss terms [B][4], which the actor's Adam launch averages.
+struct TLagWs {
+  size_t hqc[GM_MAXL], dxc, nl, dzpi, total;
+};
+TLagWs td3_lag_ws(const TLayout& lo, const TWs& w) {
+  TLagWs x = {};
+  size_t off = w.total;
+  auto take = [&](size_t n) {
+    const size_t o = off;
+    off += (n + 3) / 4 * 4;
+    return o;
+  };
+  const size_t B = lo.B;
+  for (int l = 0; l < GM_MAXL; ++l) x.hqc[l] = l < lo.q.L ? take(B * lo.q.ldh[l]) : 0;
+  x.dxc = take(B * lo.ldsa);
+  x.nl = take(4 * B);
+  x.dzpi = take(B * lo.pi.maxldh);  // the head's dz: with one hidden actor layer no backward writes it again
+  x.total = off;
+  return x;
+}
+
+// loss row b = (-q_r + lambda q_c) / (1 + lambda); its negative goes to nl[b][0] (the Adam launch logs -mean), the two
+// top-layer gradients d loss / d q to dzr and dzc
+__global__ __launch_bounds__(256) void td3_lag_row_kernel(int B, const float* __restrict__ lambda,
+                                                          const float* __restrict__ qr, const float* __restrict__ qc,
+                                                          float* __restrict__ dzr, float* __restrict__ dzc,
+                                                          float* __restrict__ nl) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float lam = *lambda, inv = 1.f / (1.f + lam), invB = inv / (float)B;
+  const f32x4 dr = {-invB, 0.f, 0.f, 0.f}, dc = {lam * invB, 0.f, 0.f, 0.f};
+  const f32x4 l = {(qr[4 * (long)b] - lam * qc[4 * (long)b]) * inv, 0.f, 0.f, 0.f};
+  *reinterpret_cast<f32x4*>(dzr + 4 * (long)b) = dr;
+  *reinterpret_cast<f32x4*>(dzc + 4 * (long)b) = dc;
+  *reinterpret_cast<f32x4*>(nl + 4 * (long)b) = l;
+}
+
+// Layer 0 of both critics' data gradient, straight to the actor head's dz:
+//   dz[b][j] = (sum_n dZ0_r[b][n] W0_r[n][D + j] + sum_n dZ0_c[b][n] W0_c[n][D + j]) (1 - th[b][j]^2),  j < A <= 32
+// ONE GEMM with K concatenated over both critics and a single 32-column MFMA tile of output: the D observation columns
+// that two full-width dX GEMMs would compute and nobody reads are never formed, and the sum and the tanh' ride on the
+// write-back.  A workgroup of four waves owns 32 rows.  The B operand -- the action columns W0[:, D : D + A], a walk of
+// stride ld in global memory -- is staged once per workgroup into LDS as [k][32] (row stride 40 floats: the two lane
+// groups of an MFMA step read rows 4 apart = 160 floats, 32 banks apart), DA_KC rows at a time, a wider slab in chunks;
+// the A operand, rows of dZ0, comes from global memory as 16-byte loads along K into float32 32x32x2 MFMAs.  K of a chunk
+// is split over the four waves; the partial tiles meet in LDS and are added in wave order (chain_layer.h's one-tile
+// branch).  No atomics, no cooperative groups, no spin-waits.
+// LDS: DA_KC x 40 floats of slab (40 KB) + 4 partial tiles (16 KB) = 56 KB static.
+constexpr int DA_KC = 256, DA_LD = 40;
+struct TDact {
+  const float* dz0[2];  // [B][ldz]: dL/d(layer 0's pre-activation) of the reward critic, of the cost critic
+  const float* W0[2];   // [H][ldw]: their first layers
+  const float* th;      // [B][lda] tanh of the actor's head
+  float* dz;            // [B][lda]
+  int B, A, D, H, ldz, ldw, lda;
+};
+__global__ __launch_bounds__(256) void td3_lag_dact_kernel(TDact g) {
+  __shared__ __attribute__((aligned(16))) float slab[DA_KC * DA_LD];
+  __shared__ float part[BC_PART];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kk = lane >> 5;
+  const int m0 = blockIdx.x * BC_ROWS, H = g.H;
+  const bool rok = m0 + l31 < g.B;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  for (int c = 0; c < 2; ++c) {
+    const float* __restrict__ W = c == 0 ? g.W0[0] : g.W0[1];
+    const float* __restrict__ arow = (c == 0 ? g.dz0[0] : g.dz0[1]) + (long)(m0 + l31) * g.ldz + 4 * kk;
+    for (int k0 = 0; k0 < H; k0 += DA_KC) {
+      const int live = H - k0 < DA_KC ? H - k0 : DA_KC, nks = (live + 7) >> 3;  // K steps of 8 in this chunk
+      // stage rows k0 .. k0 + 8 nks of the action columns; rows past H and columns past A are zero
+      for (int k = tid >> 5; k < 8 * nks; k += 8)
+        slab[k * DA_LD + l31] = (k < live && l31 < g.A) ? W[(long)(k0 + k) * g.ldw + g.D + l31] : 0.f;
+      __syncthreads();
+      const int per = (nks + 3) >> 2, s0 = wave * per, s1 = s0 + per < nks ? s0 + per : nks;
+      for (int s = s0; s < s1; ++s) {
+        const int k = 8 * s + 4 * kk;  // this lane group's four K values of the step (within the chunk)
+        f32x4 af = (rok && k0 + k < g.ldz) ? *reinterpret_cast<const f32x4*>(arow + k0 + 8 * s) : zero;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (k + q >= live) af[q] = 0.f;  // (a dX launch leaves the padding columns of dZ0 unwritten)
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q], slab[(k + q) * DA_LD + l31], acc, 0, 0, 0);
+        }
+      }
+      __syncthreads();  // the slab is free for the next chunk
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) part[(wave * 16 + r) * 64 + lane] = acc[r];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = 4 * wave + i, m = m0 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+    float v = part[(0 * 16 + r) * 64 + lane];
+    v += part[(1 * 16 + r) * 64 + lane];
+    v += part[(2 * 16 + r) * 64 + lane];
+    v += part[(3 * 16 + r) * 64 + lane];
+    if (m < g.B && l31 < g.lda) {
+      float d = 0.f;
+      if (l31 < g.A) {
+        const float t = g.th[(long)m * g.lda + l31];
+        d = v * (1.f - t * t);
+      }
+      g.dz[(long)m * g.lda + l31] = d;
+    }
+  }
+}
+// the stacked composition's row kernel: dz = (dx_r + dx_c)[action columns] (1 - tanh^2); padding zero
+__global__ __launch_bounds__(256) void td3_lag_dpi_kernel(int B, int A, int D, int lda, int ldsa,
+                                                          const float* __restrict__ dxr, const float* __restrict__ dxc,
+                                                          const float* __restrict__ th, float* __restrict__ dz) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * lda) return;
+  const int b = e / lda, j = e - b * lda;
+  float d = 0.f;
+  if (j < A) {
+    const float t = th[e];
+    d = (dxr[(long)b * ldsa + D + j] + dxc[(long)b * ldsa + D + j]) * (1.f - t * t);
+  }
+  dz[e] = d;
+}
+
+// ---- the multiplier (common/lagrange.py:95-136, common/pid_lagrange.py:98-146) ---------------------------------------
+struct TMult {
+  osa_td3_lag L;
+  const float *carry, *ep_out;
+  const long *ep_count, *step;
+  float* stats;
+  long ep_cap;
+  int ncarry, update, nslots;
+};
+__global__ __launch_bounds__(64) void td3_multiplier_kernel(TMult g) {
+  if (threadIdx.x != 0) return;
+  const osa_td3_lag& L = g.L;
+  long ne = *g.ep_count;
+  if (ne > g.ep_cap) ne = g.ep_cap;
+  if (ne < 0) ne = 0;
+  const long total = g.ncarry + ne, first = total > L.window_lens ? total - L.window_lens : 0;
+  if (g.update && total > 0) {
+    double sum = 0.0;  // oldest first
+    for (long i = first; i < total; ++i)
+      sum = __dadd_rn(sum, (double)(i < g.ncarry ? g.carry[i] : g.ep_out[3 * (i - g.ncarry) + 1]));
+    const double Jc = __ddiv_rn(sum, (double)(total - first));
+    const int t = *L.count;
+    if (L.mode == OSA_TD3_LAG_ADAM) {  // the gradient of -lambda (Jc - limit), rounded to float32 as autograd leaves it
+      const float grad = (float)(-(__dsub_rn(Jc, L.cost_limit)));
+      const float b2 = (float)0.999, omb1 = (float)(1.0 - 0.9), omb2 = (float)(1.0 - 0.999);
+      float m = L.adam[0], v = L.adam[1];
+      m = __fadd_rn(m, __fmul_rn(__fsub_rn(grad, m), omb1));                      // exp_avg.lerp_(grad, 1 - beta1)
+      v = __fadd_rn(__fmul_rn(v, b2), __fmul_rn(__fmul_rn(omb2, grad), grad));  // .mul_(beta2).addcmul_(g, g, 1 - beta2)
+      const double bc1 = 1.0 - pow(0.9, (double)(t + 1)), bc2 = 1.0 - pow(0.999, (double)(t + 1));
+      const float step_size = (float)(L.lambda_lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+      const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), (float)1e-8);
+      float lam = __fsub_rn(*L.multiplier, __fmul_rn(step_size, __fdiv_rn(m, denom)));
+      lam = fmaxf(lam, 0.f);
+      if (L.upper_bound >= 0.0) lam = fminf(lam, (float)L.upper_bound);
+      L.adam[0] = m; L.adam[1] = v;
+      *L.multiplier = lam;
+    } else {  // pid_lagrange.py::pid_step, in double and in its order
+      double* s = L.pid;
+      double* hist = s + 3;
+      const int depth = L.pid_d_delay;
+      const double err = __dsub_rn(Jc, L.cost_limit);
+      double integral = fmax(0.0, __dadd_rn(s[0], __dmul_rn(err, L.ki)));
+      if (L.diff_norm) integral = fmax(0.0, fmin(1.0, integral));
+      const double err_ema = __dadd_rn(__dmul_rn(s[1], L.alpha_p), __dmul_rn(__dsub_rn(1.0, L.alpha_p), err));
+      const double cost_ema = __dadd_rn(__dmul_rn(s[2], L.alpha_d), __dmul_rn(__dsub_rn(1.0, L.alpha_d), Jc));
+      const int oldest = t + 1 - depth > 0 ? t + 1 - depth : 0;  // history = the last `depth` of {0, ema_1, .., ema_t}
+      const double rise = fmax(0.0, __dsub_rn(cost_ema, hist[oldest % depth]));
+      double out = fmax(0.0, __dadd_rn(__dadd_rn(__dmul_rn(L.kp, err_ema), integral), __dmul_rn(L.kd, rise)));
+      if (L.diff_norm) out = fmin(1.0, out);
+      else if (!L.sum_norm) out = fmin(out, L.penalty_max);
+      hist[(t + 1) % depth] = cost_ema;
+      s[0] = integral; s[1] = err_ema; s[2] = cost_ema;
+      *L.multiplier = (float)out;
+    }
+    *L.count = t + 1;
+  }
+  const long done = *g.step > 0 ? *g.step - 1 : 0;
+  g.stats[(done % g.nslots) * OSA_TD3_NSTAT + OSA_TD3_LAG_COL] = *L.multiplier;
+}
+
 // ---- ring, draws, act ------------------------------------------------------------------------------------------------
 struct TStore {
   osa_td3_ring r;
@@ -334,9 +525,39 @@ struct TStore {
   float *ep_acc, *ep_out;
   long ep_cap;
   long* ep_count;
+  double* cn;  // the cost normaliser {mean, sumsq, count}, or null
 };
+// Normalizer._push of the n raw costs (normalizer.py:110-139) by one thread, in double with every operation rounded on
+// its own (no contraction: a float64 restatement on the host gives the same bits); out = {mean, std, count}
+__device__ void td3_cn_push(double* cn, const float* __restrict__ cost, int n, double* out) {
+  double sum = 0.0;
+  for (int i = 0; i < n; ++i) sum = __dadd_rn(sum, (double)cost[i]);
+  const double mean_raw = __ddiv_rn(sum, (double)n);
+  double sq = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const double d = __dsub_rn((double)cost[i], mean_raw);
+    sq = __dadd_rn(sq, __dmul_rn(d, d));
+  }
+  double mean = mean_raw, sumsq = sq, count = (double)n;
+  if (cn[2] > 0.0) {  // the pairwise update of Chan, Golub and LeVeque
+    const double old = cn[2], delta = __dsub_rn(mean_raw, cn[0]);
+    count = __dadd_rn(old, (double)n);
+    mean = __dadd_rn(cn[0], __ddiv_rn(__dmul_rn(delta, (double)n), count));
+    const double cross = __ddiv_rn(__dmul_rn(__dmul_rn(__dmul_rn(delta, delta), old), (double)n), count);
+    sumsq = __dadd_rn(cn[1], __dadd_rn(sq, cross));
+  }
+  cn[0] = mean; cn[1] = sumsq; cn[2] = count;
+  out[0] = mean;
+  out[1] = count > 1.0 ? fmax(__dsqrt_rn(__ddiv_rn(sumsq, __dsub_rn(count, 1.0))), 1e-2) : 1.0;
+  out[2] = count;
+}
 __global__ __launch_bounds__(256) void td3_store_kernel(TStore g) {
+  __shared__ double cn[3];
   const long pos = g.r.pos[0], fill = g.r.pos[1];
+  if (g.cn) {
+    if (threadIdx.x == 0) td3_cn_push(g.cn, g.cost, g.n, cn);
+    __syncthreads();
+  }
   const int W = g.D + g.A + g.D;
   for (int e = threadIdx.x; e < g.n * W; e += 256) {
     const int i = e / W, c = e - i * W;
@@ -357,7 +578,10 @@ __global__ __launch_bounds__(256) void td3_store_kernel(TStore g) {
   for (int i = threadIdx.x; i < g.n; i += 256) {
     const long row = (pos + i) % g.r.size;
     g.r.reward[row] = g.reward[i];
-    g.r.cost[row] = g.cost[i];
+    float c = g.cost[i];
+    if (g.cn && cn[2] > 1.0)  // Normalizer.normalize, clip 5; count <= 1: the raw cost
+      c = (float)fmin(fmax(__ddiv_rn(__dsub_rn((double)c, cn[0]), cn[1]), -5.0), 5.0);
+    g.r.cost[row] = c;
     g.r.done[row] = g.term[i] ? 1.f : 0.f;
   }
   __syncthreads();  // every thread has read the position
@@ -525,6 +749,43 @@ int td3_forward(const TLayout& lo, const TWs& w, const osa_td3_hparams* hp, cons
   return OSA_OK;
 }
 
+// both critics' data gradients from the top layer down to layer `stop`, two problems per launch; returns the index of
+// the ping-pong buffers z[0][.] (reward critic 0) and z[2][.] (cost critic) that hold layer stop's dZ
+int td3_lag_critics_dx(const TLayout& lo, const TWs& w, const TLagWs& x, const float* critic, int stop, float* ws,
+                       hipStream_t st, int* cur_out) {
+  const CNet& n = lo.q;
+  int cur = 0;
+  for (int l = n.L - 1; l >= stop; --l) {
+    GArgs gd = {};
+    gd.splits = 1;
+    for (int k = 0; k < 2; ++k) {
+      const int j = k == 0 ? 0 : 2;
+      GProb q = crr_prob();  // dZ_{l-1}[rows][in] = (dZ_l[rows][out] . W_l[out][in]) * act'(H_{l-1})
+      q.A = ws + w.z[j][cur]; q.lda = n.ldh[l];
+      q.B = critic + (long)(k == 0 ? 0 : lo.nq) * n.P + n.oW[l]; q.ldb = n.ld[l];
+      q.M = lo.B; q.N = n.in[l]; q.K = n.out[l];
+      if (l > 0) {
+        q.C = ws + w.z[j][cur ^ 1]; q.ldc = n.ldh[l - 1];
+        q.dact = n.act; q.aux = ws + (k == 0 ? w.hq[l - 1] : x.hqc[l - 1]); q.ldaux = n.ldh[l - 1];
+      } else {
+        q.C = ws + (k == 0 ? w.dx : x.dxc); q.ldc = lo.ldsa;
+      }
+      gd.p[gd.nprob++] = q;
+    }
+    const int rc = gm_gemm<false, true>(gd, st);
+    if (rc != OSA_OK) return rc;
+    cur ^= 1;
+  }
+  *cur_out = cur;
+  return OSA_OK;
+}
+
+int td3_lag_ok(const TLayout& lo, const osa_td3_lag* lag) {
+  if (!lag->multiplier || !lo.cost) return OSA_EINVAL;
+  if (lag->dact != OSA_TD3_LAG_DACT_GEMM && lag->dact != OSA_TD3_LAG_DACT_STACKED) return OSA_EINVAL;
+  return lag->dact == OSA_TD3_LAG_DACT_GEMM && lo.q.out[0] > OSA_TD3_LAG_DACT_MAXW ? OSA_EUNSUPPORTED : OSA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -562,13 +823,24 @@ int osa_td3_store(const osa_td3_ring* ring, int n, int obs_dim, int act_dim, con
                   const float* act, int ld_act, const float* reward, const float* cost, const unsigned char* terminated,
                   const unsigned char* truncated, const float* next_obs, int ld_next, const float* final_obs, int ld_final,
                   const unsigned char* final_mask, float* ep_acc, float* ep_out, long ep_cap, long* ep_count, void* stream) {
+  return osa_td3_store_cn(ring, n, obs_dim, act_dim, obs, ld_obs, act, ld_act, reward, cost, terminated, truncated,
+                          next_obs, ld_next, final_obs, ld_final, final_mask, ep_acc, ep_out, ep_cap, ep_count, nullptr,
+                          stream);
+}
+
+int osa_td3_store_cn(const osa_td3_ring* ring, int n, int obs_dim, int act_dim, const float* obs, int ld_obs,
+                     const float* act, int ld_act, const float* reward, const float* cost,
+                     const unsigned char* terminated, const unsigned char* truncated, const float* next_obs, int ld_next,
+                     const float* final_obs, int ld_final, const unsigned char* final_mask, float* ep_acc, float* ep_out,
+                     long ep_cap, long* ep_count, double* cn, void* stream) {
   OSA_REQUIRE(obs_dim >= 1 && act_dim >= 1 && td3_ring_ok(ring, obs_dim, act_dim));
+  OSA_REQUIRE((reinterpret_cast<uintptr_t>(cn) & 7) == 0);
   OSA_REQUIRE(n >= 1 && n <= ring->size && obs && act && reward && cost && terminated && truncated && next_obs);
   OSA_REQUIRE(ld_obs >= obs_dim && ld_act >= act_dim && ld_next >= obs_dim);
   OSA_REQUIRE(!final_obs || (final_mask && ld_final >= obs_dim));
   OSA_REQUIRE(!ep_acc || (ep_out && ep_count && ep_cap >= 0));
   TStore g = {*ring, n, obs_dim, act_dim, ld_obs, ld_act, ld_next, ld_final, obs, act, reward, cost, next_obs, final_obs,
-              terminated, truncated, final_mask, ep_acc, ep_out, ep_cap, ep_count};
+              terminated, truncated, final_mask, ep_acc, ep_out, ep_cap, ep_count, cn};
   hipLaunchKernelGGL(td3_store_kernel, dim3(1), dim3(256), 0, osa_stream(stream), g);
   OSA_CHECK_LAUNCH();
   return OSA_OK;
@@ -587,16 +859,19 @@ int osa_td3_draws(const osa_td3_desc* desc, unsigned long long seed, long first_
   return OSA_OK;
 }
 
-int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* s, const osa_td3_ring* ring,
-                 const osa_td3_draw_buffers* dr, float* stats, float* ws, size_t ws_floats, long update_count, int nsteps,
-                 void* stream) {
+// the step of osa_td3_step (lag null) and of osa_td3_lag_step
+static int td3_step_run(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* s,
+                        const osa_td3_lag* lag, const osa_td3_ring* ring, const osa_td3_draw_buffers* dr, float* stats,
+                        float* ws, size_t ws_floats, long update_count, int nsteps, void* stream) {
   TLayout lo;
   OSA_REQUIRE(desc && hp && s && ring && dr && stats && ws && nsteps >= 1 && update_count >= 0);
   int rc = td3_make_layout(desc, &lo);
   if (rc != OSA_OK) return rc;
   if ((rc = td3_route_ok(lo, hp->route)) != OSA_OK) return rc;
+  if (lag && (rc = td3_lag_ok(lo, lag)) != OSA_OK) return rc;
   const TWs w = td3_ws(lo);
-  OSA_REQUIRE(ws_floats >= w.total && (reinterpret_cast<uintptr_t>(ws) & 15) == 0);
+  const TLagWs x = lag ? td3_lag_ws(lo, w) : TLagWs{};
+  OSA_REQUIRE(ws_floats >= (lag ? x.total : w.total) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0);
   OSA_REQUIRE(s->actor && s->actor_m && s->actor_v && s->actor_t && s->critic && s->critic_m && s->critic_v &&
               s->critic_t && s->adam_step && s->step);
   OSA_REQUIRE(td3_ring_ok(ring, lo.D, lo.A) && dr->idx && dr->eps && dr->nslots >= 1);
@@ -632,24 +907,85 @@ int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_
       float* th = ws + w.hp[lo.pi.L - 1];
       hipLaunchKernelGGL(td3_pi_kernel, dim3(crr_blocks((long)B * lo.ldsa, 256)), dim3(256), 0, st, B, lo.A, lo.D, lo.lda,
                          lo.ldsa, th, ws + w.xq, ws + w.xc, ws + w.z[0][0]);
-      const CFwd qf = {s->critic, ws + w.xc, lo.ldsa, B, w.hq};
-      if ((rc = crr_forward(lo.q, &qf, 1, ws, st)) != OSA_OK) return rc;
-      if ((rc = td3_critic_dx(lo.q, s->critic, w.hq, w.z[0], w.dx, B, lo.ldsa, ws, st)) != OSA_OK) return rc;
-      hipLaunchKernelGGL(td3_dpi_kernel, dim3(crr_blocks((long)B * lo.lda, 256)), dim3(256), 0, st, B, lo.A, lo.D, lo.lda,
-                         lo.ldsa, ws + w.dx, th, ws + w.z[1][0]);
-      const CBwd pb = {s->actor, ws + w.xq, lo.ldsa, w.hp, {w.z[1][0], w.z[1][1]}, ws + w.gp};
+      if (!lag) {
+        const CFwd qf = {s->critic, ws + w.xc, lo.ldsa, B, w.hq};
+        if ((rc = crr_forward(lo.q, &qf, 1, ws, st)) != OSA_OK) return rc;
+        if ((rc = td3_critic_dx(lo.q, s->critic, w.hq, w.z[0], w.dx, B, lo.ldsa, ws, st)) != OSA_OK) return rc;
+        hipLaunchKernelGGL(td3_dpi_kernel, dim3(crr_blocks((long)B * lo.lda, 256)), dim3(256), 0, st, B, lo.A, lo.D,
+                           lo.lda, lo.ldsa, ws + w.dx, th, ws + w.z[1][0]);
+      } else {  // ddpg_lag.py:73-100: reward critic 0 and the cost critic, lambda read on the device
+        const float* qc = s->critic + nq * Pc;
+        const CFwd qf[2] = {{s->critic, ws + w.xc, lo.ldsa, B, w.hq}, {qc, ws + w.xc, lo.ldsa, B, x.hqc}};
+        if ((rc = crr_forward(lo.q, qf, 2, ws, st)) != OSA_OK) return rc;
+        hipLaunchKernelGGL(td3_lag_row_kernel, dim3(crr_blocks(B, 256)), dim3(256), 0, st, B, lag->multiplier,
+                           ws + w.hq[top], ws + x.hqc[top], ws + w.z[0][0], ws + w.z[2][0], ws + x.nl);
+        const bool gemm = lag->dact == OSA_TD3_LAG_DACT_GEMM;
+        int cur = 0;
+        if ((rc = td3_lag_critics_dx(lo, w, x, s->critic, gemm ? 1 : 0, ws, st, &cur)) != OSA_OK) return rc;
+        if (gemm) {
+          const TDact da = {{ws + w.z[0][cur], ws + w.z[2][cur]}, {s->critic + lo.q.oW[0], qc + lo.q.oW[0]}, th,
+                            ws + x.dzpi, B, lo.A, lo.D, lo.q.out[0], lo.q.ldh[0], lo.q.ld[0], lo.lda};
+          hipLaunchKernelGGL(td3_lag_dact_kernel, dim3((B + BC_ROWS - 1) / BC_ROWS), dim3(256), 0, st, da);
+        } else {
+          hipLaunchKernelGGL(td3_lag_dpi_kernel, dim3(crr_blocks((long)B * lo.lda, 256)), dim3(256), 0, st, B, lo.A,
+                             lo.D, lo.lda, lo.ldsa, ws + w.dx, ws + x.dxc, th, ws + x.dzpi);
+        }
+      }
+      const CBwd pb = {s->actor, ws + w.xq, lo.ldsa, w.hp, {lag ? x.dzpi : w.z[1][0], w.z[1][1]}, ws + w.gp};
       if ((rc = crr_backward(lo.pi, &pb, 1, B, ws, st)) != OSA_OK) return rc;
       double* apart = part + (long)2 * T_NB * 2;
       TNorm na = {{ws + w.gp, nullptr}, {s->actor, nullptr}, {lo.pi.P, 0}, {s->adam_step, nullptr}, apart, 0.f};
       hipLaunchKernelGGL(td3_norm_kernel, dim3(T_NB, 1), dim3(256), 0, st, na);
       TAdam aa = {lo.pi.Pn, 1, B, dr->nslots, 1, (long)lo.pi.P, 0, s->actor, s->actor_m, s->actor_v, s->actor_t, stats,
-                  ws + w.gp, nullptr, ws + w.hq[top], apart, s->adam_step, s->step, hp->lr_actor, hp->max_grad_norm, 0.f,
+                  ws + w.gp, nullptr, ws + (lag ? x.nl : w.hq[top]), apart, s->adam_step, s->step, hp->lr_actor, hp->max_grad_norm, 0.f,
                   hp->polyak, hp->one_minus_polyak, hp->beta1, hp->beta2, hp->adam_eps};
       hipLaunchKernelGGL(td3_adam_kernel, dim3(crr_blocks(lo.pi.Pn, 256), 1), dim3(256), 0, st, aa);
     }
     hipLaunchKernelGGL(td3_finish_kernel, dim3(1), dim3(64), 0, st, s->step);
     OSA_CHECK_LAUNCH();
   }
+  return OSA_OK;
+}
+
+int osa_td3_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* s, const osa_td3_ring* ring,
+                 const osa_td3_draw_buffers* dr, float* stats, float* ws, size_t ws_floats, long update_count, int nsteps,
+                 void* stream) {
+  return td3_step_run(desc, hp, s, nullptr, ring, dr, stats, ws, ws_floats, update_count, nsteps, stream);
+}
+
+size_t osa_td3_lag_ws_floats(const osa_td3_desc* desc) {
+  TLayout lo;
+  if (td3_make_layout(desc, &lo) != OSA_OK || !lo.cost) return 0;
+  return td3_lag_ws(lo, td3_ws(lo)).total;
+}
+
+size_t osa_td3_lag_dz_offset(const osa_td3_desc* desc) {
+  TLayout lo;
+  if (td3_make_layout(desc, &lo) != OSA_OK) return 0;
+  return td3_lag_ws(lo, td3_ws(lo)).dzpi;
+}
+
+int osa_td3_lag_step(const osa_td3_desc* desc, const osa_td3_hparams* hp, const osa_td3_state* s, const osa_td3_lag* lag,
+                     const osa_td3_ring* ring, const osa_td3_draw_buffers* dr, float* stats, float* ws, size_t ws_floats,
+                     long update_count, int nsteps, void* stream) {
+  OSA_REQUIRE(lag);
+  return td3_step_run(desc, hp, s, lag, ring, dr, stats, ws, ws_floats, update_count, nsteps, stream);
+}
+
+int osa_td3_multiplier_update(const osa_td3_lag* lag, const float* carry, int ncarry, const float* ep_out, long ep_cap,
+                              const long* ep_count, int update, float* stats, const long* step, int nslots,
+                              void* stream) {
+  OSA_REQUIRE(lag && lag->multiplier && lag->count && ep_out && ep_count && stats && step && nslots >= 1);
+  OSA_REQUIRE(ncarry >= 0 && (ncarry == 0 || carry) && ep_cap >= 0 && lag->window_lens >= 1);
+  if (lag->mode == OSA_TD3_LAG_ADAM) {
+    OSA_REQUIRE(lag->adam && lag->lambda_lr >= 0.0);
+  } else {
+    OSA_REQUIRE(lag->mode == OSA_TD3_LAG_PID && lag->pid && lag->pid_d_delay >= 1 &&
+                (reinterpret_cast<uintptr_t>(lag->pid) & 7) == 0);
+  }
+  TMult g = {*lag, carry, ep_out, ep_count, step, stats, ep_cap, ncarry, update, nslots};
+  hipLaunchKernelGGL(td3_multiplier_kernel, dim3(1), dim3(64), 0, osa_stream(stream), g);
+  OSA_CHECK_LAUNCH();
   return OSA_OK;
 }
 

@@ -12,7 +12,8 @@ import torch
 
 from . import _lib
 from . import envs as envs_mod
-from .config import BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, SAC_DEFAULTS, Config
+from .config import (BC_DEFAULTS, BCQ_DEFAULTS, DICE_DEFAULTS, OFFPOLICY_DEFAULTS, OFFPOLICY_LAG_DEFAULTS, SAC_DEFAULTS,
+                     Config)
 from .models import ConstraintActorCritic
 from .normalizer import Normalizer
 from .spaces import Box
@@ -138,12 +139,12 @@ def build_policy(cfgs, state, obs_dim: int, act_dim: int, device, extra_inputs: 
     """``(actor, normalizer)`` of a checkpoint (evaluator.py:174-177, 250-303); ``extra_inputs``: policy input columns
     behind the observation (the Saute / Simmer safety column); ``normalizer`` is None without ``obs_normalize``.  A
     VAE-BC run gives a ``VaePolicy``, a BCQ / BCQ-Lag run a ``BcqPolicy``, whose latent draws are seeded by ``seed``; a
-    DDPG / TD3 run gives an ``MlpPolicy``."""
+    DDPG / TD3 run, constrained or not, gives an ``MlpPolicy`` (the cost normaliser is not needed to play)."""
     if str(getattr(cfgs, 'algo', '')) in BC_DEFAULTS:
         return VaePolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     if str(getattr(cfgs, 'algo', '')) in BCQ_DEFAULTS:
         return BcqPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
-    if str(getattr(cfgs, 'algo', '')) in OFFPOLICY_DEFAULTS:
+    if str(getattr(cfgs, 'algo', '')) in (*OFFPOLICY_DEFAULTS, *OFFPOLICY_LAG_DEFAULTS):
         return MlpPolicy(cfgs, state, obs_dim, act_dim, device, seed), None
     if str(getattr(cfgs, 'algo', '')) in SAC_DEFAULTS:
         return SacPolicy(cfgs, state, obs_dim, act_dim, device, seed), None

@@ -8,6 +8,10 @@ current stream with no host synchronisation; ``stats`` holds the per-step scalar
 reads them.  Draws come from ``draw(seed, first_step, n)`` (Philox on the device, indices below the ring's fill count
 at that moment) or are injected with ``set_draws`` (tests).  ``OSA_TD3_ROUTE=layer|fused`` chooses how the step's
 forward runs: one tile-GEMM launch per layer, or one launch of the row-resident kernel.
+
+``Td3LagStep`` is the step of DDPGLag, TD3Lag, DDPGPID and TD3PID: the cost critic in the actor loss with the
+multiplier read on the device, ``update_multiplier`` (one launch per update round) and, with ``cost_normalize``, the
+cost normaliser inside ``store``.  ``OSA_TD3_LAG_DACT=stacked|gemm`` chooses layer 0 of the critics' data gradient.
 """
 from __future__ import annotations
 
@@ -320,4 +324,139 @@ class Td3Step(Td3Actor):  # pylint: disable=too-many-instance-attributes
         self.update_count += int(nsteps)
 
 
-__all__ = ['Td3Desc', 'Td3HParams', 'Td3Layout', 'Td3Actor', 'Td3Step', 'STAT_KEYS', 'make_desc', 'route_of']
+# ---------------------------------------------------------------------- TD3Lag / DDPGLag / TD3PID / DDPGPID
+LAG_STAT_KEYS = STAT_KEYS + ('Metrics/LagrangeMultiplier',)  # column 5: OSA_TD3_LAG_COL
+DACTS = {'gemm': 0, 'stacked': 1}  # OSA_TD3_LAG_DACT_*
+DEFAULT_DACT = 'stacked'           # the faster one at the YAML shape: 326 v 332 us per step
+DACT_MAX_WIDTH = 1024              # OSA_TD3_LAG_DACT_MAXW
+
+
+class Td3Lag(C.Structure):
+    """ctypes mirror of ``osa_td3_lag``."""
+
+    _fields_ = [('multiplier', C.c_void_p), ('adam', C.c_void_p), ('count', C.c_void_p), ('pid', C.c_void_p),
+                ('mode', C.c_int), ('dact', C.c_int), ('window_lens', C.c_int), ('pid_d_delay', C.c_int),
+                ('sum_norm', C.c_int), ('diff_norm', C.c_int), ('cost_limit', C.c_double), ('lambda_lr', C.c_double),
+                ('upper_bound', C.c_double), ('kp', C.c_double), ('ki', C.c_double), ('kd', C.c_double),
+                ('alpha_p', C.c_double), ('alpha_d', C.c_double), ('penalty_max', C.c_double)]
+
+
+def dact_of(desc: Td3Desc, name: str | None = None) -> int:
+    """How layer 0's data gradient of the constrained actor step runs: ``name`` or ``OSA_TD3_LAG_DACT`` where given --
+    ``gemm`` above a first critic width of DACT_MAX_WIDTH is an OsaError, not another kernel -- else the default where
+    it is supported and ``stacked`` where not."""
+    name = os.environ.get('OSA_TD3_LAG_DACT', '') if name is None else name
+    if name not in ('', *DACTS):
+        raise ValueError(f'OSA_TD3_LAG_DACT={name!r}: gemm or stacked')
+    dact = DACTS[name or DEFAULT_DACT]
+    if dact == DACTS['gemm'] and int(desc.hidden[1][0]) > DACT_MAX_WIDTH:
+        if name:
+            raise _lib.OsaError(f'OSA_TD3_LAG_DACT=gemm: a first critic layer wider than {DACT_MAX_WIDTH}')
+        dact = DACTS['stacked']
+    return dact
+
+
+def check_lagrange_cfgs(lagrange_cfgs: dict) -> str:
+    """``'pid'`` or ``'adam'`` for a ``lagrange_cfgs`` block; NotImplementedError, before any GPU is touched, for a
+    ``lambda_optimizer`` other than Adam (the device step restates torch.optim.Adam on the scalar)."""
+    if 'pid_kp' in lagrange_cfgs:
+        return 'pid'
+    if lagrange_cfgs.get('lambda_optimizer', 'Adam') != 'Adam':
+        raise NotImplementedError(f"lambda_optimizer {lagrange_cfgs['lambda_optimizer']!r}: the device multiplier "
+                                  "takes 'Adam' only")
+    return 'adam'
+
+
+class Td3LagStep(Td3Step):  # pylint: disable=too-many-instance-attributes
+    """``Td3Step`` with the cost critic in the actor loss (ddpg_lag.py:73-100), the multiplier on the device
+    (``multiplier``, float32 [1]; ``update_multiplier`` is lagrange.py / pid_lagrange.py as one launch) and, with
+    ``cost_normalize``, ``CostNormalize`` inside the store launch (``cost_normalizer``: mean, sumsq, count as doubles).
+    ``OSA_TD3_LAG_DACT=gemm|stacked`` chooses layer 0 of the critics' data gradient."""
+
+    def __init__(self, desc: Td3Desc, *, lagrange_cfgs: dict, window_lens: int, cost_normalize: bool = False,
+                 dact: str | None = None, **kw) -> None:
+        mode = check_lagrange_cfgs(lagrange_cfgs)
+        if not desc.use_cost:
+            raise ValueError('the constrained step needs the cost critic: use_cost')
+        self.dact = dact_of(desc, dact)
+        super().__init__(desc, **kw)
+        g, dev = dict(lagrange_cfgs), self.device
+        self.ws_floats = int(self._lib.osa_td3_lag_ws_floats(C.byref(desc)))
+        self.ws = torch.zeros(self.ws_floats, **self.f32)
+        init = float(g['lagrangian_multiplier_init'])
+        # lagrange.py:71-75: max(init, 0); pid_lagrange.py:77-83: the penalty starts at 0, the integral at init
+        self.initial_multiplier = 0.0 if mode == 'pid' else max(init, 0.0)
+        self.multiplier = torch.full((1,), self.initial_multiplier, **self.f32)
+        self.lag_adam = torch.zeros(2, **self.f32)
+        self.lag_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        depth = int(g.get('pid_d_delay', 1))
+        self.lag_pid = torch.zeros(3 + depth, dtype=torch.float64, device=dev)
+        self.lag_pid[0] = init
+        self.cost_normalizer = torch.zeros(3, dtype=torch.float64, device=dev) if cost_normalize else None
+        bound = g.get('lagrangian_upper_bound')
+        p = _lib.ptr
+        self._lag = Td3Lag(p(self.multiplier), p(self.lag_adam), p(self.lag_count), p(self.lag_pid),
+                           int(mode == 'pid'), self.dact, int(window_lens), depth, int(bool(g.get('sum_norm', False))),
+                           int(bool(g.get('diff_norm', False))), float(g['cost_limit']), float(g.get('lambda_lr', 0.0)),
+                           -1.0 if bound is None else float(bound), float(g.get('pid_kp', 0.0)),
+                           float(g.get('pid_ki', 0.0)), float(g.get('pid_kd', 0.0)),
+                           float(g.get('pid_delta_p_ema_alpha', 0.0)), float(g.get('pid_delta_d_ema_alpha', 0.0)),
+                           float(g.get('penalty_max', 0.0)))
+
+    def head_dz(self) -> torch.Tensor:
+        """The actor head's dz of the last actor step, padded: a view ``[batch][act_dim rounded up to 4]`` of the
+        workspace (intact after the step while the actor has one hidden layer: a deeper backward reuses it)."""
+        off, lda = int(self._lib.osa_td3_lag_dz_offset(C.byref(self.desc))), (self.A + 3) // 4 * 4
+        return self.ws[off:off + self.B * lda].view(self.B, lda)
+
+    def state_dict(self, which: str = 'actor'):
+        """``Td3Step.state_dict``; with ``cost_normalize`` the actor's carries the normaliser's running moments
+        ``[mean, sumsq, count]`` under ``cost_normalizer``.  The multiplier and its optimiser state are not saved."""
+        sd = super().state_dict(which)
+        if which == 'actor' and self.cost_normalizer is not None:
+            sd['cost_normalizer'] = self.cost_normalizer.clone()
+        return sd
+
+    def load_state_dict(self, sd, which: str = 'actor') -> None:
+        super().load_state_dict(sd, which)
+        if which == 'actor' and self.cost_normalizer is not None and 'cost_normalizer' in sd:
+            self.cost_normalizer.copy_(torch.as_tensor(sd['cost_normalizer'], dtype=torch.float64))
+
+    def store(self, obs, act, reward, cost, terminated, truncated, next_obs, final_obs=None, final_mask=None,
+              episodes: tuple | None = None) -> None:
+        """``Td3Step.store``; with ``cost_normalize`` the ring takes the normalised cost, the episodes the raw one."""
+        if self.cost_normalizer is None:
+            return super().store(obs, act, reward, cost, terminated, truncated, next_obs, final_obs, final_mask,
+                                 episodes)
+        n = int(obs.shape[0])
+        p = _lib.ptr
+        acc, out, count = episodes or (None, None, None)
+        _lib.check(self._lib.osa_td3_store_cn(
+            C.byref(self._ring), n, self.D, self.A, p(obs), obs.stride(0), p(act), act.stride(0), p(reward), p(cost),
+            p(terminated), p(truncated), p(next_obs), next_obs.stride(0), p(final_obs),
+            final_obs.stride(0) if final_obs is not None else 0, p(final_mask), p(acc), p(out),
+            int(out.shape[0]) if out is not None else 0, p(count), p(self.cost_normalizer), _lib.stream_ptr()),
+            'osa_td3_store_cn')
+        return None
+
+    def update_multiplier(self, carry, ncarry: int, episodes: tuple, update: bool = True) -> None:
+        """One launch after an update round: the multiplier's step on the mean cost of the last ``window_lens``
+        episodes of ``carry[:ncarry]`` and the running epoch's ``episodes`` (``update`` False: none), and the
+        multiplier into column 5 of the round's last statistics row."""
+        _, out, count = episodes
+        p = _lib.ptr
+        _lib.check(self._lib.osa_td3_multiplier_update(
+            C.byref(self._lag), p(carry), int(ncarry), p(out), int(out.shape[0]), p(count), int(bool(update)),
+            p(self.stats), p(self.step), self.nslots, _lib.stream_ptr()), 'osa_td3_multiplier_update')
+
+    def run(self, nsteps: int = 1) -> None:
+        """Enqueue ``nsteps`` gradient steps on the current stream (ddpg.py:382-400 with ddpg_lag.py:73-100)."""
+        _lib.check(self._lib.osa_td3_lag_step(
+            C.byref(self.desc), C.byref(self.hp), C.byref(self._state), C.byref(self._lag), C.byref(self._ring),
+            C.byref(self._draws), _lib.ptr(self.stats), _lib.ptr(self.ws), self.ws_floats, self.update_count,
+            int(nsteps), _lib.stream_ptr()), 'osa_td3_lag_step')
+        self.update_count += int(nsteps)
+
+
+__all__ = ['Td3Desc', 'Td3HParams', 'Td3Layout', 'Td3Actor', 'Td3Step', 'Td3Lag', 'Td3LagStep', 'STAT_KEYS',
+           'LAG_STAT_KEYS', 'make_desc', 'route_of', 'dact_of', 'check_lagrange_cfgs']
